@@ -82,7 +82,61 @@ def parse():
                          "without GPUs - gloo process group, the HIP emulation libraries of tests/native (the same device source compiled "
                          "for the host) in place of libmvgx_hip.so, the BA exchange through the callback transport over gloo, a tiny image "
                          "set and BA scene. The printed line carries \"rehearsal\": true.")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (rank 0's shard) as DIR/<name>.npy: "
+                         "see OutputDump")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+class OutputDump:
+    """--dump-outputs: the match lists the last timed pass delivered, captured batch by batch from the same pass (streamed) or read
+    from the context after it (--collect), written as float64 .npy files, < 64 MB in all:
+      match_counts.npy    (K, 3)  [I, J, number of matches] for every image pair, or a fixed seeded sample of 2^20 pairs if more
+      sample_matches.npy  (M, 4)  [I, J, i, j] the full lists of a fixed seeded sample of up to 1024 pairs (in pair order, cut at 32 MB)
+      stats.npy           (3,)    [image pairs, descriptor pairs, matches] of the pass
+    The descriptors and pair lists are seeded, so the same arguments give the same inputs on every run and build."""
+    SEED = 0x5EED0D
+    MAX_COUNT_PAIRS = 1 << 20
+    LIST_PAIRS = 1024
+    LIST_BYTES = 32 << 20
+
+    def __init__(self, pairs):
+        self.pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(self.pairs)
+        rng = np.random.default_rng(self.SEED)
+        self.count_idx = np.arange(n) if n <= self.MAX_COUNT_PAIRS else np.sort(rng.choice(n, self.MAX_COUNT_PAIRS, replace=False))
+        self.counts = np.full(len(self.count_idx), -1, np.int64)   # -1: a pair the pass never delivered
+        self.list_idx = np.sort(rng.choice(n, min(n, self.LIST_PAIRS), replace=False))
+        self.lists = {}
+
+    def on_batch(self, p0, off, ij):
+        """Lists of pairs [p0, p0 + len(off) - 1): offsets relative to the batch's ij. Cheap: a few hundred slices per pass."""
+        p1 = p0 + len(off) - 1
+        lo, hi = np.searchsorted(self.count_idx, [p0, p1])
+        k = self.count_idx[lo:hi] - p0
+        self.counts[lo:hi] = off[k + 1].astype(np.int64) - off[k].astype(np.int64)
+        lo, hi = np.searchsorted(self.list_idx, [p0, p1])
+        for p in self.list_idx[lo:hi]:
+            self.lists[int(p)] = np.array(ij[int(off[p - p0]):int(off[p - p0 + 1])])
+        return False   # (a true value would stop the run)
+
+    def write(self, out_dir, st):
+        os.makedirs(out_dir, exist_ok=True)
+        counts = np.concatenate([self.pairs[self.count_idx], self.counts[:, None]], axis=1).astype(np.float64)
+        rows, nbytes = [], 0
+        for p in self.list_idx:
+            m = self.lists.get(int(p), np.zeros((0, 2), np.uint32))
+            nbytes += m.shape[0] * 4 * 8
+            if nbytes > self.LIST_BYTES:
+                break
+            rows.append(np.concatenate([np.broadcast_to(self.pairs[p], (m.shape[0], 2)), m.astype(np.int64)], axis=1))
+        sample = np.concatenate(rows).astype(np.float64) if rows else np.zeros((0, 4))
+        stats = np.array([st.n_pairs, st.n_desc_pairs, st.n_matches], np.float64)
+        for name, a in (("match_counts", counts), ("sample_matches", sample), ("stats", stats)):
+            np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(descs, pairs, ratio, budget_s):
@@ -293,22 +347,23 @@ def main():
         if not rehearsal:
             torch.cuda.synchronize()
 
-    def one_pass():
+    def one_pass(on_batch=None):
         if args.collect:
             return ctx.run(pairs, ratio_sq, fetch=False)[0]
-        return ctx.run_stream(pairs, ratio_sq)      # every batch's lists reach host memory; nothing is kept
+        return ctx.run_stream(pairs, ratio_sq, on_batch)      # every batch's lists reach host memory; nothing is kept
 
     for _ in range(args.warmup):
         one_pass()
 
+    dump = OutputDump(pairs) if args.dump_outputs and rank == 0 else None
     kernel_ms = 0.0
     launches = 0
     desc_pairs = 0
     matches = 0
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        st = one_pass()
+    for step in range(args.steps):
+        st = one_pass(dump.on_batch if dump is not None and step == args.steps - 1 else None)
         kernel_ms += st.kernel_ms
         launches += int(st.n_kernel_launches)
         desc_pairs += int(st.n_desc_pairs)
@@ -316,6 +371,10 @@ def main():
         variant = int(st.variant)
     barrier()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        if args.collect:
+            dump.on_batch(0, *ctx.results(len(pairs)))
+        dump.write(args.dump_outputs, st)
 
     if world > 1:
         t = torch.tensor([dt, float(desc_pairs), kernel_ms, float(launches)], dtype=torch.float64, device=tdev)

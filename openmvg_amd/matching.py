@@ -178,14 +178,17 @@ class MatchContext:
         _capi.check(_capi.lib().mvgx_match_run(self._h, pairs.ctypes.data, pairs.shape[0], np.float32(ratio_sq), C.byref(st)))
         if not fetch:
             return st, None, None
+        return (st,) + self.results(pairs.shape[0])
+
+    def results(self, n):
+        """The lists of the last run() over n pairs: (offsets[n+1] uint64, ij[(n_matches, 2)] uint32), copied out."""
         po = C.POINTER(C.c_uint64)()
         pij = C.POINTER(C.c_uint32)()
         _capi.check(_capi.lib().mvgx_match_results(self._h, C.byref(po), C.byref(pij)))
-        n = pairs.shape[0]
         offsets = np.ctypeslib.as_array(po, shape=(n + 1,)).copy() if n + 1 > 0 else np.zeros(1, np.uint64)
         total = int(offsets[-1])
         ij = np.ctypeslib.as_array(pij, shape=(total, 2)).copy() if total else np.zeros((0, 2), np.uint32)
-        return st, offsets, ij
+        return offsets, ij
 
 
     def run_stream(self, pairs, ratio_sq, on_batch=None):

@@ -1,15 +1,19 @@
-# tests/native/adapter_harness.mk — TEST INFRASTRUCTURE ONLY.
+# oracle/adapter_harness.mk — TEST INFRASTRUCTURE ONLY.
 # Links the product's adapter objects (openmvg_amd/adapter/Makefile -> openmvg_amd/lib/adapter_obj/*.o) with the UNCHANGED
 # caller-side shims of oracle/ (ref_shim_{match,ba}.cpp: the same code that drives the reference in oracle/_ref), the
 # openMVG objects those callers and adapters still need (taken from oracle/_ref/obj, built by oracle/Makefile from the sources
 # under $(REF)) and libmvgx_hip.so. The parity tests then call identical entry points in oracle/_ref/libref_*.so (reference
-# TUs) and in tests/native/_build/libmvgx_openmvg_adapter{,_ba}.so (replacement TUs).
+# TUs) and in oracle/_ref/adapter/libmvgx_openmvg_adapter{,_ba,_geo}.so (replacement TUs).
+# The device builds live under oracle/_ref like the reference libraries: they need the openMVG tree, so they are made where it is
+# and are kept with oracle/_ref wherever the tests run. The emulation builds (target `emu`, CPU only) go to tests/native/_build beside the
+# emulation libraries of tests/_emu.py.
 # Two libraries, because the two halves are compiled with different Eigen ABIs (AVX2 for the matching objects, none for the
 # sfm / geometry objects) and must not share inline Eigen allocation code.
 REF ?= /root/reference/src
 HERE := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
-ROOT := $(abspath $(HERE)/../..)
-OUT := $(ROOT)/tests/native/_build
+ROOT := $(abspath $(HERE)/..)
+OUT := $(ROOT)/oracle/_ref/adapter
+EMU := $(ROOT)/tests/native/_build
 LIBDIR := $(ROOT)/openmvg_amd/lib
 AOBJ := $(LIBDIR)/adapter_obj
 REFOBJ := $(ROOT)/oracle/_ref/obj
@@ -53,10 +57,10 @@ GEO_FLAGS := $(BASEFLAGS) -I$(ROOT)/openmvg_amd/adapter -include $(ROOT)/openmvg
 $(OUT)/libmvgx_openmvg_adapter_geo.so: $(ROOT)/oracle/ref_shim_geofilter.cpp $(AOBJ)/mvgx_geometric_filter.o $(LIBDIR)/libmvgx_hip.so $(lastword $(MAKEFILE_LIST))
 	@mkdir -p $(OUT)
 	$(CXX) $(GEO_FLAGS) -shared -Wl,-Bsymbolic $(RPATH) -o $@ $(ROOT)/oracle/ref_shim_geofilter.cpp $(GEO_REF_SRCS) $(AOBJ)/mvgx_geometric_filter.o -L$(LIBDIR) -lmvgx_hip -lpthread
-$(OUT)/libmvgx_openmvg_adapter_geo_emu.so: $(ROOT)/oracle/ref_shim_geofilter.cpp $(AOBJ)/mvgx_geometric_filter.o $(OUT)/libmvgx_ba_emu.so $(lastword $(MAKEFILE_LIST))
-	@mkdir -p $(OUT)
-	$(CXX) $(GEO_FLAGS) -shared -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN' -o $@ $(ROOT)/oracle/ref_shim_geofilter.cpp $(GEO_REF_SRCS) $(AOBJ)/mvgx_geometric_filter.o -L$(OUT) -lmvgx_ba_emu -lpthread
-emu: $(OUT)/libmvgx_openmvg_adapter_geo_emu.so
+$(EMU)/libmvgx_openmvg_adapter_geo_emu.so: $(ROOT)/oracle/ref_shim_geofilter.cpp $(AOBJ)/mvgx_geometric_filter.o $(EMU)/libmvgx_ba_emu.so $(lastword $(MAKEFILE_LIST))
+	@mkdir -p $(EMU)
+	$(CXX) $(GEO_FLAGS) -shared -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN' -o $@ $(ROOT)/oracle/ref_shim_geofilter.cpp $(GEO_REF_SRCS) $(AOBJ)/mvgx_geometric_filter.o -L$(EMU) -lmvgx_ba_emu -lpthread
+emu: $(EMU)/libmvgx_openmvg_adapter_geo_emu.so
 
 $(OUT)/ref_shim_match.o: $(ROOT)/oracle/ref_shim_match.cpp
 	@mkdir -p $(OUT)
@@ -77,13 +81,13 @@ $(OUT)/libmvgx_openmvg_adapter_ba.so: $(OUT)/ref_shim_ba.o $(ADAPTER_BA_OBJS) $(
 
 # The matcher half once more, linked against the two emulation libraries instead of libmvgx_hip.so: the C++ routing code of the
 # adapter (region-type dispatch, batching, delivery threads) runs on the CPU test box (tests/test_adapter_emu_cpu.py).
-emu: $(OUT)/libmvgx_openmvg_adapter_emu.so
-$(OUT)/libmvgx_openmvg_adapter_emu.so: $(OUT)/ref_shim_match.o $(AOBJ)/mvgx_matcher_regions.o $(AOBJ)/mvgx_cascade_hashing_matcher_regions.o $(REF_MATCH_OBJS) $(OUT)/libmvgx_ba_emu.so $(OUT)/libmvgx_match_emu.so $(lastword $(MAKEFILE_LIST))
-	$(CXX) -shared -fopenmp -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN' -o $@ $(OUT)/ref_shim_match.o $(AOBJ)/mvgx_matcher_regions.o $(AOBJ)/mvgx_cascade_hashing_matcher_regions.o $(REF_MATCH_OBJS) -L$(OUT) -lmvgx_match_emu -lmvgx_ba_emu -lpthread
+emu: $(EMU)/libmvgx_openmvg_adapter_emu.so
+$(EMU)/libmvgx_openmvg_adapter_emu.so: $(OUT)/ref_shim_match.o $(AOBJ)/mvgx_matcher_regions.o $(AOBJ)/mvgx_cascade_hashing_matcher_regions.o $(REF_MATCH_OBJS) $(EMU)/libmvgx_ba_emu.so $(EMU)/libmvgx_match_emu.so $(lastword $(MAKEFILE_LIST))
+	$(CXX) -shared -fopenmp -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN' -o $@ $(OUT)/ref_shim_match.o $(AOBJ)/mvgx_matcher_regions.o $(AOBJ)/mvgx_cascade_hashing_matcher_regions.o $(REF_MATCH_OBJS) -L$(EMU) -lmvgx_match_emu -lmvgx_ba_emu -lpthread
 
-$(OUT)/libmvgx_openmvg_adapter_ba_emu.so: $(OUT)/ref_shim_ba.o $(ADAPTER_BA_OBJS) $(ADAPTER_BA_REF_OBJS) $(OUT)/libmvgx_ba_emu.so $(lastword $(MAKEFILE_LIST))
-	$(CXX) -shared -fopenmp -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN' -o $@ $(OUT)/ref_shim_ba.o $(ADAPTER_BA_OBJS) $(ADAPTER_BA_REF_OBJS) -L$(OUT) -lmvgx_ba_emu -lpthread
-emu: $(OUT)/libmvgx_openmvg_adapter_ba_emu.so
+$(EMU)/libmvgx_openmvg_adapter_ba_emu.so: $(OUT)/ref_shim_ba.o $(ADAPTER_BA_OBJS) $(ADAPTER_BA_REF_OBJS) $(EMU)/libmvgx_ba_emu.so $(lastword $(MAKEFILE_LIST))
+	$(CXX) -shared -fopenmp -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN' -o $@ $(OUT)/ref_shim_ba.o $(ADAPTER_BA_OBJS) $(ADAPTER_BA_REF_OBJS) -L$(EMU) -lmvgx_ba_emu -lpthread
+emu: $(EMU)/libmvgx_openmvg_adapter_ba_emu.so
 
 clean:
-	rm -f $(OUT)/libmvgx_openmvg_adapter.so $(OUT)/libmvgx_openmvg_adapter_ba.so $(OUT)/ref_shim_match.o $(OUT)/ref_shim_ba.o
+	rm -rf $(OUT)

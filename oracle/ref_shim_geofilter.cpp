@@ -237,7 +237,7 @@ void ref_five_point(const double* b1, const double* b2, double* Es_out, int* n_o
 // ---- container level: ImageCollectionGeometricFilter::Robust_model_estimation on an in-memory scene --------------------------
 // The same caller code is compiled twice: into oracle/_ref/libref_geofilter.so against the reference headers alone (the member
 // template of GeometricFilter.hpp is instantiated), and into the adapter harness with -include mvgx_geometric_filter.hpp, where
-// the explicit specialisation of openmvg_amd/adapter/mvgx_geometric_filter.cpp is linked instead (tests/native/adapter_harness.mk).
+// the explicit specialisation of openmvg_amd/adapter/mvgx_geometric_filter.cpp is linked instead (oracle/adapter_harness.mk).
 #include "openMVG/cameras/Camera_Pinhole_Radial.hpp"
 #include "openMVG/features/regions_factory.hpp"
 #include "openMVG/matching_image_collection/E_ACRobust.hpp"

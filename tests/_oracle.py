@@ -53,7 +53,7 @@ def have_ref_match():
 
 def _bind_match_shim(L):
     """Prototypes of oracle/ref_shim_match.cpp (the same caller code is linked into oracle/_ref/libref_match.so and,
-    against the MI355X replacements, into tests/native/_build/libmvgx_openmvg_adapter.so)."""
+    against the MI355X replacements, into oracle/_ref/adapter/libmvgx_openmvg_adapter.so)."""
     L.ref_matcher_regions_match_u8.restype = C.c_uint64
     L.ref_matcher_regions_match_u8.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p,
                                                C.c_uint64, C.c_float, SINK, C.c_void_p]
@@ -678,18 +678,20 @@ def ref_save_baf(scene, path):
 # ---------------------------------------------------------------------------------------------------------
 # the openMVG-side adapter build (product code + the same caller shims as oracle/_ref)
 # ---------------------------------------------------------------------------------------------------------
-ADAPTER_SO = os.path.join(ROOT, "tests", "native", "_build", "libmvgx_openmvg_adapter.so")
-ADAPTER_BA_SO = os.path.join(ROOT, "tests", "native", "_build", "libmvgx_openmvg_adapter_ba.so")
+ADAPTER_DIR = os.path.join(ROOT, "oracle", "_ref", "adapter")   # built beside the reference libraries: travels with oracle/_ref
+ADAPTER_SO = os.path.join(ADAPTER_DIR, "libmvgx_openmvg_adapter.so")
+ADAPTER_BA_SO = os.path.join(ADAPTER_DIR, "libmvgx_openmvg_adapter_ba.so")
+HARNESS_MK = os.path.join(ROOT, "oracle", "adapter_harness.mk")
 _adapter = None
 
 
 def build_adapter_harness(verbose=False):
-    """tests/native/adapter_harness.mk: the product's adapter objects + the reference's caller shims (needs the openMVG tree
-    and the objects of oracle/Makefile; a no-op elsewhere - the GPU box uses the prebuilt libraries)."""
+    """oracle/adapter_harness.mk: the product's adapter objects + the reference's caller shims (needs the openMVG tree
+    and the objects of oracle/Makefile; a no-op elsewhere, where the libraries already built under oracle/_ref/adapter are used)."""
     import subprocess
     if not os.path.isdir("/root/reference/src"):
         return None
-    subprocess.run(["make", "-f", os.path.join(ROOT, "tests", "native", "adapter_harness.mk")], check=True,
+    subprocess.run(["make", "-f", HARNESS_MK], check=True,
                    stdout=None if verbose else subprocess.DEVNULL)
     return ADAPTER_SO
 
@@ -699,7 +701,7 @@ _adapter_emu = None
 
 
 def adapter_emu():
-    """The matcher adapter linked against the HIP emulation libraries (tests/native/adapter_harness.mk, target `emu`): the
+    """The matcher adapter linked against the HIP emulation libraries (oracle/adapter_harness.mk, target `emu`): the
     adapter's C++ code on the CPU. None where the openMVG tree / reference objects are absent."""
     global _adapter_emu
     if _adapter_emu is None:
@@ -709,7 +711,7 @@ def adapter_emu():
             return None
         try:   # a missing prerequisite (reference objects, compiler) skips the emulated adapter tests instead of breaking collection
             _emu.build(); _emu.build_match()
-            subprocess.run(["make", "-f", os.path.join(ROOT, "tests", "native", "adapter_harness.mk"), "emu"], check=True,
+            subprocess.run(["make", "-f", HARNESS_MK, "emu"], check=True,
                            stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             _adapter_emu = _bind_match_shim(C.CDLL(ADAPTER_EMU_SO, mode=os.RTLD_LOCAL | os.RTLD_NOW | os.RTLD_DEEPBIND))
         except Exception:
@@ -935,7 +937,7 @@ def port_geofilter_h(tv, precision=4.0, max_iterations=2048):
 
 # ---- the geometric filter at container level: the same caller (oracle/ref_shim_geofilter.cpp::ref_geofilter_container) in the
 # reference library and in the adapter harness (explicit specialisation of openmvg_amd/adapter/mvgx_geometric_filter.cpp) ----
-ADAPTER_GEO_SO = os.path.join(ROOT, "tests", "native", "_build", "libmvgx_openmvg_adapter_geo.so")
+ADAPTER_GEO_SO = os.path.join(ADAPTER_DIR, "libmvgx_openmvg_adapter_geo.so")
 ADAPTER_GEO_EMU_SO = os.path.join(ROOT, "tests", "native", "_build", "libmvgx_openmvg_adapter_geo_emu.so")
 GEO_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32)
 _geo_libs = {}
