@@ -374,22 +374,27 @@ void Matcher_Regions::Match(const std::shared_ptr<sfm::Regions_Provider>& region
     // call of a process they cost what the plain-memory copies they replace cost (~100 ms at 1 000 x 2 000), later calls find them in place
     std::thread reserve_thread;
     struct JoinReserve { std::thread& t; ~JoinReserve() { if (t.joinable()) t.join(); } } join_reserve{reserve_thread};
+    const char* stage = "create";
     if (!inj && rc == MVGX_OK && ctx.l2) {
       const char* env = std::getenv("MVGX_ADAPTER_PINNED_RESULTS");
       const char* envb = std::getenv("MVGX_ADAPTER_BATCH_PAIRS");
-      const int64_t batch_pairs = envb ? std::max(1, std::atoi(envb)) : (1 << 14);
-      mvgx_match_set_option(ctx.l2, "stream_hold", 1);
-      mvgx_match_set_option(ctx.l2, "pinned_stream", env ? std::atoi(env) : 1);
-      mvgx_match_set_option(ctx.l2, "batch_pairs", batch_pairs);
+      // (clamped into the library's [1, 2^20]; every option is set on the kept context too, so a refused one is a device failure
+      // rather than the previous call's setting left in place)
+      const int64_t batch_pairs = envb ? std::min<int64_t>(1 << 20, std::max<int64_t>(1, std::strtoll(envb, nullptr, 10))) : (1 << 14);
+      rc = mvgx_match_set_option(ctx.l2, "stream_hold", 1);
+      if (rc == MVGX_OK) rc = mvgx_match_set_option(ctx.l2, "pinned_stream", env ? std::atoi(env) : 1);
+      if (rc == MVGX_OK) rc = mvgx_match_set_option(ctx.l2, "batch_pairs", batch_pairs);
+      if (rc != MVGX_OK) stage = "set_option";
       uint64_t sum_desc = 0;
       for (uint32_t v : n_desc) sum_desc += v;
       // a guess at a batch's lists: 0.4 matches per feature of the left image (dense synthetic sets reach 0.2, real image sets a tenth
       // of that), capped at 128 MB per buffer; a batch that exceeds its buffer re-pins it with headroom (the library's rule)
       const uint64_t words = std::min<uint64_t>((128u << 20) / 4, (uint64_t)(0.4 * 2.0 * (double)batch_pairs * (double)sum_desc / std::max<size_t>(n_desc.size(), 1)));
       mvgx_match_ctx* l2 = ctx.l2;
-      reserve_thread = std::thread([l2, words]() { (void)mvgx_match_set_option(l2, "stream_reserve", (int64_t)words); });   // (a failure here: the run allocates itself)
+      if (rc == MVGX_OK)
+        reserve_thread = std::thread([l2, words]() { (void)mvgx_match_set_option(l2, "stream_reserve", (int64_t)words); });   // (a failure here: the run allocates itself)
     }
-    if (step("create", rc, inj)) {
+    if (step(stage, rc, inj)) {
       inj = injected("match", "set_regions");
       if (!inj)
         rc = hamming ? mvgx_hamming_set_regions(ctx.hm, rows.data(), n_desc.data(), n_img, static_cast<uint32_t>(binary_len ? binary_len : 64))

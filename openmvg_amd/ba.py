@@ -184,6 +184,16 @@ class BaContext:
         _capi.check(_capi.lib().mvgx_ba_get_solver_info(self._h, C.byref(info)))
         return info
 
+    def speculation(self):
+        """test hook mvgx_debug_ba_speculation: (evaluations launched ahead of the accept decision, consumed as the next Jacobian, gate
+        stayed shut) since the context was created; a multi-device context sums its shards"""
+        f = _capi.lib().mvgx_debug_ba_speculation
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(3, np.uint64)
+        _capi.check(f(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
     def read_params(self):
         npz, ni, nx = self.shape
         poses = np.zeros((npz, 6)); intr = np.zeros((ni, 8)); pts = np.zeros((nx, 3))

@@ -3496,6 +3496,7 @@ struct mvgx_ba_ctx {
   int* d_accept = nullptr;             // device word: the accept decision of the step just computed (ba_publish_scalars_kernel)
   bool speculate = true;               // MVGX_BA_SPECULATE=0: the next Jacobian evaluation is launched after the host's decision, as before round 6
   bool spec_done = false;              // this step's Jacobian evaluation at x + delta is already enqueued, gated by d_accept
+  uint64_t spec_stats[3] = {0, 0, 0};  // since creation: evaluations launched ahead, consumed as the next Jacobian, gate stayed shut (mvgx_debug_ba_speculation)
   mvgx_allreduce_f64 allreduce = nullptr;
   void* allreduce_user = nullptr;
   mvgx::RcclComm* rccl = nullptr;
@@ -4150,6 +4151,7 @@ int speculative_evaluation(mvgx_ba_ctx* c, void* arg) {
   std::swap(d.poses, d.cposes); std::swap(d.intr, d.cintr); std::swap(d.pts, d.cpts);
   c->fail_clear = fail_clear; c->gmax_pending = gmax_pending; c->dmin = dmin; c->dmax = dmax;
   c->spec_done = rc == MVGX_OK;
+  if (c->spec_done) ++c->spec_stats[0];
   return rc;
 }
 
@@ -4290,6 +4292,7 @@ int lm_iteration(mvgx_ba_ctx* c, const mvgx_ba_options* opt) {
   c->gmax_resolved = false;
   int rc = compute_step(c, &ok, &model_cost_change, opt);
   if (rc) return rc;
+  if (c->spec_done && !((int)c->h_scalars[kSCount + 2] & 2)) ++c->spec_stats[2];   // (a rejected step, or one the tolerance tests end on)
   // The gradient test of this iteration's start, made now that the max |gradient| of the last Jacobian evaluation has come back
   // with the step's scalars (one host round trip per iteration instead of two): the step just computed is dropped, as if the
   // test had fired before it.
@@ -4323,6 +4326,7 @@ int lm_iteration(mvgx_ba_ctx* c, const mvgx_ba_options* opt) {
     c->x_cost = cand;   // the cost pass of the candidate IS the cost at the new x
     c->x_sqerr = c->h_scalars[kSSqErr];
     if (c->spec_done) {   // the evaluation at the new x is on its way: what it leaves on the host side
+      ++c->spec_stats[1];
       c->fail_clear = c->d.n_pichunks != 0;
       c->dmin = opt->min_lm_diagonal; c->dmax = opt->max_lm_diagonal;
       c->gmax_pending = true;
@@ -5467,6 +5471,16 @@ static int ba_update_impl(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_
   c->started = false; c->finished = false;
   c->gmax_pending = false; c->gmax_resolved = false; c->fail_clear = false; c->fold_cand_now = false; c->candidate_cost_done = false;
   drain.ok = true;
+  return MVGX_OK;
+}
+
+// Test hook (not declared in include/mvgx.h): what the speculative Jacobian evaluation did since the context was created - out[0]
+// evaluations launched ahead of the host's decision, out[1] of them consumed as the next iteration's Jacobian, out[2] of them whose
+// gate stayed shut (the device rejected the step or saw a tolerance test end the solve). A multi-device context sums its shards.
+int mvgx_debug_ba_speculation(mvgx_ba_ctx* c, uint64_t* out) {
+  MVGX_REQUIRE(c && out, MVGX_ERR_ARG, "mvgx_debug_ba_speculation: NULL argument");
+  if (c->multi) return mvgx::ba_multi_speculation(c->multi, out);
+  for (int k = 0; k < 3; ++k) out[k] = c->spec_stats[k];
   return MVGX_OK;
 }
 

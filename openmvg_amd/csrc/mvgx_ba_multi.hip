@@ -32,6 +32,8 @@
 #include "mvgx_ba_multi.h"
 #include "mvgx_common.h"
 
+extern "C" int mvgx_debug_ba_speculation(mvgx_ba_ctx* c, uint64_t* out);   // (test hook of mvgx_ba.hip)
+
 namespace mvgx {
 namespace {
 
@@ -396,6 +398,17 @@ int ba_multi_update(BaMulti* m, const mvgx_ba_problem* p) {
     if (r != 0) { sp.n_pose_priors = 0; sp.prior_pose = nullptr; sp.prior_center = nullptr; sp.prior_weight = nullptr; }
     return mvgx_ba_update(m->child[r], &sp);
   });
+}
+
+int ba_multi_speculation(BaMulti* m, uint64_t* out) {
+  for (int k = 0; k < 3; ++k) out[k] = 0;
+  for (int r = 0; r < m->n; ++r) {
+    uint64_t s[3];
+    const int rc = mvgx_debug_ba_speculation(m->child[r], s);
+    if (rc) return rc;
+    for (int k = 0; k < 3; ++k) out[k] += s[k];
+  }
+  return MVGX_OK;
 }
 
 int ba_multi_n_shards(const BaMulti* m) { return m->n; }

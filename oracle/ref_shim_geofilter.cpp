@@ -13,6 +13,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstring>
+#include <exception>
 #include <limits>
 #include <vector>
 
@@ -314,7 +315,11 @@ static uint64_t container_impl(const float* feat_xy, const uint8_t* descs, const
   }
   std::shared_ptr<sfm::Regions_Provider> base = provider;
   matching_image_collection::ImageCollectionGeometricFilter filter(&scene, base);
-  filter.Robust_model_estimation(Functor(precision, max_iterations), putative, guided != 0, distance_ratio);
+  try {   // (the reference's filter never throws; a replacement asked to - MVGX_ON_DEVICE_ERROR=throw - must not unwind into ctypes)
+    filter.Robust_model_estimation(Functor(precision, max_iterations), putative, guided != 0, distance_ratio);
+  } catch (const std::exception&) {
+    return UINT64_MAX;
+  }
   const matching::PairWiseMatches& out = filter.Get_geometric_matches();
   std::vector<uint32_t> buf;
   for (const auto& kv : out) {

@@ -171,7 +171,11 @@ uint64_t ref_matcher_regions_match_binary64(const uint8_t* const* desc_rows, con
   matching::PairWiseMatches out;
   matching_image_collection::Matcher_Regions matcher(dist_ratio, matching::BRUTE_FORCE_HAMMING);
   std::shared_ptr<sfm::Regions_Provider> base = provider;
-  matcher.Match(base, pairs, out, nullptr);
+  try {   // (as in ref_matcher_regions_match_u8: a replacement TU asked to throw must not unwind into ctypes)
+    matcher.Match(base, pairs, out, nullptr);
+  } catch (const std::exception&) {
+    return UINT64_MAX;
+  }
   std::vector<uint32_t> flat;
   for (const auto& kv : out) {
     flat.resize(kv.second.size() * 2);
@@ -203,7 +207,11 @@ uint64_t ref_matcher_regions_match_float64(const float* const* desc_rows, const 
   matching::PairWiseMatches out;
   matching_image_collection::Matcher_Regions matcher(dist_ratio, matching::BRUTE_FORCE_L2);
   std::shared_ptr<sfm::Regions_Provider> base = provider;
-  matcher.Match(base, pairs, out, nullptr);
+  try {   // (as in ref_matcher_regions_match_u8: a replacement TU asked to throw must not unwind into ctypes)
+    matcher.Match(base, pairs, out, nullptr);
+  } catch (const std::exception&) {
+    return UINT64_MAX;
+  }
   std::vector<uint32_t> flat;
   for (const auto& kv : out) {
     flat.resize(kv.second.size() * 2);
@@ -231,7 +239,11 @@ int ref_matcher_regions_match_u8_timed(const uint8_t* const* desc_rows, const ui
   matching_image_collection::Matcher_Regions matcher(dist_ratio, matching::BRUTE_FORCE_L2);
   std::shared_ptr<sfm::Regions_Provider> base = provider;
   const auto t0 = std::chrono::steady_clock::now();
-  matcher.Match(base, pairs, res, nullptr);
+  try {
+    matcher.Match(base, pairs, res, nullptr);
+  } catch (const std::exception&) {
+    return -1;
+  }
   out[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   uint64_t n = 0;
   for (const auto& kv : res) n += kv.second.size();
@@ -252,7 +264,11 @@ uint64_t ref_matcher_regions_match_liop144(const uint8_t* const* desc_rows, cons
   matching::PairWiseMatches out;
   matching_image_collection::Matcher_Regions matcher(dist_ratio, matching::BRUTE_FORCE_L2);
   std::shared_ptr<sfm::Regions_Provider> base = provider;
-  matcher.Match(base, pairs, out, nullptr);
+  try {   // (as in ref_matcher_regions_match_u8: a replacement TU asked to throw must not unwind into ctypes)
+    matcher.Match(base, pairs, out, nullptr);
+  } catch (const std::exception&) {
+    return UINT64_MAX;
+  }
   std::vector<uint32_t> flat;
   for (const auto& kv : out) {
     flat.resize(kv.second.size() * 2);
@@ -331,7 +347,11 @@ uint64_t ref_cascade_matcher_regions_match_u8(const uint8_t* const* desc_rows, c
   matching::PairWiseMatches out;
   matching_image_collection::Cascade_Hashing_Matcher_Regions matcher(dist_ratio);
   std::shared_ptr<sfm::Regions_Provider> base = provider;
-  matcher.Match(base, pairs, out, nullptr);
+  try {   // (as in ref_matcher_regions_match_u8: a replacement TU asked to throw must not unwind into ctypes)
+    matcher.Match(base, pairs, out, nullptr);
+  } catch (const std::exception&) {
+    return UINT64_MAX;
+  }
   std::vector<uint32_t> flat;
   for (const auto& kv : out) {
     flat.resize(kv.second.size() * 2);
@@ -364,7 +384,11 @@ static uint64_t cascade_match_typed(std::shared_ptr<features::Regions> (*make)(c
   matching::PairWiseMatches out;
   matching_image_collection::Cascade_Hashing_Matcher_Regions matcher(dist_ratio);
   std::shared_ptr<sfm::Regions_Provider> base = provider;
-  matcher.Match(base, pairs, out, nullptr);
+  try {   // (as in ref_matcher_regions_match_u8: a replacement TU asked to throw must not unwind into ctypes)
+    matcher.Match(base, pairs, out, nullptr);
+  } catch (const std::exception&) {
+    return UINT64_MAX;
+  }
   std::vector<uint32_t> flat;
   for (const auto& kv : out) {
     flat.resize(kv.second.size() * 2);

@@ -163,7 +163,8 @@ def ref_cascade_matcher_regions_match(descs, feats_xy, pairs, dist_ratio, lib=No
     cb = SINK(sink)
     L = lib or ref_match()
     L.ref_cascade_matcher_regions_match_u8.restype = C.c_uint64
-    L.ref_cascade_matcher_regions_match_u8(ptrs, xp, cnt, n, C.c_void_p(pairs.ctypes.data), C.c_uint64(len(pairs)), C.c_float(dist_ratio), cb, None)
+    if L.ref_cascade_matcher_regions_match_u8(ptrs, xp, cnt, n, C.c_void_p(pairs.ctypes.data), C.c_uint64(len(pairs)), C.c_float(dist_ratio), cb, None) == 2 ** 64 - 1:
+        raise RuntimeError("Cascade_Hashing_Matcher_Regions::Match threw")
     return out
 
 
@@ -191,7 +192,8 @@ def ref_cascade_matcher_regions_match_typed(kind, descs, feats_xy, pairs, dist_r
     L = lib or ref_match()
     f = getattr(L, "ref_cascade_matcher_regions_match_" + kind)
     f.restype = C.c_uint64
-    f(ptrs, xp, cnt, n, C.c_void_p(pairs.ctypes.data), C.c_uint64(len(pairs)), C.c_float(dist_ratio), cb, None)
+    if f(ptrs, xp, cnt, n, C.c_void_p(pairs.ctypes.data), C.c_uint64(len(pairs)), C.c_float(dist_ratio), cb, None) == 2 ** 64 - 1:
+        raise RuntimeError("Cascade_Hashing_Matcher_Regions::Match threw")
     return out
 
 
@@ -268,7 +270,8 @@ def ref_matcher_regions_match_binary64(descs, pairs, dist_ratio, lib=None):
         out[(int(I), int(J))] = np.ctypeslib.as_array(pij, shape=(int(n), 2)).copy()
 
     cb = SINK(sink)
-    Lr.ref_matcher_regions_match_binary64(ptrs, cnt, len(arrs), pairs.ctypes.data, len(pairs), np.float32(dist_ratio), cb, None)
+    if Lr.ref_matcher_regions_match_binary64(ptrs, cnt, len(arrs), pairs.ctypes.data, len(pairs), np.float32(dist_ratio), cb, None) == 2 ** 64 - 1:
+        raise RuntimeError("Matcher_Regions::Match threw")
     return out
 
 
@@ -314,7 +317,8 @@ def ref_matcher_regions_match_float64(descs, pairs, dist_ratio, lib=None):
         out[(int(I), int(J))] = np.ctypeslib.as_array(pij, shape=(int(n), 2)).copy()
 
     cb = SINK(sink)
-    Lr.ref_matcher_regions_match_float64(ptrs, cnt, len(arrs), pairs.ctypes.data, len(pairs), np.float32(dist_ratio), cb, None)
+    if Lr.ref_matcher_regions_match_float64(ptrs, cnt, len(arrs), pairs.ctypes.data, len(pairs), np.float32(dist_ratio), cb, None) == 2 ** 64 - 1:
+        raise RuntimeError("Matcher_Regions::Match threw")
     return out
 
 
@@ -332,7 +336,8 @@ def ref_matcher_regions_match_liop144(descs, pairs, dist_ratio, lib=None):
         out[(int(I), int(J))] = np.ctypeslib.as_array(pij, shape=(int(n), 2)).copy()
 
     cb = SINK(sink)
-    Lr.ref_matcher_regions_match_liop144(ptrs, cnt, len(arrs), pairs.ctypes.data, len(pairs), np.float32(dist_ratio), cb, None)
+    if Lr.ref_matcher_regions_match_liop144(ptrs, cnt, len(arrs), pairs.ctypes.data, len(pairs), np.float32(dist_ratio), cb, None) == 2 ** 64 - 1:
+        raise RuntimeError("Matcher_Regions::Match threw")
     return out
 
 
@@ -754,7 +759,7 @@ def adapter():
         for name in ("ref_matcher_regions_match_u8", "ref_matcher_regions_match_binary64", "ref_matcher_regions_match_float64",
                      "ref_matcher_regions_match_liop144", "ref_cascade_matcher_regions_match_u8", "ref_cascade_matcher_regions_match_float64",
                      "ref_cascade_matcher_regions_match_liop144", "ref_cascade_hash_u8", "mvgx_adapter_counters",
-                     "mvgx_adapter_cascade_last_hash_check"):   # (the counters of the matcher half: which route produced a container)
+                     "mvgx_adapter_cascade_last_hash_check", "mvgx_adapter_match_release_context"):   # (the counters of the matcher half: which route produced a container)
             setattr(both, name, getattr(m, name))
         for name in ("ref_ba_adjust", "ref_ba_adjust_ex", "ref_ba_prior_prepare", "ref_ba_filters", "ref_ba_filters_timed", "ref_ba_reject_loop", "ref_ba_adjust_growing", "mvgx_adapter_ba_context_stats", "mvgx_adapter_ba_context_stats3",
                      "mvgx_adapter_ba_release_context", "mvgx_adapter_ba_kept_solver_info"):
@@ -964,6 +969,12 @@ def geofilter_container_lib(kind):
     return lib
 
 
+def _geo_out(n, out):
+    if n == 2 ** 64 - 1:   # (the shim caught an exception out of Robust_model_estimation: MVGX_ON_DEVICE_ERROR=throw)
+        raise RuntimeError("Robust_model_estimation threw")
+    return out
+
+
 def geofilter_container(kind, feats_xy, image_wh, putative, precision=4.0, max_iterations=2048, guided=False, ratio=0.6, k1=0.0, descs=None, model="f", focal=0.0,
                         desc_type=0):
     """feats_xy: list of (n_k, 2) float32 positions; image_wh: (n_images, 2); putative: {(I, J): (n, 2) uint32}. -> {(I, J): (m, 2)}
@@ -990,23 +1001,23 @@ def geofilter_container(kind, feats_xy, image_wh, putative, precision=4.0, max_i
     if model == "eo":   # the orthographic essential functor: the E container's signature
         fn = lib.ref_geofilter_container_eo
         fn.restype = C.c_uint64
-        fn(P(fx), None if dd is None else P(dd), P(fstart), P(wh), C.c_uint32(len(feats_xy)), P(pij), P(mstart), P(mij), C.c_uint64(len(keys)),
+        n = fn(P(fx), None if dd is None else P(dd), P(fstart), P(wh), C.c_uint32(len(feats_xy)), P(pij), P(mstart), P(mij), C.c_uint64(len(keys)),
            C.c_double(precision), C.c_uint32(max_iterations), C.c_int(1 if guided else 0), C.c_double(ratio), C.c_double(focal), cb, None)
-        return out
+        return _geo_out(n, out)
     if model in ("ea", "eu"):   # the angular essential functors: (..., precision [degrees], max_iterations, upright, focal, sink, user)
         fn = lib.ref_geofilter_container_ea
         fn.restype = C.c_uint64
-        fn(P(fx), None if dd is None else P(dd), P(fstart), P(wh), C.c_uint32(len(feats_xy)), P(pij), P(mstart), P(mij), C.c_uint64(len(keys)),
+        n = fn(P(fx), None if dd is None else P(dd), P(fstart), P(wh), C.c_uint32(len(feats_xy)), P(pij), P(mstart), P(mij), C.c_uint64(len(keys)),
            C.c_double(precision), C.c_uint32(max_iterations), C.c_int(1 if model == "eu" else 0), C.c_double(focal), cb, None)
-        return out
+        return _geo_out(n, out)
     fn = lib.ref_geofilter_container if model == "f" else lib.ref_geofilter_container_h if model == "h" else lib.ref_geofilter_container_e
     if model == "e":   # (the k1 slot of the shim carries the focal length of the views' pinhole cameras)
         k1 = focal
     fn.restype = C.c_uint64
-    fn(P(fx), None if dd is None else P(dd), P(fstart), P(wh), C.c_uint32(len(feats_xy)), P(pij), P(mstart), P(mij),
+    n = fn(P(fx), None if dd is None else P(dd), P(fstart), P(wh), C.c_uint32(len(feats_xy)), P(pij), P(mstart), P(mij),
                                 C.c_uint64(len(keys)), C.c_double(precision), C.c_uint32(max_iterations), C.c_int(1 if guided else 0),
                                 C.c_double(ratio), C.c_double(k1), cb, None)
-    return out
+    return _geo_out(n, out)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import pytest
 
 from openmvg_amd import matching, synth
 from tests import _oracle
+from tests._adapter_route import device_route
 from tests.test_l2u8_cpu import liop_like
 
 pytestmark = pytest.mark.skipif(_oracle.adapter_emu() is None, reason="openMVG tree / adapter objects not present")
@@ -18,11 +19,12 @@ def _same(a, b):
         assert np.array_equal(a[k], b[k]), k
 
 
-def test_sift_uint8_route():
+def test_sift_uint8_route(monkeypatch):
     descs = synth.image_descriptors(5, n_desc=150, seed=11)
     descs[3] = descs[3][:0]; descs[4] = descs[4][:1]
     pairs = matching.exhaustive_pairs_array(5)
-    got = _oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter_emu())
+    with device_route(_oracle.adapter_emu(), len(pairs), monkeypatch):   # every view is SIFT_Regions, the empty one included
+        got = _oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter_emu())
     off, ij = _oracle.port_matcher_regions_match(descs, pairs, 0.8)
     want = _oracle.offsets_to_dict(pairs, off, ij)
     assert sum(len(v) for v in want.values()) > 20
@@ -39,14 +41,17 @@ def test_sift_route_on_the_devices_of_the_environment(monkeypatch):
     want = _oracle.offsets_to_dict(pairs, off, ij)
     for env in ("0,0", "0,0,0", "all"):
         monkeypatch.setenv("MVGX_DEVICES", env)
-        _same(_oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter_emu()), want)
+        with device_route(_oracle.adapter_emu(), len(pairs), monkeypatch):
+            got = _oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter_emu())
+        _same(got, want)
 
 
-def test_liop_uint8_144_route():
+def test_liop_uint8_144_route(monkeypatch):
     sizes = [120, 0, 130, 64, 1, 2]
     imgs = liop_like(sizes, 144, seed=21)
     pairs = matching.exhaustive_pairs_array(len(sizes))
-    got = _oracle.ref_matcher_regions_match_liop144(imgs, pairs, 0.8, lib=_oracle.adapter_emu())
+    with device_route(_oracle.adapter_emu(), len(pairs), monkeypatch):
+        got = _oracle.ref_matcher_regions_match_liop144(imgs, pairs, 0.8, lib=_oracle.adapter_emu())
     off, ij = _oracle.port_matcher_regions_match(imgs, pairs, 0.8, dim=144)
     want = _oracle.offsets_to_dict(pairs, off, ij)
     assert sum(len(v) for v in want.values()) > 20
@@ -55,15 +60,17 @@ def test_liop_uint8_144_route():
         _same(got, _oracle.ref_matcher_regions_match_liop144(imgs, pairs, 0.8))
 
 
-def test_binary_and_float_routes():
+def test_binary_and_float_routes(monkeypatch):
     sizes = [100, 0, 90, 1, 2]
     b = synth.binary_descriptors(len(sizes), sizes, seed=9)
     pairs = matching.exhaustive_pairs_array(len(sizes))
-    got = _oracle.ref_matcher_regions_match_binary64(b, pairs, 0.8, lib=_oracle.adapter_emu())
+    with device_route(_oracle.adapter_emu(), len(pairs), monkeypatch):
+        got = _oracle.ref_matcher_regions_match_binary64(b, pairs, 0.8, lib=_oracle.adapter_emu())
     off, ij = _oracle.port_matcher_regions_match_hamming(b, pairs, 0.8)
     _same(got, _oracle.offsets_to_dict(pairs, off, ij))
     f = synth.float_descriptors(len(sizes), sizes, seed=9)
-    got = _oracle.ref_matcher_regions_match_float64(f, pairs, 0.8, lib=_oracle.adapter_emu())
+    with device_route(_oracle.adapter_emu(), len(pairs), monkeypatch):
+        got = _oracle.ref_matcher_regions_match_float64(f, pairs, 0.8, lib=_oracle.adapter_emu())
     off, ij = _oracle.port_matcher_regions_match_f32(f, pairs, 0.8)
     want = _oracle.offsets_to_dict(pairs, off, ij)
     assert sum(len(v) for v in want.values()) > 10
@@ -79,14 +86,17 @@ def test_ratio_above_one_uses_the_reference_route():
 
 
 @pytest.mark.parametrize("tag", ["synthetic", "synthetic_grid", "sceaux"])
-def test_cascade_hashing_replacement_equals_the_reference_lists(tag):
+def test_cascade_hashing_replacement_equals_the_reference_lists(tag, monkeypatch):
     """Cascade_Hashing_Matcher_Regions::Match of the replacement TU (hashing stage = the reference's CascadeHasher on the host,
     matching stage = emulated device code, de-duplication = the reference's classes) against the reference's stored containers:
     same pairs, same lists in the same order - including the cases where the coordinate de-duplication removes matches"""
     from tests.test_cascade import load
     descs, xy, hs, bs, pairs, ref = load(tag)
+    # the device pairs: every pair whose image I has regions (the reference skips the others, Cascade_Hashing_Matcher_Regions.cpp:151-176)
+    n_dev = sum(1 for I, J in pairs if len(descs[int(I)]))
     for ratio in (0.8, 0.6):
-        got = _oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, ratio, lib=_oracle.adapter_emu())
+        with device_route(_oracle.adapter_emu(), n_dev, monkeypatch):
+            got = _oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, ratio, lib=_oracle.adapter_emu())
         _same(got, ref[int(ratio * 100)])
 
 

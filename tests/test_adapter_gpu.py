@@ -10,6 +10,7 @@ import pytest
 from openmvg_amd import synth
 from openmvg_amd import matching
 from tests import _oracle
+from tests._adapter_route import device_route
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not _oracle.have_adapter(), reason="adapter library not built (needs the openMVG tree)")]
 
@@ -52,14 +53,15 @@ def test_matcher_regions_replacement_ratio_above_one_uses_reference_route():
           _oracle.ref_matcher_regions_match(descs, pairs, 1.05))
 
 
-def test_matcher_regions_replacement_hamming_equals_reference():
+def test_matcher_regions_replacement_hamming_equals_reference(monkeypatch):
     """-n BRUTEFORCEHAMMING on AKAZE_Binary_Regions: the same caller shim linked against the reference TUs
     (oracle/_ref/libref_match.so) and against the MI355X replacement (adapter library)"""
     from openmvg_amd import matching, synth
     sizes = [300, 0, 257, 64, 1, 2, 500]
     imgs = synth.binary_descriptors(len(sizes), sizes, seed=9)
     pairs = matching.exhaustive_pairs_array(len(sizes))
-    got = _oracle.ref_matcher_regions_match_binary64(imgs, pairs, 0.8, lib=_oracle.adapter())
+    with device_route(_oracle.adapter(), len(pairs), monkeypatch):   # every view is AKAZE_Binary_Regions: every pair is a device pair
+        got = _oracle.ref_matcher_regions_match_binary64(imgs, pairs, 0.8, lib=_oracle.adapter())
     o_off, o_ij = _oracle.port_matcher_regions_match_hamming(imgs, pairs, 0.8)
     want = _oracle.offsets_to_dict(pairs, o_off, o_ij)
     assert sum(len(v) for v in want.values()) > 100
@@ -68,14 +70,15 @@ def test_matcher_regions_replacement_hamming_equals_reference():
         _same(got, _oracle.ref_matcher_regions_match_binary64(imgs, pairs, 0.8))
 
 
-def test_matcher_regions_replacement_float_equals_reference():
+def test_matcher_regions_replacement_float_equals_reference(monkeypatch):
     """-n BRUTEFORCEL2 on AKAZE_Float_Regions (64 floats): same caller shim, reference TUs vs the MI355X replacement;
     the lists are identical because the device sums in the reference's order"""
     from openmvg_amd import matching, synth
     sizes = [300, 0, 257, 64, 1, 2, 500]
     imgs = synth.float_descriptors(len(sizes), sizes, seed=9)
     pairs = matching.exhaustive_pairs_array(len(sizes))
-    got = _oracle.ref_matcher_regions_match_float64(imgs, pairs, 0.8, lib=_oracle.adapter())
+    with device_route(_oracle.adapter(), len(pairs), monkeypatch):
+        got = _oracle.ref_matcher_regions_match_float64(imgs, pairs, 0.8, lib=_oracle.adapter())
     o_off, o_ij = _oracle.port_matcher_regions_match_f32(imgs, pairs, 0.8)
     want = _oracle.offsets_to_dict(pairs, o_off, o_ij)
     assert sum(len(v) for v in want.values()) > 100
@@ -84,13 +87,14 @@ def test_matcher_regions_replacement_float_equals_reference():
         _same(got, _oracle.ref_matcher_regions_match_float64(imgs, pairs, 0.8))
 
 
-def test_matcher_regions_replacement_liop_equals_reference():
+def test_matcher_regions_replacement_liop_equals_reference(monkeypatch):
     """-n BRUTEFORCEL2 on AKAZE_Liop_Regions (144 x uint8): same caller shim, reference TUs vs the MI355X replacement"""
     from tests.test_l2u8_cpu import liop_like
     sizes = [300, 0, 257, 64, 1, 2, 500]
     imgs = liop_like(sizes, 144, seed=21)
     pairs = matching.exhaustive_pairs_array(len(sizes))
-    got = _oracle.ref_matcher_regions_match_liop144(imgs, pairs, 0.8, lib=_oracle.adapter())
+    with device_route(_oracle.adapter(), len(pairs), monkeypatch):
+        got = _oracle.ref_matcher_regions_match_liop144(imgs, pairs, 0.8, lib=_oracle.adapter())
     o_off, o_ij = _oracle.port_matcher_regions_match(imgs, pairs, 0.8, dim=144)
     want = _oracle.offsets_to_dict(pairs, o_off, o_ij)
     assert sum(len(v) for v in want.values()) > 50
@@ -151,9 +155,11 @@ def test_matcher_regions_replacement_uses_the_devices_of_the_environment(monkeyp
     descs = synth.image_descriptors(30, n_desc=700, seed=13)
     descs[4] = descs[4][:0]
     pairs = matching.exhaustive_pairs_array(30)
-    one = _oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter())
+    with device_route(_oracle.adapter(), len(pairs), monkeypatch):
+        one = _oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter())
     monkeypatch.setenv("MVGX_DEVICES", "0,0")
-    two = _oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter())
+    with device_route(_oracle.adapter(), len(pairs), monkeypatch):
+        two = _oracle.ref_matcher_regions_match(descs, pairs, 0.8, lib=_oracle.adapter())
     _same(one, two)
     off, ij = _oracle.port_matcher_regions_match(descs, pairs, 0.8)
     _same(two, _oracle.offsets_to_dict(pairs, off, ij))
@@ -178,15 +184,19 @@ def test_bundle_adjustment_ceres_replacement_on_the_devices_of_the_environment(n
 
 
 @pytest.mark.parametrize("tag", ["synthetic", "synthetic_grid", "sceaux"])
-def test_cascade_hashing_replacement_equals_the_reference_lists(tag):
+def test_cascade_hashing_replacement_equals_the_reference_lists(tag, monkeypatch):
     """-n CASCADEHASHINGL2 (main_ComputeMatches' default) through the replacement TU: hashing by the reference's CascadeHasher on
     the host, matching stage on the MI355X, the reference's de-duplication classes - containers equal the reference's stored ones
     (synthetic set with an empty image, a grid of repeated feature positions, the real SceauxCastle regions), order included"""
     from tests.test_cascade import load
     descs, xy, hs, bs, pairs, ref = load(tag)
+    # the device pairs: every pair whose image I has regions (the reference skips the others, Cascade_Hashing_Matcher_Regions.cpp:151-176)
+    n_dev = sum(1 for I, J in pairs if len(descs[int(I)]))
     for ratio in (0.8, 0.6):
-        got = _oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, ratio, lib=_oracle.adapter())
+        with device_route(_oracle.adapter(), n_dev, monkeypatch):
+            got = _oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, ratio, lib=_oracle.adapter())
         _same(got, ref[int(ratio * 100)])
     if _oracle.have_ref_match():    # and live against the reference TU at another ratio
-        _same(_oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, 0.9, lib=_oracle.adapter()),
-              _oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, 0.9))
+        with device_route(_oracle.adapter(), n_dev, monkeypatch):
+            got = _oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, 0.9, lib=_oracle.adapter())
+        _same(got, _oracle.ref_cascade_matcher_regions_match(descs, xy, pairs, 0.9))

@@ -13,6 +13,7 @@ import pytest
 
 from openmvg_amd import geofilter, synth
 from tests import _emu, _geofilter_cases as gc, _oracle
+from tests._adapter_route import device_route
 
 GOLD_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geofilter_angular.npz")
 FUNCTOR = geofilter.GeometricFilter_ESphericalMatrix_AC_Angular
@@ -96,21 +97,25 @@ def test_argument_errors_under_emulation():
 
 
 # ---- the drop-in: ImageCollectionGeometricFilter::Robust_model_estimation<GeometricFilter_ESphericalMatrix_AC_Angular<...>> ----
-def _container_case(kind, model):
+def _container_case(kind, model, monkeypatch=None):
     """calibrated pairs (every view but the last has a Pinhole_Intrinsic: the pair of the last view takes the functor's "no intrinsic
     information" branch) through the same caller, linked against the reference template or the adapter's specialisation; the
     geometric matches are the inliers that survive RelativePoseFromEssential"""
     from tests import _geofilter_scene
     feats, wh, putative = _geofilter_scene.collection(n_pairs=5, seed=12, n_min=40, n_max=70, inlier_frac=(0.6, 0.9), no_geometry_frac=0.2, size=(1000, 1000))
-    return _oracle.geofilter_container(kind, feats, wh, putative, max_iterations=512, model=model, focal=900.0)
+    if monkeypatch is None:
+        return _oracle.geofilter_container(kind, feats, wh, putative, max_iterations=512, model=model, focal=900.0)
+    last = len(feats) - 1   # the device pairs: both views calibrated
+    with device_route(_oracle.geofilter_container_lib(kind), sum(1 for k in putative if last not in k), monkeypatch):
+        return _oracle.geofilter_container(kind, feats, wh, putative, max_iterations=512, model=model, focal=900.0)
 
 
 @pytest.mark.parametrize("model", ["ea", "eu"])
-def test_adapter_specialisation_fills_the_container_like_the_reference_template(model):
+def test_adapter_specialisation_fills_the_container_like_the_reference_template(model, monkeypatch):
     ref_lib, lib = _oracle.geofilter_container_lib("reference"), _oracle.geofilter_container_lib("adapter_emu")
     if ref_lib is None or lib is None or not hasattr(ref_lib, "ref_geofilter_container_ea"):
         pytest.skip("needs /root/reference (reference library and adapter harness)")
-    want, got = _container_case("reference", model), _container_case("adapter_emu", model)
+    want, got = _container_case("reference", model), _container_case("adapter_emu", model, monkeypatch)
     assert set(want) == set(got) and len(want) >= 2 and (8, 9) not in want
     assert all(np.array_equal(want[k], got[k]) for k in want)
 
@@ -145,10 +150,10 @@ def test_device_equals_the_compiled_reference_on_mixed_sizes(upright):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("model", ["ea", "eu"])
-def test_adapter_specialisation_on_the_device(model):
+def test_adapter_specialisation_on_the_device(model, monkeypatch):
     ref_lib, lib = _oracle.geofilter_container_lib("reference"), _oracle.geofilter_container_lib("adapter")
     if ref_lib is None or lib is None or not hasattr(ref_lib, "ref_geofilter_container_ea"):
         pytest.skip("adapter harness / reference library not present")
-    want, got = _container_case("reference", model), _container_case("adapter", model)
+    want, got = _container_case("reference", model), _container_case("adapter", model, monkeypatch)
     assert set(want) == set(got) and len(want) >= 2
     assert all(np.array_equal(want[k], got[k]) for k in want)

@@ -7,6 +7,7 @@ import pytest
 
 from openmvg_amd import _capi, geofilter, synth
 from tests import _emu, _geofilter_cases as gc, _oracle
+from tests._adapter_route import device_route
 
 GOLD = np.load(__import__("os").path.join(__import__("os").path.dirname(__file__), "golden", "geofilter.npz"))
 
@@ -146,7 +147,7 @@ def test_emulated_global_table_form_equals_the_lds_form():
     assert np.array_equal(out["lds"][0], out["global"][0]) and out["lds"][1].tobytes() == out["global"][1].tobytes()
 
 
-def test_adapter_specialisation_fills_the_container_like_the_reference_template():
+def test_adapter_specialisation_fills_the_container_like_the_reference_template(monkeypatch):
     """ImageCollectionGeometricFilter::Robust_model_estimation<GeometricFilter_FMatrix_AC>: the same caller code linked once against
     the reference header's template and once against the explicit specialisation of openmvg_amd/adapter/mvgx_geometric_filter.cpp
     (device code under the HIP emulation): same pairs in the container, same match lists, with and without a distorting
@@ -158,7 +159,8 @@ def test_adapter_specialisation_fills_the_container_like_the_reference_template(
     feats, wh, putative = _geofilter_scene.collection(n_pairs=6, seed=9, n_min=40, n_max=70, inlier_frac=(0.6, 0.9), no_geometry_frac=0.2)
     for k1 in (0.0, 0.02):
         want = _oracle.geofilter_container("reference", feats, wh, putative, max_iterations=512, k1=k1)
-        got = _oracle.geofilter_container("adapter_emu", feats, wh, putative, max_iterations=512, k1=k1)
+        with device_route(emu_lib, len(putative), monkeypatch):   # every putative pair is a device pair
+            got = _oracle.geofilter_container("adapter_emu", feats, wh, putative, max_iterations=512, k1=k1)
         assert set(want) == set(got) and len(want) >= 2
         assert all(np.array_equal(want[k], got[k]) for k in want)
 

@@ -13,6 +13,7 @@ import pytest
 
 from openmvg_amd import _capi, geofilter, synth
 from tests import _emu, _geofilter_cases as gc, _oracle
+from tests._adapter_route import device_route
 
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geofilter_e.npz"))
 FUNCTOR = geofilter.GeometricFilter_EMatrix_AC
@@ -239,27 +240,38 @@ def test_host_bearings_give_the_same_inlier_sets_as_the_reference_cameras():
 
 
 # ---- the drop-in: ImageCollectionGeometricFilter::Robust_model_estimation<GeometricFilter_EMatrix_AC> ----
-def _container_case(kind, guided=False):
+def _container_case(kind, guided=False, monkeypatch=None):
     """a collection of calibrated pairs (every view but the last has a Pinhole_Intrinsic: the pairs of the last view take the functor's
-    "no intrinsic information" branch) through the same caller, linked against the reference template or the adapter's specialisation"""
+    "no intrinsic information" branch) through the same caller, linked against the reference template or the adapter's specialisation.
+    With `monkeypatch` the call runs under the route check: the device pairs are those whose two views have a pinhole intrinsic, and
+    (guided) every accepted one of them is guided on the device (SIFT rows)"""
     from tests import _geofilter_scene
     feats, wh, putative = _geofilter_scene.collection(n_pairs=5, seed=12, n_min=40, n_max=70, inlier_frac=(0.6, 0.9), no_geometry_frac=0.2, size=(1000, 1000))
-    return _oracle.geofilter_container(kind, feats, wh, putative, max_iterations=512, guided=guided, model="e", focal=900.0)
+    run = lambda: _oracle.geofilter_container(kind, feats, wh, putative, max_iterations=512, guided=guided, model="e", focal=900.0)   # noqa: E731
+    if monkeypatch is None:
+        return run()
+    last = len(feats) - 1
+    on_device = [k for k in putative if last not in k]
+    got = {}
+    with device_route(_oracle.geofilter_container_lib(kind), len(on_device), monkeypatch,
+                      guided=(lambda: (sum(k in got for k in on_device), 0)) if guided else None):
+        got.update(run())
+    return got
 
 
-def test_adapter_specialisation_fills_the_container_like_the_reference_template():
+def test_adapter_specialisation_fills_the_container_like_the_reference_template(monkeypatch):
     if _oracle.geofilter_container_lib("reference") is None or _oracle.geofilter_container_lib("adapter_emu") is None:
         pytest.skip("needs /root/reference (reference library and adapter harness)")
-    want, got = _container_case("reference"), _container_case("adapter_emu")
+    want, got = _container_case("reference"), _container_case("adapter_emu", monkeypatch=monkeypatch)
     assert set(want) == set(got) and len(want) >= 2 and (8, 9) not in want   # (the pair of the view without intrinsics is rejected by both)
     assert all(np.array_equal(want[k], got[k]) for k in want)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("guided", [False, True])
-def test_adapter_specialisation_on_the_device(guided):
+def test_adapter_specialisation_on_the_device(guided, monkeypatch):
     if _oracle.geofilter_container_lib("reference") is None or _oracle.geofilter_container_lib("adapter") is None:
         pytest.skip("adapter harness / reference library not present")
-    want, got = _container_case("reference", guided), _container_case("adapter", guided)
+    want, got = _container_case("reference", guided), _container_case("adapter", guided, monkeypatch)
     assert set(want) == set(got) and len(want) >= 2
     assert all(np.array_equal(want[k], got[k]) for k in want)

@@ -6,6 +6,7 @@ import pytest
 
 from openmvg_amd import _capi, geofilter, synth
 from tests import _geofilter_cases as gc, _oracle
+from tests._adapter_route import device_route
 from tests.test_geofilter_cpu import GOLD, _gold_tv
 
 pytestmark = pytest.mark.gpu
@@ -126,7 +127,7 @@ def test_container_form():
 
 
 @pytest.mark.parametrize("guided", [False, True])
-def test_adapter_specialisation_against_the_reference_template(guided):
+def test_adapter_specialisation_against_the_reference_template(guided, monkeypatch):
     """the drop-in (openmvg_amd/adapter/mvgx_geometric_filter.{hpp,cpp}) on the device against the reference's member template
     through identical caller code; guided matching runs the reference's own Geometry_guided_matching with the device's F"""
     from tests import _geofilter_scene
@@ -136,7 +137,9 @@ def test_adapter_specialisation_against_the_reference_template(guided):
     feats, wh, putative = _geofilter_scene.collection(n_pairs=200, seed=21, n_max=250)
     descs = [np.random.default_rng(7 + k).integers(0, 256, (len(f), 128), dtype=np.uint8) for k, f in enumerate(feats)] if guided else None
     want = _oracle.geofilter_container("reference", feats, wh, putative, guided=guided, ratio=0.8, descs=descs)
-    got = _oracle.geofilter_container("adapter", feats, wh, putative, guided=guided, ratio=0.8, descs=descs)
+    # every putative pair is a device pair (F model, finite precision); guided: every accepted pair is guided on the device (SIFT rows)
+    with device_route(dev_lib, len(putative), monkeypatch, guided=(lambda: (len(got), 0)) if guided else None):
+        got = _oracle.geofilter_container("adapter", feats, wh, putative, guided=guided, ratio=0.8, descs=descs)
     differing = [k for k in set(want) | set(got) if k not in want or k not in got or not np.array_equal(want[k], got[k])]
     from tests import _geofilter_cases as gc
     assert len(want) > 100 and len(differing) <= gc.allowed_differing(len(want), "f"), (len(want), len(got), differing[:5])

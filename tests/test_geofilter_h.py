@@ -10,6 +10,7 @@ import pytest
 
 from openmvg_amd import geofilter, synth
 from tests import _emu, _geofilter_cases as gc, _oracle
+from tests._adapter_route import device_route
 
 GOLD_H = np.load(os.path.join(os.path.dirname(__file__), "golden", "geofilter_h.npz"))
 FUNCTOR = geofilter.GeometricFilter_HMatrix_AC
@@ -163,7 +164,7 @@ def test_pairs_beyond_the_lds_classes_and_degenerate_inputs():
         assert np.array_equal(ref["mask"][lo:hi], mask[lo:hi]) or (ref["mask"][lo:hi] != mask[lo:hi]).mean() < 1e-3
 
 
-def _container_case(kind, guided=False):
+def _container_case(kind, monkeypatch, guided=False):
     from tests import _geofilter_scene
     ref_lib, lib = _oracle.geofilter_container_lib("reference"), _oracle.geofilter_container_lib(kind)
     if ref_lib is None or lib is None or not hasattr(ref_lib, "ref_geofilter_container_h"):
@@ -173,21 +174,23 @@ def _container_case(kind, guided=False):
                                                       no_geometry_frac=0.2, homography=True)
     for k1 in (0.0, 0.02):
         want = _oracle.geofilter_container("reference", feats, wh, putative, max_iterations=512, k1=k1, model="h", guided=guided)
-        got = _oracle.geofilter_container(kind, feats, wh, putative, max_iterations=512, k1=k1, model="h", guided=guided)
+        # every putative pair is a device pair; guided (ratio 0.6 > 0: the descriptor form): every accepted pair is guided on the device
+        with device_route(lib, len(putative), monkeypatch, guided=(lambda: (len(got), 0)) if guided else None):
+            got = _oracle.geofilter_container(kind, feats, wh, putative, max_iterations=512, k1=k1, model="h", guided=guided)
         assert set(want) == set(got) and len(want) >= 2
         n_same = sum(np.array_equal(want[k], got[k]) for k in want)
         assert n_same >= len(want) - (1 if big else 0), (n_same, len(want))
 
 
-def test_adapter_specialisation_fills_the_container_like_the_reference_template():
+def test_adapter_specialisation_fills_the_container_like_the_reference_template(monkeypatch):
     """ImageCollectionGeometricFilter::Robust_model_estimation<GeometricFilter_HMatrix_AC>: the same caller code
     (oracle/ref_shim_geofilter.cpp::ref_geofilter_container_h) linked against the reference header's template and against the explicit
     specialisation of openmvg_amd/adapter/mvgx_geometric_filter.cpp (device code under the HIP emulation): same pairs in the container,
     same match lists, with and without a distorting intrinsic"""
-    _container_case("adapter_emu")
+    _container_case("adapter_emu", monkeypatch)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("guided", [False, True])
-def test_adapter_specialisation_on_the_device(guided):
-    _container_case("adapter", guided)
+def test_adapter_specialisation_on_the_device(guided, monkeypatch):
+    _container_case("adapter", monkeypatch, guided)

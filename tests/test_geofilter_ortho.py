@@ -12,6 +12,7 @@ import pytest
 
 from openmvg_amd import _capi, geofilter, synth
 from tests import _emu, _oracle
+from tests._adapter_route import device_route
 
 GOLD_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geofilter_ortho.npz")
 FUNCTOR = geofilter.GeometricFilter_EOMatrix_RA
@@ -112,19 +113,30 @@ def test_host_mirror_and_argument_errors_under_emulation():
 
 
 # ---- the drop-in: ImageCollectionGeometricFilter::Robust_model_estimation<GeometricFilter_EOMatrix_RA> ----
-def _container_case(kind, guided=False):
+def _container_case(kind, guided=False, monkeypatch=None):
+    """with `monkeypatch`, under the route check: the device pairs are those whose two views have a pinhole intrinsic (every view but the
+    last); the orthographic model has no device guided matching, so (guided) its accepted pairs take the functor's own member function"""
     from tests import _geofilter_scene
     feats, wh, putative = _geofilter_scene.collection(n_pairs=5, seed=12, n_min=40, n_max=70, inlier_frac=(0.6, 0.9), no_geometry_frac=0.2, size=(1000, 1000))
-    return _oracle.geofilter_container(kind, feats, wh, putative, precision=2.0, max_iterations=512, guided=guided, model="eo", focal=900.0)
+    run = lambda: _oracle.geofilter_container(kind, feats, wh, putative, precision=2.0, max_iterations=512, guided=guided, model="eo", focal=900.0)   # noqa: E731
+    if monkeypatch is None:
+        return run()
+    last = len(feats) - 1
+    on_device = [k for k in putative if last not in k]
+    got = {}
+    with device_route(_oracle.geofilter_container_lib(kind), len(on_device), monkeypatch,
+                      guided=(lambda: (0, sum(k in got for k in on_device))) if guided else None):
+        got.update(run())
+    return got
 
 
 @pytest.mark.parametrize("guided", [False, True])
-def test_adapter_specialisation_fills_the_container_like_the_reference_template(guided):
+def test_adapter_specialisation_fills_the_container_like_the_reference_template(guided, monkeypatch):
     """(guided: the functor's Geometry_guided_matching returns no matches and the caller swaps them in - empty lists in both)"""
     ref_lib, lib = _oracle.geofilter_container_lib("reference"), _oracle.geofilter_container_lib("adapter_emu")
     if ref_lib is None or lib is None or not hasattr(ref_lib, "ref_geofilter_container_eo"):
         pytest.skip("needs /root/reference (reference library and adapter harness)")
-    want, got = _container_case("reference", guided), _container_case("adapter_emu", guided)
+    want, got = _container_case("reference", guided), _container_case("adapter_emu", guided, monkeypatch)
     assert set(want) == set(got) and len(want) >= 2 and (8, 9) not in want
     assert all(np.array_equal(want[k], got[k]) for k in want)
     assert guided == all(len(v) == 0 for v in want.values())
@@ -154,10 +166,10 @@ def test_device_is_bit_identical_to_the_compiled_reference_on_mixed_sizes():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("guided", [False, True])
-def test_adapter_specialisation_on_the_device(guided):
+def test_adapter_specialisation_on_the_device(guided, monkeypatch):
     ref_lib, lib = _oracle.geofilter_container_lib("reference"), _oracle.geofilter_container_lib("adapter")
     if ref_lib is None or lib is None or not hasattr(ref_lib, "ref_geofilter_container_eo"):
         pytest.skip("adapter harness / reference library not present")
-    want, got = _container_case("reference", guided), _container_case("adapter", guided)
+    want, got = _container_case("reference", guided), _container_case("adapter", guided, monkeypatch)
     assert set(want) == set(got) and len(want) >= 2
     assert all(np.array_equal(want[k], got[k]) for k in want)
