@@ -3864,44 +3864,53 @@ int factor_and_solve_sparse(mvgx_ba_ctx* c) {
   return MVGX_OK;
 }
 
+// The dense solver: factor the N x N lower triangle of S (column-major, leading dimension LD = N + 1, row N = the right-hand side)
+// in place and solve - zsol[0, N) receives the solution, fail[0] is raised by a pivot that is not positive. linv holds
+// (N + 63) / 64 blocks of 8192 doubles. The context (factor_and_solve) and the test hook mvgx_debug_dense_solve both run this
+// launch sequence; the two thresholds are the context's tuning values (MVGX_BA_TWO_LEVEL_MIN_N, MVGX_BA_UPDATE128_MIN_TILES).
+// Two-level blocking: outer panels of pw columns; inside a panel the classic 64-column steps update only the panel's
+// own columns, the rest of the trailing matrix gets one update per panel with K = pw. The trailing matrix is read and
+// written N / pw times instead of N / 64 (C5: the update is bound by that traffic). Small systems are launch-latency
+// bound instead and keep pw = 64 (= the classic right-looking sweep: no inner update, one full update per step).
+int dense_factor_and_solve(double* S, int N, int LD, double* linv_all, double* zsol, int* fail, hipStream_t stream, int two_level_min_n,
+                           int update128_min_tiles) {
+  const int pw_cfg = N >= two_level_min_n ? 256 : 64;
+  for (int p0 = 0; p0 < N; p0 += pw_cfg) {
+    const int pend = std::min(N, p0 + pw_cfg);
+    for (int k0 = p0; k0 < pend; k0 += 64) {
+      const int kb = std::min(64, pend - k0);
+      double* linv = linv_all + (size_t)(k0 / 64) * 8192;
+      hipLaunchKernelGGL(chol_diag_inv_kernel, dim3(1), dim3(256), kDiagLds, stream, S, LD, k0, kb, linv, fail);
+      const int rows_below = N + 1 - (k0 + kb);   // >= 1: the rhs row
+      hipLaunchKernelGGL(chol_panel_mfma_kernel, dim3((rows_below + 63) / 64), dim3(256), kPanelLds, stream, S, N, LD, k0, kb, linv);
+      if (k0 + kb < pend) {   // columns of this panel right of the block
+        const int ntr = (rows_below + 63) / 64, ntc = (pend - (k0 + kb) + 63) / 64;
+        hipLaunchKernelGGL(chol_update_mfma_kernel, dim3(ntr, ntc), dim3(256), 0, stream, S, N, LD, k0, kb, k0 + kb, pend);
+      }
+    }
+    if (pend < N) {   // everything right of the panel, K = panel width
+      const int nt = (N + 1 - pend + 63) / 64, nt2 = (N + 1 - pend + 127) / 128;
+      if (pw_cfg > 64 && nt2 * (nt2 + 1) / 2 >= update128_min_tiles)
+        hipLaunchKernelGGL(chol_update128_kernel, dim3(nt2, nt2), dim3(256), kUpd128Lds, stream, S, N, LD, p0, pend - p0, pend, N);
+      else
+        hipLaunchKernelGGL(chol_update_mfma_kernel, dim3(nt, nt), dim3(256), 0, stream, S, N, LD, p0, pend - p0, pend, N);
+    }
+  }
+  BA_LAUNCH_CHECK();
+  for (int b0 = ((N - 1) / 64) * 64; b0 >= 0; b0 -= 64) {
+    const int kb = std::min(64, N - b0);
+    hipLaunchKernelGGL(chol_backsolve_step_kernel, dim3(std::max(1, (b0 + 255) / 256)), dim3(256), 0, stream, S, N, LD, b0, kb,
+                       linv_all + (size_t)(b0 / 64) * 8192 + 4096, zsol);
+  }
+  BA_LAUNCH_CHECK();
+  return MVGX_OK;
+}
+
 int factor_and_solve(mvgx_ba_ctx* c) {
   Dev& d = c->d;
   if (!d.N) return MVGX_OK;
   if (d.sp.enabled) return factor_and_solve_sparse(c);
-  // two-level blocking: outer panels of pw columns; inside a panel the classic 64-column steps update only the panel's
-  // own columns, the rest of the trailing matrix gets one update per panel with K = pw. The trailing matrix is read and
-  // written N / pw times instead of N / 64 (C5: the update is bound by that traffic). Small systems are launch-latency
-  // bound instead and keep pw = 64 (= the classic right-looking sweep: no inner update, one full update per step).
-  const int pw_cfg = d.N >= c->two_level_min_n ? 256 : 64;
-  for (int p0 = 0; p0 < d.N; p0 += pw_cfg) {
-    const int pend = std::min(d.N, p0 + pw_cfg);
-    for (int k0 = p0; k0 < pend; k0 += 64) {
-      const int kb = std::min(64, pend - k0);
-      double* linv = d.linv + (size_t)(k0 / 64) * 8192;
-      hipLaunchKernelGGL(chol_diag_inv_kernel, dim3(1), dim3(256), kDiagLds, c->stream, d.S, d.LD, k0, kb, linv, d.fail);
-      const int rows_below = d.N + 1 - (k0 + kb);   // >= 1: the rhs row
-      hipLaunchKernelGGL(chol_panel_mfma_kernel, dim3((rows_below + 63) / 64), dim3(256), kPanelLds, c->stream, d.S, d.N, d.LD, k0, kb, linv);
-      if (k0 + kb < pend) {   // columns of this panel right of the block
-        const int ntr = (rows_below + 63) / 64, ntc = (pend - (k0 + kb) + 63) / 64;
-        hipLaunchKernelGGL(chol_update_mfma_kernel, dim3(ntr, ntc), dim3(256), 0, c->stream, d.S, d.N, d.LD, k0, kb, k0 + kb, pend);
-      }
-    }
-    if (pend < d.N) {   // everything right of the panel, K = panel width
-      const int nt = (d.N + 1 - pend + 63) / 64, nt2 = (d.N + 1 - pend + 127) / 128;
-      if (pw_cfg > 64 && nt2 * (nt2 + 1) / 2 >= c->update128_min_tiles)
-        hipLaunchKernelGGL(chol_update128_kernel, dim3(nt2, nt2), dim3(256), kUpd128Lds, c->stream, d.S, d.N, d.LD, p0, pend - p0, pend, d.N);
-      else
-        hipLaunchKernelGGL(chol_update_mfma_kernel, dim3(nt, nt), dim3(256), 0, c->stream, d.S, d.N, d.LD, p0, pend - p0, pend, d.N);
-    }
-  }
-  BA_LAUNCH_CHECK();
-  for (int b0 = ((d.N - 1) / 64) * 64; b0 >= 0; b0 -= 64) {
-    const int kb = std::min(64, d.N - b0);
-    hipLaunchKernelGGL(chol_backsolve_step_kernel, dim3(std::max(1, (b0 + 255) / 256)), dim3(256), 0, c->stream, d.S, d.N, d.LD, b0, kb,
-                       d.linv + (size_t)(b0 / 64) * 8192 + 4096, d.zsol);
-  }
-  BA_LAUNCH_CHECK();
-  return MVGX_OK;
+  return dense_factor_and_solve(d.S, d.N, d.LD, d.linv, d.zsol, d.fail, c->stream, c->two_level_min_n, c->update128_min_tiles);
 }
 
 // One-time agreement across ranks, before the first iteration:
@@ -5503,6 +5512,45 @@ int mvgx_debug_factor64(const double* a, int kb, double* l_out, double* linv_out
   MVGX_HIP(hipMemcpy(&fail, dfail, sizeof(int), hipMemcpyDeviceToHost));
   (void)hipFree(dA); (void)hipFree(dLi); (void)hipFree(dfail);
   MVGX_REQUIRE(fail == 0, MVGX_ERR_NUMERIC, "mvgx_debug_factor64: not positive definite");
+  return MVGX_OK;
+}
+
+// Test hook (not declared in include/mvgx.h): solve A x = b with the dense solver of the reduced camera system - the launch sequence
+// of the context (dense_factor_and_solve) on its layout (column-major, LD = n + 1, b in row n), with the two tuning thresholds given
+// explicitly. a: n x n column-major SPD (lower triangle read); x_out: n doubles. MVGX_ERR_NUMERIC when a pivot is not positive.
+int mvgx_debug_dense_solve(const double* a, const double* b, int n, int two_level_min_n, int update128_min_tiles, double* x_out) {
+  MVGX_REQUIRE(a && b && x_out && n > 0 && n < 46000, MVGX_ERR_ARG, "mvgx_debug_dense_solve: bad argument");
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_diag_inv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_panel_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds));
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_update128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kUpd128Lds));
+  const int ld = n + 1;
+  const size_t n_s = (size_t)n * ld, n_linv = (size_t)((n + 63) / 64) * 8192;
+  struct Bufs {
+    double *S = nullptr, *linv = nullptr, *z = nullptr; int* fail = nullptr;
+    ~Bufs() { (void)hipFree(S); (void)hipFree(linv); (void)hipFree(z); (void)hipFree(fail); }
+  } m;
+  MVGX_HIP(hipMalloc(reinterpret_cast<void**>(&m.S), n_s * sizeof(double)));
+  MVGX_HIP(hipMalloc(reinterpret_cast<void**>(&m.linv), n_linv * sizeof(double)));
+  MVGX_HIP(hipMalloc(reinterpret_cast<void**>(&m.z), (size_t)n * sizeof(double)));
+  MVGX_HIP(hipMalloc(reinterpret_cast<void**>(&m.fail), sizeof(int)));
+  {
+    std::vector<double> h(n_s);
+    for (int c = 0; c < n; ++c) {
+      std::memcpy(h.data() + (size_t)c * ld, a + (size_t)c * n, (size_t)n * sizeof(double));
+      h[(size_t)c * ld + n] = b[c];
+    }
+    MVGX_HIP(hipMemcpy(m.S, h.data(), n_s * sizeof(double), hipMemcpyHostToDevice));
+  }
+  MVGX_HIP(hipMemset(m.linv, 0, n_linv * sizeof(double)));
+  MVGX_HIP(hipMemset(m.z, 0, (size_t)n * sizeof(double)));
+  MVGX_HIP(hipMemset(m.fail, 0, sizeof(int)));
+  int rc = dense_factor_and_solve(m.S, n, ld, m.linv, m.z, m.fail, 0, two_level_min_n, update128_min_tiles);
+  if (rc) return rc;
+  MVGX_HIP(hipStreamSynchronize(0));
+  int fail = 0;
+  MVGX_HIP(hipMemcpy(&fail, m.fail, sizeof(int), hipMemcpyDeviceToHost));
+  MVGX_REQUIRE(fail == 0, MVGX_ERR_NUMERIC, "mvgx_debug_dense_solve: not positive definite");
+  MVGX_HIP(hipMemcpy(x_out, m.z, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MVGX_OK;
 }
 

@@ -6,6 +6,7 @@ same C ABI against the oracle. They check the index arithmetic of every kernel (
 blocked Cholesky with partial last block, back substitution, reductions) and the LM driver — what they cannot check is
 gfx950 code generation and timing, which the `-m gpu` tests and bench.py cover on the MI355X. Scenes are tiny: the
 emulation runs each workgroup as 64..1024 fibers."""
+import contextlib
 import ctypes as C
 import threading
 
@@ -444,29 +445,59 @@ def test_block_sparse_solver_on_a_ring_equals_dense_and_oracle(monkeypatch, leaf
     assert np.allclose(xs, opx, atol=1e-9) and np.allclose(ps, opp, atol=1e-9) and np.allclose(isn, opi, rtol=1e-9, atol=1e-9)
 
 
+@contextlib.contextmanager
+def _stderr_fd(out):
+    """collects what native code writes to file descriptor 2 inside the block (appended to the list `out`)"""
+    import os
+    import sys
+    import tempfile
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            yield
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+            tmp.seek(0)
+            out.append(tmp.read().decode(errors="replace"))
+
+
 def _lookahead_schedules_agree(monkeypatch, sc, iters, emulated):
-    """The block-sparse solve under its three schedules: level by level (rounds 2 - 4: factor, T, U launches per level), look-ahead (round 5:
+    """The block-sparse solve under its schedules: level by level (rounds 2 - 4: factor, T, U launches per level), look-ahead (round 5:
     one launch per level, the factor workgroups take the contributions of the level before themselves, the U tasks rebuild their strips
-    of L), and look-ahead with every level on its fall-back form (MVGX_BA_LOOKAHEAD_MAX_PRE=0: tasks first, then the factorisation). The
-    arithmetic and its order are the same by construction: every output must be equal bit for bit."""
-    import contextlib
+    of L), and look-ahead with every level on its fall-back form (MVGX_BA_LOOKAHEAD_MAX_PRE=0: tasks first, then the factorisation); the
+    reverse sweep as one polling launch (the default), as a launch per level under the chain kernel at the top of the tree
+    (MVGX_BA_BACKSOLVE_FLAGS=0), and as a launch per level all the way (... and MVGX_BA_BACKSOLVE_CHAIN=0); the chain levels of the
+    factorisation with their panel and update tasks in separate launches (MVGX_BA_CHAIN_FUSE=0). The arithmetic and its order are the
+    same by construction: every output must be equal bit for bit."""
+    import re
     from tests import _emu as emu
     out = {}
     for name, env in (("levels", {"MVGX_BA_LOOKAHEAD": "0"}), ("lookahead", {"MVGX_BA_LOOKAHEAD": "1"}),
                       ("fallback", {"MVGX_BA_LOOKAHEAD": "1", "MVGX_BA_LOOKAHEAD_MAX_PRE": "0"}), ("one", {"MVGX_BA_LOOKAHEAD": "1", "MVGX_BA_LOOKAHEAD_MAX_PRE": "1"}),
-                      ("flags", {"MVGX_BA_BACKSOLVE_FLAGS": "1"})):   # (the reverse sweep as one launch, columns handed over through flags)
+                      ("flags", {"MVGX_BA_BACKSOLVE_FLAGS": "1"}),   # (the reverse sweep as one launch)
+                      ("sweep_levels", {"MVGX_BA_BACKSOLVE_FLAGS": "0", "MVGX_BA_PLAN_DEBUG": "1"}),
+                      ("sweep_levels_no_chain", {"MVGX_BA_BACKSOLVE_FLAGS": "0", "MVGX_BA_BACKSOLVE_CHAIN": "0", "MVGX_BA_PLAN_DEBUG": "1"}),
+                      ("no_chain_fuse", {"MVGX_BA_CHAIN_FUSE": "0"})):
         monkeypatch.setenv("MVGX_BA_SOLVER", "sparse")
         monkeypatch.setenv("MVGX_BA_ND_LEAF_COLS", "64")
-        for k in ("MVGX_BA_LOOKAHEAD", "MVGX_BA_LOOKAHEAD_MAX_PRE", "MVGX_BA_BACKSOLVE_FLAGS"):
+        for k in ("MVGX_BA_LOOKAHEAD", "MVGX_BA_LOOKAHEAD_MAX_PRE", "MVGX_BA_BACKSOLVE_FLAGS", "MVGX_BA_BACKSOLVE_CHAIN", "MVGX_BA_CHAIN_FUSE",
+                  "MVGX_BA_PLAN_DEBUG"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        with (emu.emulated() if emulated else contextlib.nullcontext()):
+        err = []
+        with (emu.emulated() if emulated else contextlib.nullcontext()), _stderr_fd(err):
             ctx = ba.BaContext(sc)
             s = ctx.solve(ba.default_options(max_num_iterations=iters)); info = ctx.solver_info(); prm = ctx.read_params(); ctx.close()
         assert info.sparse == 1 and info.n_levels >= 3
+        if name.startswith("sweep_levels"):   # the chain kernel runs (or, switched off, does not): the plan says how many levels it takes
+            chain = [int(m) for m in re.findall(r"chain at the top (\d+) levels", err[0])]
+            assert chain and (chain[-1] >= 2 if name == "sweep_levels" else chain[-1] == 0), (name, chain)
         out[name] = (s.num_iterations, s.num_successful_steps, s.final_cost, s.final_rmse) + tuple(prm)
-    for name in ("lookahead", "fallback", "one", "flags"):
+    for name in ("lookahead", "fallback", "one", "flags", "sweep_levels", "sweep_levels_no_chain", "no_chain_fuse"):
         a, b = out["levels"], out[name]
         assert a[:4] == b[:4] and all(np.array_equal(x, y) for x, y in zip(a[4:], b[4:])), name
 
@@ -659,3 +690,25 @@ def test_factor_and_invert_kernel_against_numpy():
     from tests import _factor64
     _factor64.check_factor64(_emu.handle())
     _factor64.check_factor64_rejects_indefinite(_emu.handle())
+
+
+@pytest.mark.parametrize("tiles128", [1, 10 ** 6])
+def test_dense_solver_with_outer_panels_against_a_refined_solution(tiles128):
+    """the dense solver's production launch sequence (mvgx_debug_dense_solve) with 256-column outer panels forced onto narrow systems,
+    the deferred update on 128 x 128 tiles (tiles128 = 1) or on 64 x 64 tiles: random, Schur-shaped and ill-conditioned systems within
+    the backward / forward error bounds of tests/_dense_solve.py"""
+    from tests import _dense_solve
+    _dense_solve.check_widths(_emu.handle(), (65, 257, 300, 513), two_level_min_n=1, update128_min_tiles=tiles128)
+
+
+def test_dense_solver_default_form_against_a_refined_solution():
+    from tests import _dense_solve
+    _dense_solve.check_widths(_emu.handle(), (1, 6, 63, 64, 65, 130))
+
+
+@pytest.mark.parametrize("tiles128", [1, 10 ** 6])
+def test_dense_solver_reports_the_first_non_positive_pivot(tiles128):
+    """a pivot that turns negative in the first block, at a block edge, on either side of the 256-column panel edge or in the last column
+    fails the solve (MVGX_ERR_NUMERIC), and the next call on an SPD system succeeds"""
+    from tests import _dense_solve
+    _dense_solve.check_indefinite(_emu.handle(), 300, (0, 63, 64, 255, 256, 299), seed=5, two_level_min_n=1, update128_min_tiles=tiles128)

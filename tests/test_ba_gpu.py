@@ -439,3 +439,73 @@ def test_factor_and_invert_kernel_against_numpy():
     from tests import _factor64
     _factor64.check_factor64(_capi.lib())
     _factor64.check_factor64_rejects_indefinite(_capi.lib())
+
+
+# ---- the dense solver of the reduced camera system, on its own (mvgx_debug_dense_solve: the context's launch sequence) ------------
+# Widths at every change of form: one partial block, block edges, the panel edge at 256, the switch to 256-column outer panels at
+# 2048, the switch of the first deferred update from 64 x 64 to 128 x 128 tiles between 2175 and 2176, and a width above 4096 that
+# is not a multiple of 64.
+@pytest.mark.parametrize("n", [1, 6, 63, 64, 65, 255, 256, 257, 1208, 2047, 2048, 2049, 2175, 2176, 2305, 4161])
+def test_dense_solver_against_a_refined_solution(n):
+    from tests import _dense_solve
+    _dense_solve.check_widths(_capi.lib(), (n,))
+
+
+@pytest.mark.parametrize("tiles128", [1, 10 ** 6])
+def test_dense_solver_with_forced_outer_panels_against_a_refined_solution(tiles128):
+    from tests import _dense_solve
+    _dense_solve.check_widths(_capi.lib(), (65, 257, 300, 513), two_level_min_n=1, update128_min_tiles=tiles128)
+
+
+@pytest.mark.parametrize("kind", ["random", "schur", "illcond"])
+def test_dense_solver_one_and_two_level_forms_agree(kind):
+    from tests import _dense_solve
+    _dense_solve.check_one_and_two_level_agree(_capi.lib(), 2192, kind, seed=2192)
+
+
+@pytest.mark.parametrize("tiles128", [128, 10 ** 6])
+def test_dense_solver_reports_the_first_non_positive_pivot(tiles128):
+    """N = 2192 (two-level form; its deferred updates on 128 x 128 tiles, or on 64 x 64 tiles): a pivot turned to -delta at the first
+    column, at block and panel edges, past the first panel or at the last column fails the solve, and the next SPD call succeeds"""
+    from tests import _dense_solve
+    _dense_solve.check_indefinite(_capi.lib(), 2192, (0, 63, 64, 255, 256, 300, 2191), seed=6, update128_min_tiles=tiles128)
+
+
+def test_dense_schur_scene_at_a_two_level_width(monkeypatch):
+    """360 poses and 4 intrinsic groups: a reduced system of 2192 columns, which the dense solver factors with 256-column outer panels
+    and 128 x 128-tile deferred updates. Against the oracle, the block-sparse solver, the replacement TU's DENSE_SCHUR route (and the
+    reference's own DENSE_SCHUR run) and a two-shard context."""
+    from tests.test_ba_linear_solver import _kept_info
+    sc = synth.ba_scene(n_cams=360, n_points=12000, track_len=8, model=3, n_intr_groups=4, seed=78)
+    iters = 5
+    rc, osum, opp, opi, opx, _ = _oracle.port_ba_solve(sc, options=_oracle.default_ba_options(max_num_iterations=iters))
+    assert rc == 0
+    sd, info_d, pd, idn, xd = _solve_mode(sc, "dense", monkeypatch, ba.default_options(max_num_iterations=iters))
+    assert info_d.sparse == 0 and info_d.n_columns == 6 * 360 + 8 * 4 >= 2176
+    assert sd.num_iterations == osum.num_iterations and sd.num_successful_steps == osum.num_successful_steps
+    assert abs(sd.final_rmse - osum.final_rmse) < RMSE_TOL
+    assert abs(sd.final_cost - osum.final_cost) <= 1e-8 * osum.final_cost
+    ss, info_s, ps, isn, xs = _solve_mode(sc, "sparse", monkeypatch, ba.default_options(max_num_iterations=iters))
+    assert info_s.sparse == 1 and ss.num_iterations == sd.num_iterations
+    assert np.allclose(xs, xd, atol=1e-6) and np.allclose(ps, pd, atol=1e-6) and np.allclose(isn, idn, rtol=1e-6, atol=1e-6)
+    # two shards on one device, the dense solver on the summed system
+    monkeypatch.setenv("MVGX_BA_SOLVER", "dense")
+    monkeypatch.setenv("MVGX_BA_MULTI_MIN_OBS", "1")
+    monkeypatch.setenv("MVGX_BA_TRANSPORT", "peer")
+    many = ba.BaContext(sc, devices=[0, 0])
+    s2 = many.solve(ba.default_options(max_num_iterations=iters)); p2, i2, x2 = many.read_params(); many.close()
+    assert s2.num_iterations == sd.num_iterations and s2.num_successful_steps == sd.num_successful_steps
+    assert abs(s2.final_rmse - sd.final_rmse) < 1e-9 and abs(s2.final_cost - sd.final_cost) <= 1e-9 * sd.final_cost
+    assert np.allclose(p2, pd, atol=1e-6) and np.allclose(i2, idn, rtol=1e-6, atol=1e-6) and np.allclose(x2, xd, atol=1e-6)
+    for k in ("MVGX_BA_SOLVER", "MVGX_BA_MULTI_MIN_OBS", "MVGX_BA_TRANSPORT", "MVGX_BA_ND_LEAF_COLS"):
+        monkeypatch.delenv(k, raising=False)
+    # DENSE_SCHUR through the replacement TU: the kept context runs the dense solver
+    lib = _oracle.adapter()
+    lib.mvgx_adapter_ba_release_context()
+    rc, stats, *_ = _oracle.ref_ba_adjust_ex(sc, max_iterations=iters, linear_solver=1, lib=lib)
+    krc, info_a = _kept_info(lib)
+    lib.mvgx_adapter_ba_release_context()
+    assert rc == 0 and stats[3] == 1.0 and krc == 0 and info_a.sparse == 0 and info_a.n_columns == info_d.n_columns
+    if _oracle.have_ref_ba():   # the reference itself, DENSE_SCHUR
+        rrc, rstats, *_ = _oracle.ref_ba_adjust_ex(sc, max_iterations=iters, linear_solver=1)
+        assert rrc == 0 and abs(rstats[1] - stats[1]) < 1e-6
