@@ -3472,12 +3472,7 @@ int dev_upload_n(mvgx::Arena& pool, T** p, const T* v, size_t n, hipStream_t s) 
   return MVGX_OK;
 }
 template <typename T>
-int dev_upload(mvgx::Arena& pool, T** p, const std::vector<T>& v, hipStream_t s) {
-  int rc = dev_alloc(pool, p, v.size());
-  if (rc) return rc;
-  if (!v.empty()) MVGX_HIP(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-  return MVGX_OK;
-}
+int dev_upload(mvgx::Arena& pool, T** p, const std::vector<T>& v, hipStream_t s) { return dev_upload_n(pool, p, v.data(), v.size(), s); }
 
 }  // namespace
 
@@ -3537,10 +3532,11 @@ struct mvgx_ba_ctx {
   // 0.249): taking a contribution inside the factor workgroup costs the 6 us the separate task launch did, and the U tasks that rebuild their
   // strips of L do six times the MFMA work at a quarter of the occupancy. Off by default; kept as the cross-check of the schedule (tests).
   bool lookahead = false;
-  // reverse sweep of the block-sparse solve in ONE launch, columns handed over through device-scope flags (MVGX_BA_BACKSOLVE_FLAGS=1). Built and
-  // measured in round 5 (call r5_16): bit-identical, and SLOWER - C5 solve 0.474 against 0.409 ms, C3 0.246 against 0.245: a device-scope release on
-  // this eight-XCD part writes the producer's whole L2 back, a hand-over costs ~15 us where a launch boundary costs 10. Off by default.
-  bool bs_one_launch = true;    // the reverse sweep of the block-sparse solver as ONE launch (round 6: values polled, no flags - sp_backsolve_all_kernel); MVGX_BA_BACKSOLVE_FLAGS=0: a launch per level
+  // reverse sweep of the block-sparse solve in ONE launch (sp_backsolve_all_kernel: the consumers poll the solution's values). On by default;
+  // MVGX_BA_BACKSOLVE_FLAGS=0 runs a launch per level. Round 5's form of it handed the columns over through device-scope flags and was
+  // bit-identical but SLOWER (call r5_16: C5 solve 0.474 against 0.409 ms, C3 0.246 against 0.245): a device-scope release on this eight-XCD
+  // part writes the producer's whole L2 back, a hand-over cost ~15 us where a launch boundary costs 10.
+  bool bs_one_launch = true;
   unsigned bs_epoch = 0;       // number of the solve whose solution the flags of that launch announce
   int chain_fuse_max_tasks = 4096;   // single-column levels with at most this many update tasks run panel + update as one launch (MVGX_BA_CHAIN_FUSE=0: never)
   bool fold_cand_now = false;   // this step: set by compute_step before the solve
@@ -3556,6 +3552,11 @@ struct mvgx_ba_ctx {
   mvgx_sparse::Plan plan;          // host copy of the schedule (launch geometry per level)
   int update128_min_tiles = 128;   // tuning (MVGX_BA_UPDATE128_MIN_TILES): deferred updates with at least this many 128 x 128 tiles use them
   int two_level_min_n = 2048;   // tuning (MVGX_BA_TWO_LEVEL_MIN_N): reduced systems at least this wide factor with 256-column outer panels
+  // settings of the structure build (read_settings)
+  bool groups_on = true;        // MVGX_BA_GROUPS=0: no point groups
+  int sg_max_groups = 0;        // groups per supergroup at most (MVGX_BA_SG_GROUPS)
+  bool sg_index_order = false;  // MVGX_BA_SG_INDEX_ORDER: supergroups launched in the order of construction (A/B runs), not largest first
+  bool generic_models = false;  // MVGX_BA_GENERIC_MODELS=1: the point-group kernels keep the spherical / fisheye branches whatever the models
   // phase timing (MVGX_BA_PHASE_TIMING=1 at create): HIP events around the five phases of an iteration, summed into phase_ms
   bool phase_timing = false;
   struct Mark { int id; hipEvent_t a, b; };
@@ -4485,7 +4486,871 @@ void ba_ctx_comm_abort(mvgx_ba_ctx* c) {
 }
 }  // namespace mvgx
 
-namespace mvgx { bool ba_create_plan_deferred(); }
+namespace {
+// ---- mvgx_ba_create in stages ----
+
+// MVGX_BA_CREATE_TIMING=1: phase times of mvgx_ba_create on stderr (host structure vs allocation vs upload)
+struct CreateTimer {
+  const bool on = getenv("MVGX_BA_CREATE_TIMING") != nullptr;
+  const std::chrono::steady_clock::time_point t_enter = std::chrono::steady_clock::now();
+  std::chrono::steady_clock::time_point t_prev = t_enter;
+  void operator()(const char* what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[mvgx_ba_create] %-36s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+    t_prev = now;
+  }
+  void total() { t_prev = t_enter; (*this)("total (before the locals are released)"); }
+};
+
+// Every environment setting of a context, read once by mvgx_ba_create (after the counts of Dev are set).
+void read_settings(mvgx_ba_ctx* c) {
+  if (const char* env = getenv("MVGX_BA_SPECULATE")) c->speculate = atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_POLL_SCALARS")) c->poll_scalars = c->poll_scalars && atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_SEPARATE_COST")) c->fold_candidate = atoi(env) == 0;
+  if (const char* env = getenv("MVGX_BA_CHAIN_FUSE")) c->chain_fuse_max_tasks = atoi(env);
+  if (const char* env = getenv("MVGX_BA_LOOKAHEAD")) c->lookahead = atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_BACKSOLVE_FLAGS")) c->bs_one_launch = atoi(env) != 0;
+  c->phase_timing = getenv("MVGX_BA_PHASE_TIMING") != nullptr;
+  if (getenv("MVGX_BA_FACTOR_DEBUG")) { const int one = 1; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_factor_debug), &one, sizeof(one)); }
+  {   // (a synchronous copy: only when the setting changes)
+    static std::atomic<int> last_on{0};
+    const int on = getenv("MVGX_BA_GROUP_DEBUG") ? 1 : 0;
+    if (last_on.exchange(on) != on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_group_debug), &on, sizeof(on));
+    static std::atomic<int> last_compact{1};
+    const char* env_c = getenv("MVGX_BA_GROUP_COMPACT");
+    const int compact_on = env_c ? (atoi(env_c) != 0) : 1;
+    if (last_compact.exchange(compact_on) != compact_on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_group_compact), &compact_on, sizeof(compact_on));
+  }
+  if (const char* env = getenv("MVGX_BA_MODEL_COST")) c->model_cost_from_jacobian = !strcmp(env, "jacobian");
+  if (const char* env = getenv("MVGX_BA_SOLVER")) {
+    c->solver_mode = !strcmp(env, "dense") ? 1 : !strcmp(env, "sparse") ? 2 : 0;
+    c->solver_from_env = true;   // ("auto" included: the library's rule, whatever the caller's options say)
+  }
+  if (const char* env = getenv("MVGX_BA_TWO_LEVEL_MIN_N")) c->two_level_min_n = std::max(1, atoi(env));
+  if (const char* env = getenv("MVGX_BA_UPDATE128_MIN_TILES")) c->update128_min_tiles = std::max(1, atoi(env));
+  // MVGX_BA_GROUPS=0 disables the point groups; so does MVGX_BA_MODEL_COST=jacobian (Ceres' form of the model cost reads the Jacobian
+  // records of every observation).
+  if (const char* env = getenv("MVGX_BA_GROUPS")) c->groups_on = atoi(env) != 0;
+  // A supergroup covers up to 2048 observations (8 groups); problems of 4 M observations and more - enough supergroups to fill the device
+  // several times either way - up to 4096 (16 groups): fewer prologues, MFMA flushes and partial blocks. MVGX_BA_SG_GROUPS=n sets the
+  // limit (sweeps of calls 83 / 84 / 86 with the largest-first launch order: C3 0.625 ms at 8, 0.654 at 12, 0.715 at 16, 0.726 at 6;
+  // C5 1.747 ms at 8, 1.729 at 12, 1.714 at 16, 1.754 at 24, 1.914 at 6).
+  c->sg_max_groups = c->d.n_obs >= 4000000ull ? 4096 / kGroupThreads : 2048 / kGroupThreads;
+  if (const char* env = getenv("MVGX_BA_SG_GROUPS")) c->sg_max_groups = std::max(1, std::min(64, atoi(env)));
+  c->sg_index_order = getenv("MVGX_BA_SG_INDEX_ORDER") != nullptr;
+  if (const char* env = getenv("MVGX_BA_GENERIC_MODELS")) c->generic_models = atoi(env) != 0;
+}
+
+constexpr size_t kObsGrain = 16384;   // observations per work item of the structure build's loops
+inline size_t obs_grains(uint64_t no) { return (size_t)((no + kObsGrain - 1) / kObsGrain); }
+
+// Which blocks carry a residual of the observations that are on (obs_enabled null: all of them) - the poses of the priors included -,
+// and how many of those observations count in the RMSE (not control points). With a subset, off[k] marks the point-order positions k
+// whose observation (the caller's perm[k]) is off. (Host threads: the flags are bytes that only ever receive 1, the counts are summed
+// per grain; neither depends on the order the observations are visited in.)
+struct UsedBlocks { std::vector<uint8_t> pose, intr, pt, off; double n_rmse = 0; bool any_off = false; };
+UsedBlocks used_blocks(const mvgx_ba_problem* p, const std::vector<uint32_t>& perm, const uint8_t* obs_enabled) {
+  const uint64_t no = p->n_obs;
+  const size_t n_grains = obs_grains(no);
+  UsedBlocks u;
+  u.pose.assign(p->n_poses, 0); u.intr.assign(p->n_intrinsics, 0); u.pt.assign(p->n_points, 0);
+  if (obs_enabled) u.off.assign((size_t)std::max<uint64_t>(no, 1), 0);
+  std::vector<double> cnt(n_grains, 0.0);
+  std::vector<uint8_t> any_off(n_grains, 0);
+  parallel_for_dynamic(n_grains, 1, host_threads(no), [&](size_t g, unsigned) {
+    // (read before write: a few hundred flag bytes stored to by every thread for every observation bounce between the cores;
+    // relaxed atomic accesses: several host threads set the same byte - the only value it ever receives is 1)
+    auto set_flag = [](uint8_t& f) { if (!__atomic_load_n(&f, __ATOMIC_RELAXED)) __atomic_store_n(&f, (uint8_t)1, __ATOMIC_RELAXED); };
+    double n = 0;
+    for (uint64_t k = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); k < e; ++k) {
+      const uint64_t s_ = obs_enabled && !perm.empty() ? perm[k] : k;
+      if (obs_enabled && !obs_enabled[s_]) { u.off[k] = 1; any_off[g] = 1; continue; }
+      set_flag(u.pose[p->obs_pose[s_]]); set_flag(u.intr[p->obs_intr[s_]]); set_flag(u.pt[p->obs_point[s_]]);
+      n += (p->obs_is_control && p->obs_is_control[s_]) ? 0.0 : 1.0;
+    }
+    cnt[g] = n;
+  });
+  for (size_t g = 0; g < n_grains; ++g) { u.n_rmse += cnt[g]; u.any_off = u.any_off || any_off[g]; }
+  for (uint32_t k = 0; k < p->n_pose_priors; ++k) u.pose[p->prior_pose[k]] = 1;
+  return u;
+}
+
+// The host-side structure of a context (the analogue of Ceres' preprocessor: ordering, chunks, block structure), a function of the
+// fingerprinted structure alone. The build_* stages fill it and enqueue no device work; upload_observation_lists and upload_structure
+// take it to the device. The large lists live in the create call's mvgx::HostArena.
+struct HostStructure {
+  unsigned T = 1;                                                 // host threads of the build
+  // point order: the observations sorted by point (stable); sorted: the caller's list already is, its arrays are read where they lie
+  bool sorted = true;
+  std::vector<uint32_t> pt_start;                                 // [point]: its first observation
+  const uint32_t *opose = nullptr, *ointr = nullptr, *opt = nullptr;   // the observation lists in point order (the caller's, or gathered)
+  uint32_t* orig = nullptr;                                       // the caller's index of every position (null: sorted)
+  uint8_t* octrl = nullptr;                                       // control-point flags (null: no control points)
+  UsedBlocks used;                                                // of every observation; used.pt: the free points (not constant)
+  std::vector<uint32_t> ptk_start, slot_intr, slot_point;         // (point, intrinsic) slots
+  uint32_t* oslot = nullptr;                                      // [observation]: its slot
+  // pose lists: observations by (pose, intrinsic), the pairs, their chunks; the pose priors by pose
+  uint32_t* pi_obs = nullptr;
+  std::vector<uint32_t> pi_intr, pose_pi_start, pichunk_lo, pichunk_hi, pi_chunk0, pichunk_pose, pichunk_intr, intr_pichunk_start, intr_pichunk;
+  std::vector<uint32_t> prior_pose, pose_prior_start, pose_prior_idx;
+  // point groups (GroupList): [entry] observation / entry word; per supergroup which destination blocks exist; the launch order
+  std::vector<uint8_t> in_group, sg_pp, sg_pi, sg_ii;
+  std::vector<uint32_t> sg_start{0}, g_obs_start{0}, g_pt_start{0}, g_pts, g_pt_estart, g_pt_ksplit, sg_cams, sg_intrs, sg_order;
+  uint32_t *g_eobs = nullptr, *g_eq = nullptr, n_sg_wide = 0;
+  size_t n_gentries = 0;
+  TripExt gext_pp, gext_pi, gext_ii;
+  // product lists of the points outside every group (ungrouped: their observations, ascending)
+  uint32_t* ungrouped = nullptr;
+  size_t n_ungrouped = 0;
+  TripHost hpp, hpi, hii;
+  std::vector<std::pair<uint32_t, uint32_t>> h_blocks;
+  bool diag_blocks_complete = false;
+};
+
+// Observations sorted by point (stable): identity when the caller's list already is (a landmark-by-landmark export of an SfM_Data
+// scene), else one counting sort and a gather of the index lists into page-locked scratch.
+int build_point_order(const mvgx_ba_problem* p, mvgx::HostArena& ha, HostStructure& S) {
+  const uint64_t no = p->n_obs;
+  const size_t n_grains = obs_grains(no);
+  const unsigned T = S.T;
+  int rc;
+  std::vector<uint32_t>& pt_start = S.pt_start;
+  std::atomic<int> unsorted{0};
+  parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
+    bool bad = false;
+    for (uint64_t k = std::max<uint64_t>(1, g * kObsGrain), e = std::min<uint64_t>(no, (g + 1) * kObsGrain); k < e; ++k) bad = bad || p->obs_point[k - 1] > p->obs_point[k];
+    if (bad) unsorted.store(1);
+  });
+  S.sorted = !unsorted.load();
+  S.opose = p->obs_pose; S.ointr = p->obs_intr; S.opt = p->obs_point;
+  if (S.sorted) {
+    pt_start.assign((size_t)p->n_points + 1, 0);
+    // CSR starts from the boundaries of the sorted list: observation k opens the points (obs_point[k - 1], obs_point[k]]
+    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
+      for (uint64_t k = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); k < e; ++k) {
+        const uint32_t cur = p->obs_point[k], prev = k ? p->obs_point[k - 1] : UINT32_MAX;
+        if (k == 0) { for (uint32_t q = 0; q <= cur; ++q) pt_start[q] = 0; }
+        else if (cur != prev) { for (uint32_t q = prev + 1; q <= cur; ++q) pt_start[q] = (uint32_t)k; }
+      }
+    });
+    const uint32_t last = no ? p->obs_point[no - 1] : UINT32_MAX;
+    for (uint32_t q = (no ? last + 1 : 0); q <= p->n_points; ++q) pt_start[q] = (uint32_t)no;
+  } else {
+    uint32_t *g_pose = nullptr, *g_intr = nullptr, *g_pt = nullptr;
+    if ((rc = ha.array(&S.orig, no)) || (rc = ha.array(&g_pose, no)) || (rc = ha.array(&g_intr, no)) || (rc = ha.array(&g_pt, no))) return rc;
+    counting_sort_indices(no, p->n_points, 1, [&](uint64_t k) { return p->obs_point[k]; }, pt_start, S.orig);   // (one thread: the per-thread histograms of 100k points cost more than they save)
+    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
+      for (uint64_t k = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); k < e; ++k) {
+        const uint32_t s_ = S.orig[k];
+        g_pose[k] = p->obs_pose[s_]; g_intr[k] = p->obs_intr[s_]; g_pt[k] = p->obs_point[s_];
+      }
+    });
+    S.opose = g_pose; S.ointr = g_intr; S.opt = g_pt;
+  }
+  if (p->obs_is_control) {
+    if ((rc = ha.array(&S.octrl, std::max<uint64_t>(no, 1)))) return rc;
+    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
+      for (uint64_t k = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); k < e; ++k) S.octrl[k] = p->obs_is_control[S.sorted ? k : S.orig[k]] ? 1 : 0;
+    });
+  }
+  return MVGX_OK;
+}
+
+// The blocks that carry a residual, the RMSE count, the free points (with residuals, not constant). (Over the lists in point order: a
+// shuffled caller's list would scatter the point flags.)
+void build_used_flags(const mvgx_ba_problem* p, HostStructure& S) {
+  mvgx_ba_problem in_point_order = *p;
+  in_point_order.obs_pose = S.opose; in_point_order.obs_intr = S.ointr; in_point_order.obs_point = S.opt; in_point_order.obs_is_control = S.octrl;
+  S.used = used_blocks(&in_point_order, {}, nullptr);
+  for (uint32_t j = 0; j < p->n_points; ++j)
+    if (p->points_constant || (p->point_const_mask && p->point_const_mask[j])) S.used.pt[j] = 0;
+}
+
+// (point, intrinsic) slots: the distinct intrinsics of a point in order of first appearance; counted, then filled
+int build_slots(const mvgx_ba_problem* p, mvgx::HostArena& ha, HostStructure& S) {
+  const uint32_t n_pts = p->n_points, *ointr = S.ointr;
+  const std::vector<uint32_t>& pt_start = S.pt_start;
+  std::vector<uint32_t>& ptk_start = S.ptk_start;
+  if (const int rc = ha.array(&S.oslot, std::max<uint64_t>(p->n_obs, 1))) return rc;
+  ptk_start.assign((size_t)n_pts + 1, 0);
+  const size_t n_pgrains = ((size_t)n_pts + 4095) / 4096;
+  parallel_for_dynamic(n_pgrains, 1, S.T, [&](size_t g, unsigned) {
+    for (uint32_t j = (uint32_t)(g * 4096), e = (uint32_t)std::min<size_t>(n_pts, (g + 1) * 4096); j < e; ++j) {
+      uint32_t n = 0;
+      for (uint32_t o = pt_start[j]; o < pt_start[j + 1]; ++o) {
+        bool seen = false;
+        for (uint32_t q = pt_start[j]; q < o && !seen; ++q) seen = ointr[q] == ointr[o];
+        n += seen ? 0u : 1u;
+      }
+      ptk_start[j + 1] = n;
+    }
+  });
+  for (uint32_t j = 0; j < n_pts; ++j) ptk_start[j + 1] += ptk_start[j];
+  S.slot_intr.resize(ptk_start[n_pts]); S.slot_point.resize(ptk_start[n_pts]);
+  parallel_for_dynamic(n_pgrains, 1, S.T, [&](size_t g, unsigned) {
+    for (uint32_t j = (uint32_t)(g * 4096), e = (uint32_t)std::min<size_t>(n_pts, (g + 1) * 4096); j < e; ++j) {
+      const uint32_t first = ptk_start[j];
+      uint32_t used = first;
+      for (uint32_t o = pt_start[j]; o < pt_start[j + 1]; ++o) {
+        uint32_t s_ = first;
+        while (s_ < used && S.slot_intr[s_] != ointr[o]) ++s_;
+        if (s_ == used) { S.slot_intr[used] = ointr[o]; S.slot_point[used] = j; ++used; }
+        S.oslot[o] = s_;
+      }
+    }
+  });
+  return MVGX_OK;
+}
+
+// Observations by pose (ascending observation index inside a pose): the rows of the product lists; then, inside a pose, stably by
+// intrinsic: the (pose, intrinsic) pairs of the Gram kernels, cut into chunks of kPiChunk observations. The pose-centre priors by pose.
+int build_pose_lists(const mvgx_ba_problem* p, mvgx::HostArena& ha, HostStructure& S, CreateTimer& tick) {
+  const uint64_t no = p->n_obs;
+  const uint32_t n_poses = p->n_poses, n_intr = p->n_intrinsics, n_priors = p->n_pose_priors;
+  const unsigned T = S.T;
+  const uint32_t* ointr = S.ointr;
+  int rc;
+  std::vector<uint32_t> prow_start;
+  uint32_t* pose_obs = nullptr;
+  if ((rc = ha.array(&pose_obs, std::max<uint64_t>(no, 1)))) return rc;
+  counting_sort_indices(no, n_poses, T, [&](uint64_t k) { return S.opose[k]; }, prow_start, pose_obs);
+  tick("  counting sort by pose");
+  // (the usual case - every view has one intrinsic - needs no second list)
+  std::vector<uint8_t> pose_mixed(n_poses, 0);
+  std::atomic<int> any_mixed{0};
+  parallel_for_dynamic(n_poses, 1, T, [&](size_t i, unsigned) {
+    bool one = true;
+    for (uint32_t q = prow_start[i]; q < prow_start[i + 1] && one; ++q) one = ointr[pose_obs[q]] == ointr[pose_obs[prow_start[i]]];
+    if (!one) { pose_mixed[i] = 1; any_mixed.store(1); }
+  });
+  uint32_t* pi_obs = pose_obs;
+  if (any_mixed.load()) {
+    if ((rc = ha.array(&pi_obs, std::max<uint64_t>(no, 1)))) return rc;
+    parallel_for_dynamic(n_poses, 1, T, [&](size_t i, unsigned) {
+      uint32_t* b_ = pi_obs + prow_start[i]; uint32_t* e_ = pi_obs + prow_start[i + 1];
+      std::copy(pose_obs + prow_start[i], pose_obs + prow_start[i + 1], b_);
+      if (pose_mixed[i]) std::stable_sort(b_, e_, [&](uint32_t x, uint32_t y) { return ointr[x] < ointr[y]; });
+    });
+  }
+  S.pi_obs = pi_obs;
+  tick("  pi_obs");
+  std::vector<uint32_t> pi_start;
+  std::vector<uint32_t>& pi_intr = S.pi_intr;
+  S.pose_pi_start.assign((size_t)n_poses + 1, 0);
+  {
+    std::vector<std::vector<uint32_t>> per_pose(n_poses);   // the first list position of every (pose, intrinsic) pair of the pose
+    parallel_for_dynamic(n_poses, 4, T, [&](size_t i, unsigned) {
+      for (uint32_t q = prow_start[i]; q < prow_start[i + 1]; ++q)
+        if (q == prow_start[i] || ointr[pi_obs[q]] != ointr[pi_obs[q - 1]]) per_pose[i].push_back(q);
+    });
+    for (uint32_t i = 0; i < n_poses; ++i) {
+      for (uint32_t q : per_pose[i]) { pi_start.push_back(q); pi_intr.push_back(ointr[pi_obs[q]]); }
+      S.pose_pi_start[i + 1] = (uint32_t)pi_start.size();
+    }
+  }
+  pi_start.push_back((uint32_t)no);
+  for (uint32_t i = 0; i < n_poses; ++i)   // the chunks and the pair of every chunk
+    for (uint32_t q = S.pose_pi_start[i]; q < S.pose_pi_start[i + 1]; ++q) {
+      S.pi_chunk0.push_back((uint32_t)S.pichunk_lo.size());
+      for (uint32_t lo = pi_start[q]; lo < pi_start[q + 1]; lo += kPiChunk) {
+        S.pichunk_lo.push_back(lo); S.pichunk_hi.push_back(std::min<uint32_t>(lo + kPiChunk, pi_start[q + 1]));
+        S.pichunk_pose.push_back(i); S.pichunk_intr.push_back(pi_intr[q]);
+      }
+    }
+  S.pi_chunk0.push_back((uint32_t)S.pichunk_lo.size());
+  // the chunks of every intrinsic (ascending chunk id): its own Gram blocks are summed from them on the matrix-core path
+  counting_sort_indices(S.pichunk_lo.size(), n_intr, 1, [&](uint64_t ch) { return S.pichunk_intr[ch]; }, S.intr_pichunk_start, S.intr_pichunk);
+  tick("  pairs and chunks");
+  S.prior_pose.assign(p->prior_pose, p->prior_pose + n_priors);
+  counting_sort_indices(n_priors, n_poses, 1, [&](uint64_t k) { return S.prior_pose[k]; }, S.pose_prior_start, S.pose_prior_idx);
+  return MVGX_OK;
+}
+
+// The groups of one lowest-pose bucket, as build_point_groups' sweep leaves them
+struct BucketGroups {
+  std::vector<uint32_t> sg_n, obs_n, eobs, eq, pt_n, pts, nk0, cams, intrs, dropped;   // sg_n: groups per supergroup; nk0: per point, its observations with local intrinsic 0; dropped: points of dissolved groups
+  std::vector<uint8_t> pp, pi, ii;
+};
+
+// The greedy sweep over the points of one bucket (in set-key order): add() every point, then finish(). The group under construction
+// (`cur`, its sets `cams` / `intrs`) closes when it is full or a point does not fit; a closed group joins the open supergroup when its
+// sets are the supergroup's (`tail_cams` / `tail_intrs`).
+struct GroupSweep {
+  const HostStructure& S;
+  const int max_sg_groups;
+  BucketGroups& B;
+  void add(uint32_t j) {
+    uint32_t pc[kGroupCams], pk[kGroupCams];
+    int npc = 0, npk = 0;
+    for (uint32_t o = S.pt_start[j]; o < S.pt_start[j + 1]; ++o) pc[npc++] = S.opose[o];
+    for (uint32_t sl = S.ptk_start[j]; sl < S.ptk_start[j + 1]; ++sl) pk[npk++] = S.slot_intr[sl];
+    std::sort(pc, pc + npc); std::sort(pk, pk + npk);
+    // the two forms (see kNarrowCams): a group is wide once it holds a point of more than kNarrowCams poses - then up to kGroupCams
+    // poses and kWidePts points; a group of short tracks never grows wide by union alone (it closes at kNarrowCams as before)
+    const bool cur_wide = cams.size() > (size_t)kNarrowCams;
+    const size_t max_pts = cur_wide ? (size_t)kWidePts : (size_t)kGroupPts;
+    if (cur.size() >= max_pts || cur_obs + (uint32_t)npc > (uint32_t)kGroupThreads) close_group();   // full: the next group starts from the same sets (and may continue the supergroup)
+    // (neighbours in the order mostly bring nothing new: the sets stay as they are - no union, no copies)
+    const bool inside = std::includes(cams.begin(), cams.end(), pc, pc + npc) && std::includes(intrs.begin(), intrs.end(), pk, pk + npk);
+    if (inside && (npc <= kNarrowCams || cur_wide)) { cur.push_back(j); cur_obs += (uint32_t)npc; return; }
+    mc.clear(); mi.clear();
+    std::set_union(cams.begin(), cams.end(), pc, pc + npc, std::back_inserter(mc));
+    std::set_union(intrs.begin(), intrs.end(), pk, pk + npk, std::back_inserter(mi));
+    const bool to_wide = npc > kNarrowCams || cur_wide;
+    const size_t cam_limit = to_wide ? (size_t)kGroupCams : (size_t)kNarrowCams;
+    if (mc.size() > cam_limit || mi.size() > (size_t)kGroupIntr || (to_wide && !cur_wide && cur.size() >= (size_t)kWidePts)) {
+      close_group();
+      sg_open = false;
+      mc.assign(pc, pc + npc); mi.assign(pk, pk + npk);
+    }
+    cams = mc; intrs = mi;
+    cur.push_back(j); cur_obs += (uint32_t)npc;
+  }
+  void finish() { close_group(); flush_flags(); }
+
+  static int local(const std::vector<uint32_t>& v, uint32_t id) { return (int)(std::lower_bound(v.begin(), v.end(), id) - v.begin()); }
+  // which destination blocks the supergroup under construction has: a point with local poses P and local intrinsics K marks every
+  // (x <= y) of P x P, every (x, k) of P x K, every (k <= k') of K x K. Collected as bit rows (a few ORs per point; marking the
+  // flags themselves was |P|^2 stores per point and a third of this phase) and written out when the supergroup is complete.
+  void flush_flags() {
+    if (!acc_open) return;
+    const size_t sgi = B.sg_n.size() - 1;
+    for (int x = 0; x < kGroupCams; ++x) {
+      for (int y = x; y < kGroupCams; ++y) if ((acc_pp[x] >> y) & 1u) B.pp[sgi * kGroupPairsPP + x * kGroupCams - x * (x - 1) / 2 + (y - x)] = 1;
+      for (int k = 0; k < kGroupIntr; ++k) if ((acc_pi[x] >> k) & 1u) B.pi[sgi * kGroupPairsPI + x * kGroupIntr + k] = 1;
+      acc_pp[x] = 0; acc_pi[x] = 0;
+    }
+    for (int k = 0; k < kGroupIntr; ++k) {
+      for (int k2 = k; k2 < kGroupIntr; ++k2) if ((acc_ii[k] >> k2) & 1u) B.ii[sgi * kGroupPairsII + k * kGroupIntr - k * (k - 1) / 2 + (k2 - k)] = 1;
+      acc_ii[k] = 0;
+    }
+    acc_open = false;
+  }
+  // emits `cur` as a group of the open supergroup (same camera / intrinsic sets) or as the first group of a new one
+  void emit_group(bool continues) {
+    if (!continues) {
+      flush_flags();   // (of the supergroup before)
+      B.sg_n.push_back(0);
+      const size_t sgi = B.sg_n.size() - 1;
+      B.cams.resize((sgi + 1) * kGroupCams, 0); B.intrs.resize((sgi + 1) * kGroupIntr, 0);
+      std::copy(cams.begin(), cams.end(), B.cams.begin() + sgi * kGroupCams);
+      std::copy(intrs.begin(), intrs.end(), B.intrs.begin() + sgi * kGroupIntr);
+      B.pp.resize((sgi + 1) * kGroupPairsPP, 0); B.pi.resize((sgi + 1) * kGroupPairsPI, 0); B.ii.resize((sgi + 1) * kGroupPairsII, 0);
+      tail_cams = cams; tail_intrs = intrs;
+    }
+    B.sg_n.back()++;
+    uint32_t n_obs_g = 0;
+    for (size_t q = 0; q < cur.size(); ++q) {
+      const uint32_t j = cur[q];
+      B.pts.push_back(j);
+      uint8_t xs[kGroupCams], ks[kGroupCams];
+      const uint32_t o0 = S.pt_start[j];
+      const int nx = (int)(S.pt_start[j + 1] - o0);
+      uint32_t n_k0 = 0;
+      for (int a = 0; a < nx; ++a) {   // local pose / intrinsic of every observation, once
+        xs[a] = (uint8_t)local(tail_cams, S.opose[o0 + a]); ks[a] = (uint8_t)local(tail_intrs, S.ointr[o0 + a]);
+        n_k0 += ks[a] == 0;
+      }
+      for (int pass = 0; pass < kGroupIntr; ++pass)   // the observations with local intrinsic 0 first, then those with 1
+        for (int a = 0; a < nx; ++a) {
+          if (ks[a] != pass) continue;
+          B.eobs.push_back(o0 + (uint32_t)a);
+          B.eq.push_back((uint32_t)q | ((uint32_t)xs[a] << 8) | ((uint32_t)ks[a] << 12));
+        }
+      n_obs_g += (uint32_t)nx;
+      B.nk0.push_back(n_k0);
+      uint16_t cm = 0, km = 0;
+      for (int a = 0; a < nx; ++a) { cm |= (uint16_t)(1u << xs[a]); km |= (uint16_t)(1u << ks[a]); }
+      for (int a = 0; a < nx; ++a) { acc_pp[xs[a]] |= cm; acc_pi[xs[a]] |= km; acc_ii[ks[a]] |= km; }
+      acc_open = true;
+    }
+    B.obs_n.push_back(n_obs_g);
+    B.pt_n.push_back((uint32_t)cur.size());
+  }
+  void close_group() {
+    if (cams.size() > (size_t)kNarrowCams && !cur.empty()) {
+      // a wide group takes the EXACT union of its points' sets (a group inherits the sets of the one before it - that is what lets
+      // groups of one camera set form a supergroup - but a wide group never continues one, and its columns follow its poses in use)
+      std::vector<uint32_t> ec, ei;
+      for (uint32_t j : cur) {
+        for (uint32_t o = S.pt_start[j]; o < S.pt_start[j + 1]; ++o) { ec.push_back(S.opose[o]); ei.push_back(S.ointr[o]); }
+      }
+      std::sort(ec.begin(), ec.end()); ec.erase(std::unique(ec.begin(), ec.end()), ec.end());
+      std::sort(ei.begin(), ei.end()); ei.erase(std::unique(ei.begin(), ei.end()), ei.end());
+      cams = ec; intrs = ei;
+    }
+    const bool continues = sg_open && cams == tail_cams && intrs == tail_intrs && B.sg_n.back() < (uint32_t)max_sg_groups;
+    // (a wide group stays whatever its size: a handful of points left to the record-based path costs its dozen launches per iteration)
+    if (cur.size() >= (size_t)kGroupMinPts || (continues && !cur.empty()) || (cams.size() > (size_t)kNarrowCams && !cur.empty())) { emit_group(continues); sg_open = true; }
+    else { sg_open = false; B.dropped.insert(B.dropped.end(), cur.begin(), cur.end()); }
+    if (cams.size() > (size_t)kNarrowCams) { cams.clear(); intrs.clear(); }   // (the next group starts from its own points: a wide group's sets are exact, and it continues the supergroup when they come out the same)
+    cur.clear(); cur_obs = 0;
+  }
+
+  std::vector<uint32_t> cams, intrs, mc, mi, cur;
+  std::vector<uint32_t> tail_cams, tail_intrs;   // sets of the supergroup under construction (sorted)
+  bool sg_open = false;
+  uint32_t cur_obs = 0;   // observations of `cur`
+  uint16_t acc_pp[kGroupCams] = {0}, acc_pi[kGroupCams] = {0}, acc_ii[kGroupIntr] = {0};
+  static_assert(kGroupCams <= 16 && kGroupIntr <= 16, "bit rows of the destination-block flags");
+  bool acc_open = false;
+};
+
+// The buckets' groups stitched in bucket order: offsets from a serial prefix over the buckets, copies on host threads
+int stitch_groups(std::vector<BucketGroups>& per_bucket, mvgx::HostArena& ha, HostStructure& S) {
+  const size_t nb = per_bucket.size();
+  std::vector<uint32_t> off_sg(nb + 1, 0), off_g(nb + 1, 0), off_e(nb + 1, 0), off_p(nb + 1, 0);
+  for (size_t b = 0; b < nb; ++b) {
+    const BucketGroups& B = per_bucket[b];
+    off_sg[b + 1] = off_sg[b] + (uint32_t)B.sg_n.size(); off_g[b + 1] = off_g[b] + (uint32_t)B.obs_n.size();
+    off_e[b + 1] = off_e[b] + (uint32_t)B.eobs.size(); off_p[b + 1] = off_p[b] + (uint32_t)B.pts.size();
+  }
+  const size_t tsg = off_sg[nb], tg = off_g[nb], te = off_e[nb], tp = off_p[nb];
+  S.n_gentries = te;
+  S.sg_start.resize(tsg + 1); S.g_obs_start.resize(tg + 1); S.g_pt_start.resize(tg + 1);
+  S.g_pts.resize(tp); S.g_pt_estart.resize(tp + 1); S.g_pt_ksplit.resize(tp);
+  S.sg_cams.resize(tsg * kGroupCams); S.sg_intrs.resize(tsg * kGroupIntr);
+  S.sg_pp.resize(tsg * kGroupPairsPP); S.sg_pi.resize(tsg * kGroupPairsPI); S.sg_ii.resize(tsg * kGroupPairsII);
+  int rc;
+  if ((rc = ha.array(&S.g_eobs, std::max<size_t>(te, 1))) || (rc = ha.array(&S.g_eq, std::max<size_t>(te, 1)))) return rc;
+  parallel_for_dynamic(nb, 1, S.T, [&](size_t b, unsigned) {
+    const BucketGroups& B = per_bucket[b];
+    uint32_t g = off_g[b];
+    for (size_t sgi = 0; sgi < B.sg_n.size(); ++sgi) { g += B.sg_n[sgi]; S.sg_start[off_sg[b] + sgi + 1] = g; }
+    uint32_t e = off_e[b], q = off_p[b];
+    for (size_t k = 0; k < B.obs_n.size(); ++k) {
+      e += B.obs_n[k]; q += B.pt_n[k];
+      S.g_obs_start[off_g[b] + k + 1] = e; S.g_pt_start[off_g[b] + k + 1] = q;
+    }
+    std::copy(B.eobs.begin(), B.eobs.end(), S.g_eobs + off_e[b]);
+    std::copy(B.eq.begin(), B.eq.end(), S.g_eq + off_e[b]);
+    std::copy(B.pts.begin(), B.pts.end(), S.g_pts.begin() + off_p[b]);
+    std::copy(B.cams.begin(), B.cams.end(), S.sg_cams.begin() + (size_t)off_sg[b] * kGroupCams);
+    std::copy(B.intrs.begin(), B.intrs.end(), S.sg_intrs.begin() + (size_t)off_sg[b] * kGroupIntr);
+    std::copy(B.pp.begin(), B.pp.end(), S.sg_pp.begin() + (size_t)off_sg[b] * kGroupPairsPP);
+    std::copy(B.pi.begin(), B.pi.end(), S.sg_pi.begin() + (size_t)off_sg[b] * kGroupPairsPI);
+    std::copy(B.ii.begin(), B.ii.end(), S.sg_ii.begin() + (size_t)off_sg[b] * kGroupPairsII);
+    // first entry of every grouped point (its observations are consecutive entries), and where its local intrinsic 1 starts
+    uint32_t ee = off_e[b];
+    for (size_t k = 0; k < B.pts.size(); ++k) {
+      S.g_pt_estart[off_p[b] + k] = ee; S.g_pt_ksplit[off_p[b] + k] = ee + B.nk0[k];
+      ee += S.pt_start[B.pts[k] + 1] - S.pt_start[B.pts[k]];
+    }
+  });
+  S.g_pt_estart[tp] = (uint32_t)te;
+  return MVGX_OK;
+}
+
+// Point groups (GroupList): free points with at most kGroupCams distinct poses and kGroupIntr distinct intrinsics, ordered by
+// (lowest pose, highest pose, hash of the pose set); consecutive points join a group while the union of their poses stays within
+// kGroupCams, the union of their intrinsics within kGroupIntr and the group within kGroupPts points. A group that closes because
+// it is full hands its camera set to the next one: groups with the same set form a supergroup (one workgroup, one set of partial
+// blocks), up to c->sg_max_groups of them. Groups of fewer than kGroupMinPts points are dissolved unless they continue a supergroup
+// (their points stay on the record-based path, as do long tracks and constant points).
+int build_point_groups(const mvgx_ba_problem* p, const mvgx_ba_ctx* c, mvgx::HostArena& ha, HostStructure& S, CreateTimer& tick) {
+  const uint32_t n_pts = p->n_points, n_poses = p->n_poses;
+  S.in_group.assign(n_pts, 0);
+  if (!c->groups_on || c->model_cost_from_jacobian || !n_poses || !n_pts) return MVGX_OK;
+  const unsigned T = S.T;
+  const std::vector<uint32_t>& pt_start = S.pt_start;
+  std::vector<uint32_t> lo_pose(n_pts, UINT32_MAX), hi_pose(n_pts, 0);
+  std::vector<uint64_t> set_key(n_pts, 0);   // (highest pose, order-independent hash of the pose set): equal sets become neighbours
+  parallel_for_dynamic(((size_t)n_pts + 4095) / 4096, 1, T, [&](size_t g, unsigned) {
+    for (uint32_t j = (uint32_t)(g * 4096), e = (uint32_t)std::min<size_t>(n_pts, (g + 1) * 4096); j < e; ++j) {
+      const uint32_t o0 = pt_start[j], o1 = pt_start[j + 1];
+      bool ok = S.used.pt[j] && o1 > o0 && o1 - o0 <= (uint32_t)kGroupCams && S.ptk_start[j + 1] - S.ptk_start[j] <= (uint32_t)kGroupIntr;
+      for (uint32_t o = o0; o < o1 && ok; ++o) {
+        for (uint32_t o2 = o0; o2 < o; ++o2) ok = ok && S.opose[o2] != S.opose[o];   // a pose seen twice (shared by two views): record path
+        lo_pose[j] = std::min(lo_pose[j], S.opose[o]); hi_pose[j] = std::max(hi_pose[j], S.opose[o]);
+        uint64_t h = (uint64_t)S.opose[o] * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+        set_key[j] += h * 0xBF58476D1CE4E5B9ull;   // commutative combination
+      }
+      set_key[j] = ((uint64_t)hi_pose[j] << 32) | (uint32_t)(set_key[j] >> 32);
+      if (!ok) lo_pose[j] = UINT32_MAX;
+      S.in_group[j] = ok ? 1 : 0;   // (a thread's own range of the array; the few points of dissolved groups are taken out after the sweep:
+                                    // marking points from the bucket sweep - every thread storing all over the array - was a third of that phase)
+    }
+  });
+  tick("  point keys");
+  std::vector<uint32_t> lo_start, order;   // eligible points by lowest pose (bucket n_poses: not eligible)
+  counting_sort_indices(n_pts, n_poses + 1, T, [&](uint64_t j) { return lo_pose[j] == UINT32_MAX ? n_poses : lo_pose[j]; }, lo_start, order);
+  parallel_for_dynamic(n_poses, 1, T, [&](size_t i, unsigned) {
+    std::stable_sort(order.begin() + lo_start[i], order.begin() + lo_start[i + 1], [&](uint32_t x, uint32_t y) { return set_key[x] < set_key[y]; });
+  });
+  tick("  points by lowest pose, set key");
+  // groups never span two lowest-pose buckets, so the buckets are swept independently (host threads) and their groups
+  // stitched in bucket order: the result does not depend on the thread count
+  std::vector<BucketGroups> per_bucket(n_poses);
+  parallel_for_dynamic(n_poses, 1, T, [&](size_t bucket, unsigned) {
+    BucketGroups& B = per_bucket[bucket];
+    const uint32_t q0 = lo_start[bucket], q1 = lo_start[bucket + 1];
+    {   // (one allocation per list instead of a doubling series)
+      size_t n_e = 0;
+      for (uint32_t q = q0; q < q1; ++q) n_e += pt_start[order[q] + 1] - pt_start[order[q]];
+      B.eobs.reserve(n_e); B.eq.reserve(n_e); B.pts.reserve(q1 - q0); B.nk0.reserve(q1 - q0);
+    }
+    GroupSweep sweep{S, c->sg_max_groups, B};
+    for (uint32_t q = q0; q < q1; ++q) {
+      // (the points of a bucket lie anywhere in the caller's order - a scene flattened from a hash map: their rows are fetched ahead,
+      // the CSR entry sixteen points ahead, the rows it names eight points ahead; 1.7 -> ms of this phase at 1 M observations were misses)
+      if (q + 16 < q1) { __builtin_prefetch(&pt_start[order[q + 16]]); __builtin_prefetch(&S.ptk_start[order[q + 16]]); }
+      if (q + 8 < q1) {
+        const uint32_t jn = order[q + 8], on = pt_start[jn];
+        __builtin_prefetch(&S.opose[on]); __builtin_prefetch(&S.ointr[on]); __builtin_prefetch(&S.slot_intr[S.ptk_start[jn]]);
+      }
+      sweep.add(order[q]);
+    }
+    sweep.finish();
+  });
+  for (const BucketGroups& B : per_bucket) for (uint32_t j : B.dropped) S.in_group[j] = 0;
+  tick("  greedy groups per bucket");
+  if (const int rc = stitch_groups(per_bucket, ha, S)) return rc;
+  tick("  stitch");
+  // (the buckets' lists go back to the allocator on the host threads: released one after the other at the end of this function they were 0.5 / 1.9 ms)
+  parallel_for_dynamic(per_bucket.size(), 4, T, [&](size_t b, unsigned) { per_bucket[b] = BucketGroups(); });
+  return MVGX_OK;
+}
+
+// Destination blocks of the supergroups, per product family: (row block, column block) -> partial-block id; and the launch order of
+// the supergroups: largest first (MVGX_BA_SG_INDEX_ORDER: the order of construction), the ones of the usual form before the wide ones
+// (a local pose beyond kNarrowCams in use) - two launches.
+void build_group_destinations(const mvgx_ba_problem* p, bool sg_index_order, HostStructure& S, CreateTimer& tick) {
+  const uint32_t n_sg = (uint32_t)S.sg_start.size() - 1, np_ = p->n_poses;
+  const size_t n_cb = (size_t)p->n_poses + p->n_intrinsics;
+  S.gext_pp.rows.resize(n_cb); S.gext_pi.rows.resize(n_cb); S.gext_ii.rows.resize(n_cb);
+  S.gext_pp.ext_row.assign((size_t)n_sg * kGroupPairsPP, kNoChunk);
+  S.gext_pi.ext_row.assign((size_t)n_sg * kGroupPairsPI, kNoChunk);
+  S.gext_ii.ext_row.assign((size_t)n_sg * kGroupPairsII, kNoChunk);
+  for (uint32_t sgi = 0; sgi < n_sg; ++sgi) {
+    const uint32_t* cm = S.sg_cams.data() + (size_t)sgi * kGroupCams;
+    const uint32_t* im = S.sg_intrs.data() + (size_t)sgi * kGroupIntr;
+    for (int x = 0, t = 0; x < kGroupCams; ++x)
+      for (int y = x; y < kGroupCams; ++y, ++t)
+        if (S.sg_pp[(size_t)sgi * kGroupPairsPP + t]) S.gext_pp.rows[cm[x]].emplace_back(cm[y], sgi * kGroupPairsPP + t);
+    for (int x = 0; x < kGroupCams; ++x)
+      for (int k = 0; k < kGroupIntr; ++k)
+        if (S.sg_pi[(size_t)sgi * kGroupPairsPI + x * kGroupIntr + k]) S.gext_pi.rows[cm[x]].emplace_back(np_ + im[k], sgi * kGroupPairsPI + x * kGroupIntr + k);
+    for (int k = 0, t = 0; k < kGroupIntr; ++k)
+      for (int l = k; l < kGroupIntr; ++l, ++t)
+        if (S.sg_ii[(size_t)sgi * kGroupPairsII + t]) S.gext_ii.rows[np_ + im[k]].emplace_back(np_ + im[l], sgi * kGroupPairsII + t);
+  }
+  tick("  destination rows");
+  for (TripExt* e : {&S.gext_pp, &S.gext_pi, &S.gext_ii})
+    parallel_for_dynamic(n_cb, 16, S.T, [&](size_t r, unsigned) { std::sort(e->rows[r].begin(), e->rows[r].end()); });
+  S.sg_order.resize(n_sg);
+  std::iota(S.sg_order.begin(), S.sg_order.end(), 0u);
+  const std::vector<uint32_t> &sg_start = S.sg_start, &g_obs_start = S.g_obs_start;
+  if (!sg_index_order)
+    std::stable_sort(S.sg_order.begin(), S.sg_order.end(), [&](uint32_t a, uint32_t b) {
+      return g_obs_start[sg_start[a + 1]] - g_obs_start[sg_start[a]] > g_obs_start[sg_start[b + 1]] - g_obs_start[sg_start[b]];
+    });
+  auto sg_is_wide = [&](uint32_t sgi) {
+    for (int x = kNarrowCams; x < kGroupCams; ++x)
+      if (S.sg_pp[(size_t)sgi * kGroupPairsPP + x * kGroupCams - x * (x - 1) / 2]) return true;
+    return false;
+  };
+  std::stable_partition(S.sg_order.begin(), S.sg_order.end(), [&](uint32_t sgi) { return !sg_is_wide(sgi); });
+  S.n_sg_wide = (uint32_t)std::count_if(S.sg_order.begin(), S.sg_order.end(), sg_is_wide);
+}
+
+// The observations of the points outside every group, ascending (counted per grain, then filled): the record-based path works on
+// these alone. By pose (ascending observation inside a pose) they are the rows of the product lists; their (point, intrinsic) slots
+// by intrinsic the rows of the intrinsic-intrinsic products. Schur products by destination block, generated row by row on host
+// threads. Constant / unused points have Z = 0: only their (a, a) products are listed, so that every diagonal block exists (it
+// carries the Gram block and the rhs).
+int build_product_lists(const mvgx_ba_problem* p, mvgx::HostArena& ha, HostStructure& S, CreateTimer& tick) {
+  const uint64_t no = p->n_obs;
+  const size_t n_grains = obs_grains(no);
+  const unsigned T = S.T;
+  const uint32_t np = p->n_poses;
+  const size_t n_cb = (size_t)p->n_poses + p->n_intrinsics;
+  const std::vector<uint32_t> &pt_start = S.pt_start, &ptk_start = S.ptk_start, &slot_intr = S.slot_intr;
+  const std::vector<uint8_t> &pt_free = S.used.pt, &in_group = S.in_group;
+  const uint32_t *opose = S.opose, *opt = S.opt;
+  int rc;
+  {
+    std::vector<uint32_t> cnt(n_grains + 1, 0);
+    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
+      uint32_t n = 0;
+      for (uint64_t o = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); o < e; ++o) n += !in_group[opt[o]];
+      cnt[g + 1] = n;
+    });
+    for (size_t g = 0; g < n_grains; ++g) cnt[g + 1] += cnt[g];
+    S.n_ungrouped = cnt[n_grains];
+    if ((rc = ha.array(&S.ungrouped, std::max<size_t>(S.n_ungrouped, 1)))) return rc;
+    if (S.n_ungrouped)
+      parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
+        uint32_t at = cnt[g];
+        if (at == cnt[g + 1]) return;
+        for (uint64_t o = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); o < e; ++o) if (!in_group[opt[o]]) S.ungrouped[at++] = (uint32_t)o;
+      });
+  }
+  const uint32_t* ungrouped = S.ungrouped;
+  std::vector<uint32_t> urow_start, urow;   // [pose] -> positions in `ungrouped`
+  counting_sort_indices(S.n_ungrouped, np, T, [&](uint64_t i) { return opose[ungrouped[i]]; }, urow_start, urow);
+  std::vector<uint32_t> uslots, islot_start, islot;   // slots of the points outside every group, by intrinsic (ascending slot)
+  for (uint32_t q = 0; q < (uint32_t)slot_intr.size(); ++q) if (!in_group[S.slot_point[q]]) uslots.push_back(q);
+  counting_sort_indices(uslots.size(), p->n_intrinsics, T, [&](uint64_t i) { return slot_intr[uslots[i]]; }, islot_start, islot);
+  tick("lists of the ungrouped points");
+  if ((rc = build_trip_list(n_cb, [&](uint32_t r, auto emit) {   // pose-pose: Z_a^T Z_b, pose(a) <= pose(b), same point
+        if (r >= np) return;
+        for (uint32_t q = urow_start[r]; q < urow_start[r + 1]; ++q) {   // (all products of a grouped point are formed by its group)
+          const uint32_t a = ungrouped[urow[q]], j = opt[a];
+          for (uint32_t b = pt_start[j]; b < pt_start[j + 1]; ++b)
+            if (r <= opose[b] && (pt_free[j] || a == b)) emit(opose[b], a, b);
+        }
+      }, S.hpp, T, &S.gext_pp))) return rc;
+  tick("pose-pose products");
+  if ((rc = build_trip_list(n_cb, [&](uint32_t r, auto emit) {   // pose-intrinsic: Z_a^T Zint_slot
+        if (r >= np) return;
+        for (uint32_t q = urow_start[r]; q < urow_start[r + 1]; ++q) {
+          const uint32_t a = ungrouped[urow[q]], j = opt[a];
+          for (uint32_t sl = ptk_start[j]; sl < ptk_start[j + 1]; ++sl)
+            if (pt_free[j] || sl == S.oslot[a]) emit(np + slot_intr[sl], a, sl);
+        }
+      }, S.hpi, T, &S.gext_pi))) return rc;
+  for (size_t b = 0; b < S.hpi.block_row.size(); ++b) {   // the (pose, intrinsic) pair whose Fc^T Fi belongs to the block
+    const uint32_t i = S.hpi.block_row[b], k = S.hpi.block_col[b] - np;
+    for (uint32_t q = S.pose_pi_start[i]; q < S.pose_pi_start[i + 1]; ++q)
+      if (S.pi_intr[q] == k) S.hpi.block_own[b] = (int32_t)q;
+  }
+  if ((rc = build_trip_list(n_cb, [&](uint32_t r, auto emit) {   // intrinsic-intrinsic
+        if (r < np) return;
+        const uint32_t k = r - np;
+        for (uint32_t q = islot_start[k]; q < islot_start[k + 1]; ++q) {
+          const uint32_t sa = uslots[islot[q]], j = S.slot_point[sa];
+          for (uint32_t sb = ptk_start[j]; sb < ptk_start[j + 1]; ++sb)
+            if (k <= slot_intr[sb] && (pt_free[j] || sa == sb)) emit(np + slot_intr[sb], sa, sb);
+        }
+      }, S.hii, T, &S.gext_ii))) return rc;
+  for (const TripHost* h : {&S.hpp, &S.hpi, &S.hii})
+    for (size_t b = 0; b < h->block_row.size(); ++b) S.h_blocks.emplace_back(h->block_row[b], h->block_col[b]);
+  // does every camera block have a diagonal destination in the assemble lists? (then the LM diagonal can be applied there)
+  size_t n_diag = 0;
+  for (const TripHost* h : {&S.hpp, &S.hii})
+    for (size_t b = 0; b < h->block_row.size(); ++b) n_diag += h->block_row[b] == h->block_col[b];
+  S.diag_blocks_complete = n_diag == n_cb;
+  return MVGX_OK;
+}
+
+// Copies n elements of a caller's array to the device: below 1 MB directly; above through page-locked scratch (mvgx::HostArena)
+// that the host threads fill - from pageable memory hipMemcpyAsync blocks the caller and moved 8 GB/s (18 ms for the observation
+// list of the 5M-observation scene); from page-locked memory it is an asynchronous DMA at 50 GB/s that overlaps the host work after it.
+template <class E>
+int staged_copy(mvgx_ba_ctx* c, mvgx::HostArena& ha, E* dev, const E* src, size_t n) {
+  if (!n) return MVGX_OK;
+  if (n * sizeof(E) < (1u << 20)) { MVGX_HIP(hipMemcpyAsync(dev, src, n * sizeof(E), hipMemcpyHostToDevice, c->stream)); return MVGX_OK; }
+  E* st = nullptr;
+  if (const int rc = ha.array(&st, n)) return rc;
+  const size_t per = (1u << 20) / sizeof(E), n_chunks = (n + per - 1) / per;
+  parallel_for_dynamic(n_chunks, 1, host_threads(c->d.n_obs), [&](size_t ch, unsigned) { memcpy(st + ch * per, src + ch * per, std::min(per, n - ch * per) * sizeof(E)); });
+  MVGX_HIP(hipMemcpyAsync(dev, st, n * sizeof(E), hipMemcpyHostToDevice, c->stream));
+  return MVGX_OK;
+}
+
+// The VALUES of a problem on the device (mvgx_ba_create, mvgx_ba_update): the parameters, the prior targets, and the image points and
+// weights in point order - through the permutation c->h_perm when the caller's list is not in it.
+int upload_values(mvgx_ba_ctx* c, const mvgx_ba_problem* p, mvgx::HostArena& ha) {
+  Dev& d = c->d;
+  const uint64_t no = d.n_obs;
+  int rc;
+  if ((rc = staged_copy(c, ha, d.poses, p->poses, (size_t)d.n_poses * 6)) || (rc = staged_copy(c, ha, d.intr, p->intrinsics, (size_t)d.n_intr * 8)) ||
+      (rc = staged_copy(c, ha, d.pts, p->points, (size_t)d.n_pts * 3)) ||
+      (rc = staged_copy(c, ha, d.prior_center, p->prior_center, (size_t)d.n_priors * 3)) ||
+      (rc = staged_copy(c, ha, d.prior_weight, p->prior_weight, (size_t)d.n_priors * 3)))
+    return rc;
+  if (c->h_perm.empty()) {
+    if ((rc = staged_copy(c, ha, d.oxy, p->obs_xy, (size_t)(2 * no)))) return rc;
+    if (p->obs_weight && (rc = staged_copy(c, ha, d.oweight, p->obs_weight, (size_t)no))) return rc;
+    return MVGX_OK;
+  }
+  double* g_xy = nullptr; double* g_w = nullptr;
+  if ((rc = ha.array(&g_xy, (size_t)(2 * no))) || (p->obs_weight && (rc = ha.array(&g_w, (size_t)no)))) return rc;
+  parallel_for_dynamic(obs_grains(no), 1, host_threads(no), [&](size_t g, unsigned) {
+    for (uint64_t k = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); k < e; ++k) {
+      const uint64_t s_ = c->h_perm[k];
+      g_xy[2 * k] = p->obs_xy[2 * s_]; g_xy[2 * k + 1] = p->obs_xy[2 * s_ + 1];
+      if (g_w) g_w[k] = p->obs_weight[s_];
+    }
+  });
+  if (no) MVGX_HIP(hipMemcpyAsync(d.oxy, g_xy, (size_t)(2 * no) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (g_w && no) MVGX_HIP(hipMemcpyAsync(d.oweight, g_w, (size_t)no * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return MVGX_OK;
+}
+
+// The observation lists of the structure in point order and in (pose, intrinsic) order, enqueued as soon as they exist: the DMA
+// overlaps the rest of the structure build.
+int upload_observation_lists(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const HostStructure& S, mvgx::HostArena& ha) {
+  Dev& d = c->d;
+  const uint64_t no = d.n_obs;
+  int rc;
+  if ((rc = dev_alloc(c->pool, &d.model, d.n_intr)) || (rc = staged_copy(c, ha, d.model, p->intr_model, d.n_intr))) return rc;
+  for (auto [dev, src] : {std::make_pair(&d.opose, S.opose), std::make_pair(&d.ointr, S.ointr), std::make_pair(&d.opt, S.opt)}) {
+    if (!S.sorted) rc = dev_upload_n(c->pool, dev, src, no, c->stream);   // (gathered into page-locked scratch already)
+    else if (!(rc = dev_alloc(c->pool, dev, no))) rc = staged_copy(c, ha, *dev, src, no);
+    if (rc) return rc;
+  }
+  if (!S.sorted && (rc = dev_upload_n(c->pool, &d.oorig, S.orig, no, c->stream))) return rc;
+  if (S.octrl && (rc = dev_upload_n(c->pool, &d.octrl, S.octrl, no, c->stream))) return rc;
+  return dev_upload_n(c->pool, &d.pi_obs, S.pi_obs, no, c->stream);
+}
+
+// The rest of the structure on the device (lists, product lists, point groups) and every scratch array of the iterations; what the
+// context keeps of the host structure (mvgx_ba_update, the plan of the reduced solve).
+int upload_structure(mvgx_ba_ctx* c, HostStructure& S, CreateTimer& tick) {
+  Dev& d = c->d;
+  const uint64_t no = d.n_obs;
+  int rc;
+#define UP(field, vec) if ((rc = dev_upload(c->pool, &d.field, vec, c->stream))) return rc
+#define UPN(field, ptr, n) if ((rc = dev_upload_n(c->pool, &d.field, ptr, (size_t)(n), c->stream))) return rc
+#define AL(field, n) if ((rc = dev_alloc(c->pool, &d.field, (size_t)(n)))) return rc
+  d.n_islots = (int)S.slot_intr.size(); d.n_pi = (int)S.pi_intr.size(); d.n_pichunks = (int)S.pichunk_lo.size();
+  c->h_pose_used = S.used.pose; c->h_intr_used = S.used.intr; c->h_pt_free = S.used.pt;
+  c->n_obs_rmse_all = S.used.n_rmse;
+  c->h_blocks = std::move(S.h_blocks);
+  c->diag_blocks_complete = S.diag_blocks_complete;
+  UP(pt_start, S.pt_start); UP(ptk_start, S.ptk_start); UP(slot_intr, S.slot_intr); UP(slot_point, S.slot_point);
+  AL(cam_active, d.N); AL(cam_counts, d.N); AL(pt_free, d.n_pts);
+  UP(pichunk_lo, S.pichunk_lo); UP(pichunk_hi, S.pichunk_hi); UP(pi_chunk0, S.pi_chunk0); UP(pose_pi_start, S.pose_pi_start);
+  UP(pichunk_pose, S.pichunk_pose); UP(pichunk_intr, S.pichunk_intr);
+  UP(intr_pichunk_start, S.intr_pichunk_start); UP(intr_pichunk, S.intr_pichunk);
+  UP(prior_pose, S.prior_pose); UP(pose_prior_start, S.pose_prior_start); UP(pose_prior_idx, S.pose_prior_idx);
+  AL(Jprior, (size_t)d.n_priors * kPriorJ);
+  tick("small allocations + uploads");
+  // Jacobian records and stored Z blocks: only when some point is on the record-based path (they are indexed by observation:
+  // with point groups only the entries of the other points are ever touched)
+  const bool record_path = S.n_ungrouped != 0;
+  const uint64_t nrec = record_path ? no : 0;
+  AL(cposes, d.n_poses * 6); AL(cintr, d.n_intr * 8); AL(cpts, (size_t)d.n_pts * 3);
+  AL(pi_pt, no); AL(pi_xy, no);
+  AL(JA, (size_t)kJA * nrec); AL(JB, (size_t)kJB * nrec); AL(JC, (size_t)kJC * nrec);
+  AL(cn_cam, d.N); AL(g_cam, d.N); AL(scale_cam, d.N); AL(diag_cam, d.N);
+  AL(cn_pt, (size_t)d.n_pts * 3); AL(g_pt, (size_t)d.n_pts * 3); AL(scale_pt, (size_t)d.n_pts * 3); AL(diag_pt, (size_t)d.n_pts * 3);
+  AL(pichunk_part, (size_t)d.n_pichunks * kPiGram); AL(pi_gram, (size_t)d.n_pi * kPiGram); AL(pose_gram, (size_t)d.n_poses * kPoseGram);
+  AL(igram, (size_t)d.n_intr * kIntrGram);
+  AL(pichunk_ipart, (size_t)d.n_pichunks * kIntrGram);
+  AL(intr_slice_part, (size_t)d.n_intr * kIntrSlices * kIntrGram); AL(intr_arrivals, d.n_intr);
+  MVGX_HIP(hipMemsetAsync(d.intr_arrivals, 0, (size_t)std::max<uint32_t>(d.n_intr, 1) * sizeof(unsigned), c->stream));
+  AL(Linv3, (size_t)d.n_pts * 6); AL(hp, (size_t)d.n_pts * 3);
+  AL(Zpose, (size_t)nrec * 18); AL(Zint, (size_t)(record_path ? d.n_islots : 0) * 24);
+  AL(zsol, d.N); AL(step_cam, d.N); AL(step_pt, (size_t)d.n_pts * 3);
+  tick("large scratch allocations");
+  struct { TripHost* h; TripList* l; int nv; } lists[3] = {{&S.hpp, &d.tpp, 6 * 6 + 6}, {&S.hpi, &d.tpi, 6 * 8 + 6}, {&S.hii, &d.tii, 8 * 8 + 8}};
+  for (auto& e : lists) {
+    TripHost& h = *e.h; TripList& l = *e.l;
+    l.n_trips = (uint32_t)h.trips.size(); l.n_chunks = (uint32_t)h.chunk_lo.size(); l.n_blocks = (uint32_t)h.block_row.size();
+    l.n_ext = h.n_ext;
+    if ((rc = dev_upload(c->pool, &l.trips, h.trips, c->stream)) || (rc = dev_upload(c->pool, &l.chunk_lo, h.chunk_lo, c->stream)) ||
+        (rc = dev_upload(c->pool, &l.chunk_hi, h.chunk_hi, c->stream)) || (rc = dev_upload(c->pool, &l.chunk_diag, h.chunk_diag, c->stream)) ||
+        (rc = dev_upload(c->pool, &l.block_row, h.block_row, c->stream)) || (rc = dev_upload(c->pool, &l.block_col, h.block_col, c->stream)) ||
+        (rc = dev_upload(c->pool, &l.block_chunk0, h.block_chunk0, c->stream)) || (rc = dev_upload(c->pool, &l.block_own, h.block_own, c->stream)) ||
+        (h.n_ext && (rc = dev_upload(c->pool, &l.block_ext0, h.block_ext0, c->stream))) ||
+        (rc = dev_alloc(c->pool, &l.part, ((size_t)l.n_chunks + l.n_ext) * e.nv)))
+      return rc;
+  }
+  tick("  trip lists");
+  const uint32_t n_groups = (uint32_t)S.g_pt_start.size() - 1, n_sg = (uint32_t)S.sg_start.size() - 1;
+  d.grp.n_groups = n_groups; d.grp.n_sg = n_sg;
+  c->n_grouped_points = (uint32_t)S.g_pts.size();
+  c->all_points_grouped = d.n_pts != 0 && S.g_pts.size() == (size_t)d.n_pts;
+  if (n_sg) {
+    d.grp.n_ungrouped = (uint32_t)S.n_ungrouped;
+    c->h_sg_order = std::move(S.sg_order);
+    c->n_sg_wide = S.n_sg_wide;
+    c->n_gentries = S.n_gentries;
+    UP(grp.sg_start, S.sg_start); UP(grp.sg_order, c->h_sg_order); UP(grp.obs_start, S.g_obs_start); UP(grp.pt_start, S.g_pt_start);
+    UP(grp.pts, S.g_pts); UP(grp.pt_estart, S.g_pt_estart); UP(grp.pt_ksplit, S.g_pt_ksplit);
+    UPN(grp.eq, S.g_eq, S.n_gentries); UPN(grp.eobs, S.g_eobs, S.n_gentries);
+    AL(grp.exy, S.n_gentries);   // (the image points of the entries: gathered on the device, bind_values)
+    UP(grp.cams, S.sg_cams); UP(grp.intrs, S.sg_intrs);
+    UP(grp.chunk_pp, S.gext_pp.ext_row); UP(grp.chunk_pi, S.gext_pi.ext_row); UP(grp.chunk_ii, S.gext_ii.ext_row);
+    UPN(grp.ungrouped, S.ungrouped, S.n_ungrouped);
+    UP(pt_grouped, S.in_group);
+    AL(grp.gmax_part, n_sg);
+    tick("  group uploads");
+  }
+  c->grid_obs = (int)std::max<uint64_t>(1, (no + 255) / 256);
+  c->grid_vec = (int)std::max<size_t>(1, (std::max<size_t>((size_t)d.N, (size_t)d.n_pts * 3) + 255) / 256);
+  AL(part, (size_t)6 * std::max(c->grid_obs, c->grid_vec) + 16);   // up to six partial sums per workgroup (ba_step_scalars_kernel)
+  AL(grp_part, (size_t)5 * d.grp.n_sg + 8);
+  AL(scalars, kSCount + 1);   // the fail word lives in the slot after the scalars: one D2H copy fetches both
+  if ((rc = dev_alloc(c->pool, &c->d_accept, (size_t)2))) return rc;
+  d.fail = reinterpret_cast<int*>(d.scalars + kSCount);
+#undef UP
+#undef UPN
+#undef AL
+  return MVGX_OK;
+}
+
+// Dynamic LDS of the kernels that use more than the default; which branches of the camera models the point-group kernels carry
+int set_kernel_attributes(mvgx_ba_ctx* c, const mvgx_ba_problem* p) {
+#define MVGX_GROUP_ATTR(mode, fam, wide_) MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_point_group_kernel<mode, fam, wide_>), hipFuncAttributeMaxDynamicSharedMemorySize, kGroupLds))
+  MVGX_GROUP_ATTR(kGroupNorms, false, false); MVGX_GROUP_ATTR(kGroupForward, false, false); MVGX_GROUP_ATTR(kGroupBacksub, false, false);
+  MVGX_GROUP_ATTR(kGroupNorms, true, false); MVGX_GROUP_ATTR(kGroupForward, true, false); MVGX_GROUP_ATTR(kGroupBacksub, true, false);
+  MVGX_GROUP_ATTR(kGroupNorms, false, true); MVGX_GROUP_ATTR(kGroupForward, false, true); MVGX_GROUP_ATTR(kGroupBacksub, false, true);
+  MVGX_GROUP_ATTR(kGroupNorms, true, true); MVGX_GROUP_ATTR(kGroupForward, true, true); MVGX_GROUP_ATTR(kGroupBacksub, true, true);
+#undef MVGX_GROUP_ATTR
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_diag_inv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sp_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sp_level_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_panel_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds));
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_update128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kUpd128Lds));
+  c->pinhole_family = !c->generic_models;
+  for (uint32_t k = 0; k < p->n_intrinsics; ++k) {
+    const int m = p->intr_model[k];
+    c->pinhole_family = c->pinhole_family && (m == mvgx_ba::kCamPinhole || m == mvgx_ba::kCamRadial1 || m == mvgx_ba::kCamRadial3 || m == mvgx_ba::kCamBrown);
+  }
+  return MVGX_OK;
+}
+
+// Binds the context to the values just uploaded (mvgx_ba_create, mvgx_ba_update{,_subset}): which blocks carry a residual - the
+// structure's, or with a subset those of the observations that are on -, the free points, the RMSE count, the camera component
+// flags, the loss scales, the two re-ordered copies of the image points ((pose, intrinsic) order for the camera Gram kernel, entry
+// order for the point groups); clears the scalars, the fail word and the reduced solution. Drains the stream.
+int bind_values(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_t* obs_enabled) {
+  Dev& d = c->d;
+  const uint64_t no = d.n_obs;
+  int rc;
+  UsedBlocks sub;   // with a subset: the blocks of the observations that are on
+  if (obs_enabled) {
+    sub = used_blocks(p, c->h_perm, obs_enabled);
+    for (uint32_t j = 0; j < d.n_pts; ++j) sub.pt[j] = c->h_pt_free[j] && sub.pt[j];
+  }
+  const std::vector<uint8_t>& pose_used = obs_enabled ? sub.pose : c->h_pose_used;
+  const std::vector<uint8_t>& intr_used = obs_enabled ? sub.intr : c->h_intr_used;
+  const std::vector<uint8_t>& pt_free = obs_enabled ? sub.pt : c->h_pt_free;
+  const double n_rmse = obs_enabled ? sub.n_rmse : c->n_obs_rmse_all;
+  if (sub.any_off) {
+    if (!c->odisabled_buf && (rc = dev_alloc(c->pool, &c->odisabled_buf, (size_t)no))) return rc;
+    MVGX_HIP(hipMemcpyAsync(c->odisabled_buf, sub.off.data(), (size_t)no, hipMemcpyHostToDevice, c->stream));
+    d.odisabled = c->odisabled_buf;
+  } else {
+    d.odisabled = nullptr;
+  }
+  c->n_obs_rmse_local = n_rmse;
+  c->n_obs_global = 0;   // (counted again by the next start() / mvgx_ba_evaluate: ADVICE r4 - evaluate() after an update divided by the old count)
+  if (d.n_pts) MVGX_HIP(hipMemcpyAsync(d.pt_free, pt_free.data(), (size_t)d.n_pts, hipMemcpyHostToDevice, c->stream));
+  std::vector<uint8_t> cam_active, cam_counts;
+  camera_component_flags(p, pose_used, intr_used, cam_active, cam_counts);
+  if (d.N) {
+    MVGX_HIP(hipMemcpyAsync(d.cam_active, cam_active.data(), cam_active.size(), hipMemcpyHostToDevice, c->stream));
+    MVGX_HIP(hipMemcpyAsync(d.cam_counts, cam_counts.data(), cam_counts.size(), hipMemcpyHostToDevice, c->stream));
+  }
+  d.huber_a = p->huber_a;
+  d.prior_huber_a = p->prior_huber_a;
+  if (no) hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, c->stream, d.pi_obs, (uint32_t)no, d.opt, d.oxy, d.pi_pt, d.pi_xy);
+  if (c->n_gentries)
+    hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((c->n_gentries + 255) / 256)), dim3(256), 0, c->stream, d.grp.eobs, (uint32_t)c->n_gentries,
+                       d.opt, d.oxy, static_cast<uint32_t*>(nullptr), d.grp.exy);
+  BA_LAUNCH_CHECK();
+  MVGX_HIP(hipMemsetAsync(d.scalars, 0, (kSCount + 1) * sizeof(double), c->stream));
+  MVGX_HIP(hipMemsetAsync(d.zsol, 0, (size_t)std::max(d.N, 1) * sizeof(double), c->stream));
+  MVGX_HIP(hipStreamSynchronize(c->stream));
+  return MVGX_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -4524,7 +5389,7 @@ int mvgx_ba_create_multi(const int* devices, int n_devices, const mvgx_ba_proble
 
 int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
   MVGX_REQUIRE(p && out, MVGX_ERR_ARG, "mvgx_ba_create: NULL argument");
-  const auto t_enter = std::chrono::steady_clock::now();
+  CreateTimer tick;
   { const int vrc = mvgx::ba_validate_problem(p); if (vrc) return vrc; }   // before any dispatch to the multi-device path
   if (device == -1) {   // "no preference": MVGX_DEVICES may name the device(s); small problems stay on one device
     std::vector<int> devs;
@@ -4539,15 +5404,6 @@ int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
   MVGX_REQUIRE(p->n_obs < (1ull << 31), MVGX_ERR_ARG, "mvgx_ba_create: too many observations for one device shard");
   int rc = mvgx::select_device(device);
   if (rc) return rc;
-  // MVGX_BA_CREATE_TIMING=1: phase times of this function on stderr (host structure vs allocation vs upload)
-  const bool timing = getenv("MVGX_BA_CREATE_TIMING") != nullptr;
-  auto t_prev = t_enter;
-  auto tick = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[mvgx_ba_create] %-36s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-    t_prev = now;
-  };
   mvgx::HostArena ha;   // the large lists of the structure build and the sources of the uploads (declared before the guard: the
                         // guard's destroy drains the stream before the slabs go back to the cache)
   auto* c = new mvgx_ba_ctx();
@@ -4565,725 +5421,49 @@ int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
   tick("events");
   MVGX_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_scalars), (kSCount + 3) * sizeof(double), hipHostMallocDefault));
   memset(c->h_scalars, 0, (kSCount + 3) * sizeof(double));
-  if (const char* env = getenv("MVGX_BA_SPECULATE")) c->speculate = atoi(env) != 0;
   if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_scalars_dev), c->h_scalars, 0) != hipSuccess) { (void)hipGetLastError(); c->poll_scalars = false; }
-  if (const char* env = getenv("MVGX_BA_POLL_SCALARS")) c->poll_scalars = c->poll_scalars && atoi(env) != 0;
-  if (const char* env = getenv("MVGX_BA_SEPARATE_COST")) c->fold_candidate = atoi(env) == 0;
-  if (const char* env = getenv("MVGX_BA_CHAIN_FUSE")) c->chain_fuse_max_tasks = atoi(env);
-  if (const char* env = getenv("MVGX_BA_LOOKAHEAD")) c->lookahead = atoi(env) != 0;
-  if (const char* env = getenv("MVGX_BA_BACKSOLVE_FLAGS")) c->bs_one_launch = atoi(env) != 0;
-  tick("page-locked scalars");
   c->h_fail = reinterpret_cast<int*>(c->h_scalars + kSCount);
+  tick("page-locked scalars");
   Dev& d = c->d;
   d.n_poses = p->n_poses; d.n_intr = p->n_intrinsics; d.n_pts = p->n_points; d.n_obs = p->n_obs; d.n_priors = p->n_pose_priors;
   d.N = 6 * (int)d.n_poses + 8 * (int)d.n_intr; d.LD = d.N + 1;
-  d.huber_a = p->huber_a;
-  d.prior_huber_a = p->prior_huber_a;
-  c->phase_timing = getenv("MVGX_BA_PHASE_TIMING") != nullptr;
-  if (getenv("MVGX_BA_FACTOR_DEBUG")) { const int one = 1; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_factor_debug), &one, sizeof(one)); }
-  {   // (a synchronous copy: only when the setting changes)
-    static std::atomic<int> last_on{0};
-    const int on = getenv("MVGX_BA_GROUP_DEBUG") ? 1 : 0;
-    if (last_on.exchange(on) != on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_group_debug), &on, sizeof(on));
-    static std::atomic<int> last_compact{1};
-    const char* env_c = getenv("MVGX_BA_GROUP_COMPACT");
-    const int compact_on = env_c ? (atoi(env_c) != 0) : 1;
-    if (last_compact.exchange(compact_on) != compact_on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_group_compact), &compact_on, sizeof(compact_on));
-  }
-  if (const char* env = getenv("MVGX_BA_MODEL_COST")) c->model_cost_from_jacobian = !strcmp(env, "jacobian");
-  if (const char* env = getenv("MVGX_BA_SOLVER")) {
-    c->solver_mode = !strcmp(env, "dense") ? 1 : !strcmp(env, "sparse") ? 2 : 0;
-    c->solver_from_env = true;   // ("auto" included: the library's rule, whatever the caller's options say)
-  }
-  if (const char* env = getenv("MVGX_BA_TWO_LEVEL_MIN_N")) c->two_level_min_n = std::max(1, atoi(env));
-  if (const char* env = getenv("MVGX_BA_UPDATE128_MIN_TILES")) c->update128_min_tiles = std::max(1, atoi(env));
   const uint64_t no = d.n_obs;
+  read_settings(c);
   tick("settings");
   // ---- host-side structure (the analogue of Ceres' preprocessor: ordering, chunks, block structure) ----
-  const unsigned T = host_threads(no);
-  // observations sorted by point (stable): identity when the caller's list already is (a landmark-by-landmark export of an
-  // SfM_Data scene), else one counting sort
-  constexpr size_t kGrain = 16384;
-  const size_t n_grains = (size_t)((no + kGrain - 1) / kGrain);
-#define HA(type, name, n) type* name = nullptr; if ((rc = ha.array(&name, std::max<size_t>((size_t)(n), 1)))) return rc
-#define UP(field, vec) if ((rc = dev_upload(c->pool, &d.field, vec, c->stream))) return rc
-#define UPN(field, ptr, n) if ((rc = dev_upload_n(c->pool, &d.field, ptr, (size_t)(n), c->stream))) return rc
-#define AL(field, n) if ((rc = dev_alloc(c->pool, &d.field, (size_t)(n)))) return rc
-  std::vector<uint32_t> pt_start(d.n_pts + 1, 0);
-  std::atomic<int> unsorted{0};
-  parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
-    bool bad = false;
-    for (uint64_t k = std::max<uint64_t>(1, g * kGrain), e = std::min<uint64_t>(no, (g + 1) * kGrain); k < e; ++k) bad = bad || p->obs_point[k - 1] > p->obs_point[k];
-    if (bad) unsorted.store(1);
-  });
-  const bool sorted = !unsorted.load();
-  std::vector<uint64_t> perm;   // only when the caller's list is not sorted by point
-  if (sorted) {
-    // CSR starts from the boundaries of the sorted list: observation k opens the points (obs_point[k - 1], obs_point[k]]
-    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
-      for (uint64_t k = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); k < e; ++k) {
-        const uint32_t cur = p->obs_point[k], prev = k ? p->obs_point[k - 1] : UINT32_MAX;
-        if (k == 0) { for (uint32_t q = 0; q <= cur; ++q) pt_start[q] = 0; }
-        else if (cur != prev) { for (uint32_t q = prev + 1; q <= cur; ++q) pt_start[q] = (uint32_t)k; }
-      }
-    });
-    const uint32_t last = no ? p->obs_point[no - 1] : UINT32_MAX;
-    for (uint32_t q = (no ? last + 1 : 0); q <= d.n_pts; ++q) pt_start[q] = (uint32_t)no;
-  } else {
-    for (uint64_t k = 0; k < no; ++k) pt_start[p->obs_point[k] + 1]++;
-    for (uint32_t j = 0; j < d.n_pts; ++j) pt_start[j + 1] += pt_start[j];
-    perm.resize(no);
-    std::vector<uint32_t> fill(pt_start.begin(), pt_start.end() - 1);
-    for (uint64_t k = 0; k < no; ++k) perm[fill[p->obs_point[k]]++] = k;
-  }
-  // Uploads of the caller's arrays go through page-locked scratch (mvgx::HostArena), copied there by the host threads: from
-  // pageable memory hipMemcpyAsync blocks the caller and moved 8 GB/s here (18 ms for the observation list of the 5M-observation
-  // scene); from page-locked memory it is an asynchronous DMA at 50 GB/s that overlaps the rest of this function.
-  auto staged_upload = [&](auto** dev, const auto* src, size_t n) -> int {
-    using E = std::remove_cv_t<std::remove_reference_t<decltype(*src)>>;
-    int rc_ = dev_alloc(c->pool, dev, n);
-    if (rc_ || !n) return rc_;
-    if (n * sizeof(E) < (1u << 20)) { MVGX_HIP(hipMemcpyAsync(*dev, src, n * sizeof(E), hipMemcpyHostToDevice, c->stream)); return MVGX_OK; }
-    E* st = nullptr;
-    if ((rc_ = ha.array(&st, n))) return rc_;
-    const size_t per = (1u << 20) / sizeof(E), n_chunks = (n + per - 1) / per;
-    parallel_for_dynamic(n_chunks, 1, T, [&](size_t ch, unsigned) { memcpy(st + ch * per, src + ch * per, std::min(per, n - ch * per) * sizeof(E)); });
-    MVGX_HIP(hipMemcpyAsync(*dev, st, n * sizeof(E), hipMemcpyHostToDevice, c->stream));
-    return MVGX_OK;
-  };
-#define UPS(field, ptr, n) if ((rc = staged_upload(&d.field, ptr, (size_t)(n)))) return rc
-  UPS(poses, p->poses, (size_t)d.n_poses * 6); UPS(intr, p->intrinsics, (size_t)d.n_intr * 8); UPS(pts, p->points, (size_t)d.n_pts * 3);
-  UPS(model, p->intr_model, d.n_intr);
-  AL(cposes, d.n_poses * 6); AL(cintr, d.n_intr * 8); AL(cpts, (size_t)d.n_pts * 3);
-  // The observation list in point order. A list that arrives sorted is read where it lies (oorig stays null: identity); else it
-  // is gathered into the page-locked scratch.
-  const uint32_t* opose = p->obs_pose; const uint32_t* ointr = p->obs_intr; const uint32_t* opt_ = p->obs_point;
-  const double* oxy = p->obs_xy;
-  HA(uint32_t, oslot, no);
-  HA(double, oweight, p->obs_weight ? no : 0);
-  HA(uint8_t, octrl, p->obs_is_control ? no : 0);
-  if (!sorted) {
-    HA(uint32_t, g_pose, no); HA(uint32_t, g_intr, no); HA(uint32_t, g_pt, no); HA(uint32_t, g_orig, no); HA(double, g_xy, 2 * no);
-    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
-      for (uint64_t k = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); k < e; ++k) {
-        const uint64_t s_ = perm[k];
-        g_pose[k] = p->obs_pose[s_]; g_intr[k] = p->obs_intr[s_]; g_pt[k] = p->obs_point[s_]; g_orig[k] = (uint32_t)s_;
-        g_xy[2 * k] = p->obs_xy[2 * s_]; g_xy[2 * k + 1] = p->obs_xy[2 * s_ + 1];
-      }
-    });
-    opose = g_pose; ointr = g_intr; opt_ = g_pt; oxy = g_xy;
-    c->h_perm.assign(g_orig, g_orig + no);
-    UPN(oorig, g_orig, no);
-    UPN(opose, opose, no); UPN(ointr, ointr, no); UPN(opt, opt_, no); UPN(oxy, oxy, 2 * no);
-  } else {
-    UPS(opose, opose, no); UPS(ointr, ointr, no); UPS(opt, opt_, no); UPS(oxy, oxy, 2 * no);
-  }
-  std::vector<double> ctrl_count(n_grains, 0.0);
-  if (p->obs_weight || p->obs_is_control) {
-    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
-      double nc = 0;
-      for (uint64_t k = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); k < e; ++k) {
-        const uint64_t s_ = sorted ? k : perm[k];
-        if (p->obs_weight) oweight[k] = p->obs_weight[s_];
-        if (p->obs_is_control) { octrl[k] = p->obs_is_control[s_] ? 1 : 0; nc += octrl[k]; }
-      }
-      ctrl_count[g] = nc;
-    });
-    if (p->obs_weight) { UPN(oweight, oweight, no); }
-    if (p->obs_is_control) { UPN(octrl, octrl, no); }
-  }
-  double n_rmse = (double)no;
-  for (double v : ctrl_count) n_rmse -= v;
-  c->n_obs_rmse_local = n_rmse;
-  c->n_obs_rmse_all = n_rmse;
+  HostStructure S;
+  S.T = host_threads(no);
+  if ((rc = build_point_order(p, ha, S))) return rc;
+  if (!S.sorted) c->h_perm.assign(S.orig, S.orig + no);
+  // the values go up at once (their DMA overlaps the structure build); mvgx_ba_update copies into the same arrays
+  if ((rc = dev_alloc(c->pool, &d.poses, (size_t)d.n_poses * 6)) || (rc = dev_alloc(c->pool, &d.intr, (size_t)d.n_intr * 8)) ||
+      (rc = dev_alloc(c->pool, &d.pts, (size_t)d.n_pts * 3)) || (rc = dev_alloc(c->pool, &d.oxy, (size_t)(2 * no))) ||
+      (p->obs_weight && (rc = dev_alloc(c->pool, &d.oweight, (size_t)no))) ||
+      (rc = dev_alloc(c->pool, &d.prior_center, (size_t)d.n_priors * 3)) || (rc = dev_alloc(c->pool, &d.prior_weight, (size_t)d.n_priors * 3)) ||
+      (rc = upload_values(c, p, ha)))
+    return rc;
   tick("sort by point + gather");
-  std::vector<uint8_t> pose_used(d.n_poses, 0), intr_used(d.n_intr, 0), pt_free(d.n_pts, 0);
-  parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {   // (concurrent stores of the same value 1: relaxed atomic accesses)
-    auto set_flag = [](uint8_t& f) { if (!__atomic_load_n(&f, __ATOMIC_RELAXED)) __atomic_store_n(&f, (uint8_t)1, __ATOMIC_RELAXED); };
-    for (uint64_t k = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); k < e; ++k) {
-      set_flag(pose_used[opose[k]]);
-      set_flag(intr_used[ointr[k]]);
-      set_flag(pt_free[opt_[k]]);
-    }
-  });
-  for (uint32_t k = 0; k < d.n_priors; ++k) pose_used[p->prior_pose[k]] = 1;
-  for (uint32_t j = 0; j < d.n_pts; ++j)
-    if (p->points_constant || (p->point_const_mask && p->point_const_mask[j])) pt_free[j] = 0;
+  build_used_flags(p, S);
   tick("  used flags");
-  // (point, intrinsic) slots: the distinct intrinsics of a point in order of first appearance; counted, then filled
-  std::vector<uint32_t> ptk_start(d.n_pts + 1, 0);
-  const size_t n_pgrains = ((size_t)d.n_pts + 4095) / 4096;
-  parallel_for_dynamic(n_pgrains, 1, T, [&](size_t g, unsigned) {
-    for (uint32_t j = (uint32_t)(g * 4096), e = (uint32_t)std::min<size_t>(d.n_pts, (g + 1) * 4096); j < e; ++j) {
-      uint32_t n = 0;
-      for (uint32_t o = pt_start[j]; o < pt_start[j + 1]; ++o) {
-        bool seen = false;
-        for (uint32_t q = pt_start[j]; q < o && !seen; ++q) seen = ointr[q] == ointr[o];
-        n += seen ? 0u : 1u;
-      }
-      ptk_start[j + 1] = n;
-    }
-  });
-  for (uint32_t j = 0; j < d.n_pts; ++j) ptk_start[j + 1] += ptk_start[j];
-  std::vector<uint32_t> slot_intr(ptk_start[d.n_pts]), slot_point(ptk_start[d.n_pts]);
-  parallel_for_dynamic(n_pgrains, 1, T, [&](size_t g, unsigned) {
-    for (uint32_t j = (uint32_t)(g * 4096), e = (uint32_t)std::min<size_t>(d.n_pts, (g + 1) * 4096); j < e; ++j) {
-      const uint32_t first = ptk_start[j];
-      uint32_t used = first;
-      for (uint32_t o = pt_start[j]; o < pt_start[j + 1]; ++o) {
-        uint32_t s_ = first;
-        while (s_ < used && slot_intr[s_] != ointr[o]) ++s_;
-        if (s_ == used) { slot_intr[used] = ointr[o]; slot_point[used] = j; ++used; }
-        oslot[o] = s_;
-      }
-    }
-  });
-  d.n_islots = (int)slot_intr.size();
+  if ((rc = build_slots(p, ha, S))) return rc;
   tick("  point-intrinsic slots");
-  // observations by pose (ascending observation index inside a pose): the rows of the product lists; then, inside a pose,
-  // stably by intrinsic: the (pose, intrinsic) pairs of the Gram kernels, cut into chunks of kPiChunk observations
-  std::vector<uint32_t> prow_start;
-  HA(uint32_t, pose_obs, no);
-  counting_sort_indices(no, d.n_poses, T, [&](uint64_t k) { return opose[k]; }, prow_start, pose_obs);
-  tick("  counting sort by pose");
-  // (the usual case - every view has one intrinsic - needs no second list)
-  std::vector<uint8_t> pose_mixed(d.n_poses, 0);
-  std::atomic<int> any_mixed{0};
-  parallel_for_dynamic(d.n_poses, 1, T, [&](size_t i, unsigned) {
-    bool one = true;
-    for (uint32_t q = prow_start[i]; q < prow_start[i + 1] && one; ++q) one = ointr[pose_obs[q]] == ointr[pose_obs[prow_start[i]]];
-    if (!one) { pose_mixed[i] = 1; any_mixed.store(1); }
-  });
-  uint32_t* pi_obs = pose_obs;
-  if (any_mixed.load()) {
-    HA(uint32_t, pi_sorted, no);
-    pi_obs = pi_sorted;
-    parallel_for_dynamic(d.n_poses, 1, T, [&](size_t i, unsigned) {
-      uint32_t* b_ = pi_obs + prow_start[i]; uint32_t* e_ = pi_obs + prow_start[i + 1];
-      std::copy(pose_obs + prow_start[i], pose_obs + prow_start[i + 1], b_);
-      if (pose_mixed[i]) std::stable_sort(b_, e_, [&](uint32_t x, uint32_t y) { return ointr[x] < ointr[y]; });
-    });
-  }
-  UPN(pi_obs, pi_obs, no);
-  tick("  pi_obs");
-  std::vector<uint32_t> pi_start, pi_intr, pose_pi_start(d.n_poses + 1, 0), pichunk_lo, pichunk_hi, pi_chunk0;
-  {
-    std::vector<std::vector<uint32_t>> per_pose(d.n_poses);   // the first list position of every (pose, intrinsic) pair of the pose
-    parallel_for_dynamic(d.n_poses, 4, T, [&](size_t i, unsigned) {
-      for (uint32_t q = prow_start[i]; q < prow_start[i + 1]; ++q)
-        if (q == prow_start[i] || ointr[pi_obs[q]] != ointr[pi_obs[q - 1]]) per_pose[i].push_back(q);
-    });
-    for (uint32_t i = 0; i < d.n_poses; ++i) {
-      for (uint32_t q : per_pose[i]) { pi_start.push_back(q); pi_intr.push_back(ointr[pi_obs[q]]); }
-      pose_pi_start[i + 1] = (uint32_t)pi_start.size();
-    }
-  }
-  d.n_pi = (int)pi_start.size();
-  pi_start.push_back((uint32_t)no);
-  for (int q = 0; q < d.n_pi; ++q) {
-    pi_chunk0.push_back((uint32_t)pichunk_lo.size());
-    for (uint32_t lo = pi_start[q]; lo < pi_start[q + 1]; lo += kPiChunk) {
-      pichunk_lo.push_back(lo); pichunk_hi.push_back(std::min<uint32_t>(lo + kPiChunk, pi_start[q + 1]));
-    }
-  }
-  pi_chunk0.push_back((uint32_t)pichunk_lo.size());
-  d.n_pichunks = (int)pichunk_lo.size();
-  // the chunks of every intrinsic (ascending chunk id): its own Gram blocks are summed from them on the matrix-core path
-  std::vector<uint32_t> intr_pichunk_start(d.n_intr + 1, 0), intr_pichunk(pichunk_lo.size());
-  {
-    std::vector<uint32_t> chunk_intr(pichunk_lo.size());
-    for (int q = 0; q < d.n_pi; ++q)
-      for (uint32_t ch = pi_chunk0[q]; ch < pi_chunk0[q + 1]; ++ch) { chunk_intr[ch] = pi_intr[q]; intr_pichunk_start[pi_intr[q] + 1]++; }
-    for (uint32_t k = 0; k < d.n_intr; ++k) intr_pichunk_start[k + 1] += intr_pichunk_start[k];
-    std::vector<uint32_t> fill(intr_pichunk_start.begin(), intr_pichunk_start.end() - 1);
-    for (uint32_t ch = 0; ch < (uint32_t)chunk_intr.size(); ++ch) intr_pichunk[fill[chunk_intr[ch]]++] = ch;
-  }
-  tick("  pairs and chunks");
-  // the Gram kernel's inputs in (pose, intrinsic) order - the point and the image point of every observation, contiguous - are
-  // gathered on the device from the lists uploaded above; the pair of every chunk
-  AL(pi_pt, no); AL(pi_xy, no);
-  if (no) hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, c->stream, d.pi_obs, (uint32_t)no, d.opt, d.oxy, d.pi_pt, d.pi_xy);
-  std::vector<uint32_t> pichunk_pose(pichunk_lo.size()), pichunk_intr(pichunk_lo.size());
-  for (uint32_t i = 0; i < d.n_poses; ++i)
-    for (uint32_t q = pose_pi_start[i]; q < pose_pi_start[i + 1]; ++q)
-      for (uint32_t ch = pi_chunk0[q]; ch < pi_chunk0[q + 1]; ++ch) { pichunk_pose[ch] = i; pichunk_intr[ch] = pi_intr[q]; }
-  tick("  chunk pairs");
-  // pose-centre priors by pose
-  std::vector<uint32_t> prior_pose(p->prior_pose, p->prior_pose + d.n_priors), pose_prior_start(d.n_poses + 1, 0), pose_prior_idx(d.n_priors);
-  for (uint32_t k = 0; k < d.n_priors; ++k) pose_prior_start[prior_pose[k] + 1]++;
-  for (uint32_t i = 0; i < d.n_poses; ++i) pose_prior_start[i + 1] += pose_prior_start[i];
-  { std::vector<uint32_t> fill(pose_prior_start.begin(), pose_prior_start.end() - 1);
-    for (uint32_t k = 0; k < d.n_priors; ++k) pose_prior_idx[fill[prior_pose[k]]++] = k; }
+  if ((rc = build_pose_lists(p, ha, S, tick))) return rc;
+  if ((rc = upload_observation_lists(c, p, S, ha))) return rc;
   tick("slots, pose / intrinsic lists");
-  // Schur products by destination block, generated row by row on host threads. Constant / unused points have Z = 0: only
-  // their (a, a) products are listed, so that every diagonal block exists (it carries the Gram block and the rhs).
-  TripHost hpp, hpi, hii;
-  // Point groups (GroupList): free points with at most kGroupCams distinct poses and kGroupIntr distinct intrinsics, ordered by
-  // (lowest pose, highest pose, hash of the pose set); consecutive points join a group while the union of their poses stays within
-  // kGroupCams, the union of their intrinsics within kGroupIntr and the group within kGroupPts points. A group that closes because
-  // it is full hands its camera set to the next one: groups with the same set form a supergroup (one workgroup, one set of partial
-  // blocks), up to kMaxSgGroups of them. Groups of fewer than kGroupMinPts points are dissolved unless they continue a supergroup
-  // (their points stay on the record-based path, as do long tracks and constant points). MVGX_BA_GROUPS=0 disables the groups;
-  // so does MVGX_BA_MODEL_COST=jacobian (Ceres' form of the model cost reads the Jacobian records of every observation).
-  // A supergroup covers up to 2048 observations (8 groups); problems of 4 M observations and more - enough supergroups to fill the device
-  // several times either way - up to 4096 (16 groups): fewer prologues, MFMA flushes and partial blocks. MVGX_BA_SG_GROUPS=n sets the
-  // limit (sweeps of calls 83 / 84 / 86 with the largest-first launch order: C3 0.625 ms at 8, 0.654 at 12, 0.715 at 16, 0.726 at 6;
-  // C5 1.747 ms at 8, 1.729 at 12, 1.714 at 16, 1.754 at 24, 1.914 at 6).
-  int kMaxSgGroups = no >= 4000000ull ? 4096 / kGroupThreads : 2048 / kGroupThreads;
-  if (const char* env = getenv("MVGX_BA_SG_GROUPS")) kMaxSgGroups = std::max(1, std::min(64, atoi(env)));
-  std::vector<uint8_t> in_group(d.n_pts, 0);
-  std::vector<uint32_t> sg_start{0}, g_obs_start{0}, g_pt_start{0}, g_pts, g_pt_estart, g_pt_ksplit, sg_cams, sg_intrs;
-  uint32_t* g_eobs = nullptr; uint32_t* g_eq = nullptr;   // [entry]: observation, entry word (HostArena)
-  size_t n_gentries = 0;
-  std::vector<uint8_t> sg_pp, sg_pi, sg_ii;   // per supergroup: which destination blocks exist
-  {
-    const char* env = getenv("MVGX_BA_GROUPS");
-    if (!(env && atoi(env) == 0) && !c->model_cost_from_jacobian && d.n_poses && d.n_pts) {
-      std::vector<uint32_t> lo_pose(d.n_pts, UINT32_MAX), hi_pose(d.n_pts, 0);
-      std::vector<uint64_t> set_key(d.n_pts, 0);   // (highest pose, order-independent hash of the pose set): equal sets become neighbours
-      parallel_for_dynamic(n_pgrains, 1, T, [&](size_t g, unsigned) {
-        for (uint32_t j = (uint32_t)(g * 4096), e = (uint32_t)std::min<size_t>(d.n_pts, (g + 1) * 4096); j < e; ++j) {
-          const uint32_t o0 = pt_start[j], o1 = pt_start[j + 1];
-          bool ok = pt_free[j] && o1 > o0 && o1 - o0 <= (uint32_t)kGroupCams && ptk_start[j + 1] - ptk_start[j] <= (uint32_t)kGroupIntr;
-          for (uint32_t o = o0; o < o1 && ok; ++o) {
-            for (uint32_t o2 = o0; o2 < o; ++o2) ok = ok && opose[o2] != opose[o];   // a pose seen twice (shared by two views): record path
-            lo_pose[j] = std::min(lo_pose[j], opose[o]); hi_pose[j] = std::max(hi_pose[j], opose[o]);
-            uint64_t h = (uint64_t)opose[o] * 0x9E3779B97F4A7C15ull;
-            h ^= h >> 29;
-            set_key[j] += h * 0xBF58476D1CE4E5B9ull;   // commutative combination
-          }
-          set_key[j] = ((uint64_t)hi_pose[j] << 32) | (uint32_t)(set_key[j] >> 32);
-          if (!ok) lo_pose[j] = UINT32_MAX;
-          in_group[j] = ok ? 1 : 0;   // (a thread's own range of the array; the few points of dissolved groups are taken out after the sweep:
-                                      // marking points from the bucket sweep - every thread storing all over the array - was a third of that phase)
-        }
-      });
-      tick("  point keys");
-      std::vector<uint32_t> lo_start, order;   // eligible points by lowest pose (bucket n_poses: not eligible)
-      counting_sort_indices(d.n_pts, d.n_poses + 1, T, [&](uint64_t j) { return lo_pose[j] == UINT32_MAX ? d.n_poses : lo_pose[j]; }, lo_start, order);
-      parallel_for_dynamic(d.n_poses, 1, T, [&](size_t i, unsigned) {
-        std::stable_sort(order.begin() + lo_start[i], order.begin() + lo_start[i + 1], [&](uint32_t x, uint32_t y) { return set_key[x] < set_key[y]; });
-      });
-      tick("  points by lowest pose, set key");
-      // groups never span two lowest-pose buckets, so the buckets are swept independently (host threads) and their groups
-      // stitched in bucket order: the result does not depend on the thread count
-      struct BucketGroups {
-        std::vector<uint32_t> sg_n, obs_n, eobs, eq, pt_n, pts, nk0, cams, intrs, dropped;   // sg_n: groups per supergroup; nk0: per point, its observations with local intrinsic 0; dropped: points of dissolved groups
-        std::vector<uint8_t> pp, pi, ii;
-      };
-      std::vector<BucketGroups> per_bucket(d.n_poses);
-      parallel_for_dynamic(d.n_poses, 1, T, [&](size_t bucket, unsigned) {
-        BucketGroups& B = per_bucket[bucket];
-        {   // (one allocation per list instead of a doubling series)
-          size_t n_e = 0;
-          const size_t n_p = lo_start[bucket + 1] - lo_start[bucket];
-          for (uint32_t q = lo_start[bucket]; q < lo_start[bucket + 1]; ++q) n_e += pt_start[order[q] + 1] - pt_start[order[q]];
-          B.eobs.reserve(n_e); B.eq.reserve(n_e); B.pts.reserve(n_p); B.nk0.reserve(n_p);
-        }
-        std::vector<uint32_t> cams, intrs, mc, mi, cur;
-        std::vector<uint32_t> tail_cams, tail_intrs;   // sets of the supergroup under construction (sorted)
-        bool sg_open = false;
-        uint32_t cur_obs = 0;   // observations of `cur`
-        auto local = [](const std::vector<uint32_t>& v, uint32_t id) { return (int)(std::lower_bound(v.begin(), v.end(), id) - v.begin()); };
-        // which destination blocks the supergroup under construction has: a point with local poses P and local intrinsics K marks every
-        // (x <= y) of P x P, every (x, k) of P x K, every (k <= k') of K x K. Collected as bit rows (a few ORs per point; marking the
-        // flags themselves was |P|^2 stores per point and a third of this phase) and written out when the supergroup is complete.
-        uint16_t acc_pp[kGroupCams] = {0}, acc_pi[kGroupCams] = {0}, acc_ii[kGroupIntr] = {0};
-        static_assert(kGroupCams <= 16 && kGroupIntr <= 16, "bit rows of the destination-block flags");
-        bool acc_open = false;
-        auto flush_flags = [&]() {
-          if (!acc_open) return;
-          const size_t sgi = B.sg_n.size() - 1;
-          for (int x = 0; x < kGroupCams; ++x) {
-            for (int y = x; y < kGroupCams; ++y) if ((acc_pp[x] >> y) & 1u) B.pp[sgi * kGroupPairsPP + x * kGroupCams - x * (x - 1) / 2 + (y - x)] = 1;
-            for (int k = 0; k < kGroupIntr; ++k) if ((acc_pi[x] >> k) & 1u) B.pi[sgi * kGroupPairsPI + x * kGroupIntr + k] = 1;
-            acc_pp[x] = 0; acc_pi[x] = 0;
-          }
-          for (int k = 0; k < kGroupIntr; ++k) {
-            for (int k2 = k; k2 < kGroupIntr; ++k2) if ((acc_ii[k] >> k2) & 1u) B.ii[sgi * kGroupPairsII + k * kGroupIntr - k * (k - 1) / 2 + (k2 - k)] = 1;
-            acc_ii[k] = 0;
-          }
-          acc_open = false;
-        };
-        // emits `cur` as a group of the open supergroup (same camera / intrinsic sets) or as the first group of a new one
-        auto emit_group = [&](bool continues) {
-          if (!continues) {
-            flush_flags();   // (of the supergroup before)
-            B.sg_n.push_back(0);
-            const size_t sgi = B.sg_n.size() - 1;
-            B.cams.resize((sgi + 1) * kGroupCams, 0); B.intrs.resize((sgi + 1) * kGroupIntr, 0);
-            std::copy(cams.begin(), cams.end(), B.cams.begin() + sgi * kGroupCams);
-            std::copy(intrs.begin(), intrs.end(), B.intrs.begin() + sgi * kGroupIntr);
-            B.pp.resize((sgi + 1) * kGroupPairsPP, 0); B.pi.resize((sgi + 1) * kGroupPairsPI, 0); B.ii.resize((sgi + 1) * kGroupPairsII, 0);
-            tail_cams = cams; tail_intrs = intrs;
-          }
-          const size_t sgi = B.sg_n.size() - 1;
-          B.sg_n[sgi]++;
-          uint32_t n_obs_g = 0;
-          for (size_t q = 0; q < cur.size(); ++q) {
-            const uint32_t j = cur[q];
-            B.pts.push_back(j);
-            uint8_t xs[kGroupCams], ks[kGroupCams];
-            const uint32_t o0 = pt_start[j];
-            const int nx = (int)(pt_start[j + 1] - o0);
-            uint32_t n_k0 = 0;
-            for (int a = 0; a < nx; ++a) {   // local pose / intrinsic of every observation, once
-              xs[a] = (uint8_t)local(tail_cams, opose[o0 + a]); ks[a] = (uint8_t)local(tail_intrs, ointr[o0 + a]);
-              n_k0 += ks[a] == 0;
-            }
-            for (int pass = 0; pass < kGroupIntr; ++pass)   // the observations with local intrinsic 0 first, then those with 1
-              for (int a = 0; a < nx; ++a) {
-                if (ks[a] != pass) continue;
-                B.eobs.push_back(o0 + (uint32_t)a);
-                B.eq.push_back((uint32_t)q | ((uint32_t)xs[a] << 8) | ((uint32_t)ks[a] << 12));
-              }
-            n_obs_g += (uint32_t)nx;
-            B.nk0.push_back(n_k0);
-            uint16_t cm = 0, km = 0;
-            for (int a = 0; a < nx; ++a) { cm |= (uint16_t)(1u << xs[a]); km |= (uint16_t)(1u << ks[a]); }
-            for (int a = 0; a < nx; ++a) { acc_pp[xs[a]] |= cm; acc_pi[xs[a]] |= km; acc_ii[ks[a]] |= km; }
-            acc_open = true;
-          }
-          (void)sgi;
-          B.obs_n.push_back(n_obs_g);
-          B.pt_n.push_back((uint32_t)cur.size());
-        };
-        auto close_group = [&]() {
-          if (cams.size() > (size_t)kNarrowCams && !cur.empty()) {
-            // a wide group takes the EXACT union of its points' sets (a group inherits the sets of the one before it - that is what lets
-            // groups of one camera set form a supergroup - but a wide group never continues one, and its columns follow its poses in use)
-            std::vector<uint32_t> ec, ei;
-            for (uint32_t j : cur) {
-              for (uint32_t o = pt_start[j]; o < pt_start[j + 1]; ++o) { ec.push_back(opose[o]); ei.push_back(ointr[o]); }
-            }
-            std::sort(ec.begin(), ec.end()); ec.erase(std::unique(ec.begin(), ec.end()), ec.end());
-            std::sort(ei.begin(), ei.end()); ei.erase(std::unique(ei.begin(), ei.end()), ei.end());
-            cams = ec; intrs = ei;
-          }
-          const bool continues = sg_open && cams == tail_cams && intrs == tail_intrs && B.sg_n.back() < (uint32_t)kMaxSgGroups;
-          // (a wide group stays whatever its size: a handful of points left to the record-based path costs its dozen launches per iteration)
-          if (cur.size() >= (size_t)kGroupMinPts || (continues && !cur.empty()) || (cams.size() > (size_t)kNarrowCams && !cur.empty())) { emit_group(continues); sg_open = true; }
-          else { sg_open = false; B.dropped.insert(B.dropped.end(), cur.begin(), cur.end()); }
-          if (cams.size() > (size_t)kNarrowCams) { cams.clear(); intrs.clear(); }   // (the next group starts from its own points: a wide group's sets are exact, and it continues the supergroup when they come out the same)
-          cur.clear(); cur_obs = 0;
-        };
-        for (uint32_t q = lo_start[bucket]; q < lo_start[bucket + 1]; ++q) {
-          const uint32_t j = order[q];
-          // (the points of a bucket lie anywhere in the caller's order - a scene flattened from a hash map: their rows are fetched ahead,
-          // the CSR entry sixteen points ahead, the rows it names eight points ahead; 1.7 -> ms of this phase at 1 M observations were misses)
-          if (q + 16 < lo_start[bucket + 1]) { __builtin_prefetch(&pt_start[order[q + 16]]); __builtin_prefetch(&ptk_start[order[q + 16]]); }
-          if (q + 8 < lo_start[bucket + 1]) {
-            const uint32_t jn = order[q + 8], on = pt_start[jn];
-            __builtin_prefetch(&opose[on]); __builtin_prefetch(&ointr[on]); __builtin_prefetch(&slot_intr[ptk_start[jn]]);
-          }
-          uint32_t pc[kGroupCams], pk[kGroupCams];
-          int npc = 0, npk = 0;
-          for (uint32_t o = pt_start[j]; o < pt_start[j + 1]; ++o) pc[npc++] = opose[o];
-          for (uint32_t sl = ptk_start[j]; sl < ptk_start[j + 1]; ++sl) pk[npk++] = slot_intr[sl];
-          std::sort(pc, pc + npc); std::sort(pk, pk + npk);
-          // the two forms (see kNarrowCams): a group is wide once it holds a point of more than kNarrowCams poses - then up to kGroupCams
-          // poses and kWidePts points; a group of short tracks never grows wide by union alone (it closes at kNarrowCams as before)
-          const bool cur_wide = cams.size() > (size_t)kNarrowCams;
-          const size_t max_pts = cur_wide ? (size_t)kWidePts : (size_t)kGroupPts;
-          if (cur.size() >= max_pts || cur_obs + (uint32_t)npc > (uint32_t)kGroupThreads) close_group();   // full: the next group starts from the same sets (and may continue the supergroup)
-          // (neighbours in the order mostly bring nothing new: the sets stay as they are - no union, no copies)
-          const bool inside = std::includes(cams.begin(), cams.end(), pc, pc + npc) && std::includes(intrs.begin(), intrs.end(), pk, pk + npk);
-          if (inside && (npc <= kNarrowCams || cur_wide)) { cur.push_back(j); cur_obs += (uint32_t)npc; continue; }
-          mc.clear(); mi.clear();
-          std::set_union(cams.begin(), cams.end(), pc, pc + npc, std::back_inserter(mc));
-          std::set_union(intrs.begin(), intrs.end(), pk, pk + npk, std::back_inserter(mi));
-          const bool to_wide = npc > kNarrowCams || cur_wide;
-          const size_t cam_limit = to_wide ? (size_t)kGroupCams : (size_t)kNarrowCams;
-          if (mc.size() > cam_limit || mi.size() > (size_t)kGroupIntr || (to_wide && !cur_wide && cur.size() >= (size_t)kWidePts)) {
-            close_group();
-            sg_open = false;
-            mc.assign(pc, pc + npc); mi.assign(pk, pk + npk);
-          }
-          cams = mc; intrs = mi;
-          cur.push_back(j); cur_obs += (uint32_t)npc;
-        }
-        close_group();
-        flush_flags();
-      });
-      for (const BucketGroups& B : per_bucket) for (uint32_t j : B.dropped) in_group[j] = 0;
-      tick("  greedy groups per bucket");
-      // the buckets' groups stitched in bucket order: offsets from a serial prefix over the buckets, copies on host threads
-      const size_t nb = per_bucket.size();
-      std::vector<uint32_t> off_sg(nb + 1, 0), off_g(nb + 1, 0), off_e(nb + 1, 0), off_p(nb + 1, 0);
-      for (size_t b = 0; b < nb; ++b) {
-        const BucketGroups& B = per_bucket[b];
-        off_sg[b + 1] = off_sg[b] + (uint32_t)B.sg_n.size(); off_g[b + 1] = off_g[b] + (uint32_t)B.obs_n.size();
-        off_e[b + 1] = off_e[b] + (uint32_t)B.eobs.size(); off_p[b + 1] = off_p[b] + (uint32_t)B.pts.size();
-      }
-      const size_t tsg = off_sg[nb], tg = off_g[nb], te = off_e[nb], tp = off_p[nb];
-      n_gentries = te;
-      sg_start.resize(tsg + 1); g_obs_start.resize(tg + 1); g_pt_start.resize(tg + 1);
-      g_pts.resize(tp); g_pt_estart.resize(tp + 1); g_pt_ksplit.resize(tp);
-      sg_cams.resize(tsg * kGroupCams); sg_intrs.resize(tsg * kGroupIntr);
-      sg_pp.resize(tsg * kGroupPairsPP); sg_pi.resize(tsg * kGroupPairsPI); sg_ii.resize(tsg * kGroupPairsII);
-      if ((rc = ha.array(&g_eobs, std::max<size_t>(te, 1))) || (rc = ha.array(&g_eq, std::max<size_t>(te, 1)))) return rc;
-      parallel_for_dynamic(nb, 1, T, [&](size_t b, unsigned) {
-        const BucketGroups& B = per_bucket[b];
-        uint32_t g = off_g[b];
-        for (size_t sgi = 0; sgi < B.sg_n.size(); ++sgi) { g += B.sg_n[sgi]; sg_start[off_sg[b] + sgi + 1] = g; }
-        uint32_t e = off_e[b], q = off_p[b];
-        for (size_t k = 0; k < B.obs_n.size(); ++k) {
-          e += B.obs_n[k]; q += B.pt_n[k];
-          g_obs_start[off_g[b] + k + 1] = e; g_pt_start[off_g[b] + k + 1] = q;
-        }
-        std::copy(B.eobs.begin(), B.eobs.end(), g_eobs + off_e[b]);
-        std::copy(B.eq.begin(), B.eq.end(), g_eq + off_e[b]);
-        std::copy(B.pts.begin(), B.pts.end(), g_pts.begin() + off_p[b]);
-        std::copy(B.cams.begin(), B.cams.end(), sg_cams.begin() + (size_t)off_sg[b] * kGroupCams);
-        std::copy(B.intrs.begin(), B.intrs.end(), sg_intrs.begin() + (size_t)off_sg[b] * kGroupIntr);
-        std::copy(B.pp.begin(), B.pp.end(), sg_pp.begin() + (size_t)off_sg[b] * kGroupPairsPP);
-        std::copy(B.pi.begin(), B.pi.end(), sg_pi.begin() + (size_t)off_sg[b] * kGroupPairsPI);
-        std::copy(B.ii.begin(), B.ii.end(), sg_ii.begin() + (size_t)off_sg[b] * kGroupPairsII);
-        // first entry of every grouped point (its observations are consecutive entries), and where its local intrinsic 1 starts
-        uint32_t ee = off_e[b];
-        for (size_t k = 0; k < B.pts.size(); ++k) {
-          g_pt_estart[off_p[b] + k] = ee; g_pt_ksplit[off_p[b] + k] = ee + B.nk0[k];
-          ee += pt_start[B.pts[k] + 1] - pt_start[B.pts[k]];
-        }
-      });
-      g_pt_estart[tp] = (uint32_t)te;
-      tick("  stitch");
-      // (the buckets' lists go back to the allocator on the host threads: released one after the other at the end of this block they were 0.5 / 1.9 ms)
-      parallel_for_dynamic(nb, 4, T, [&](size_t b, unsigned) { per_bucket[b] = BucketGroups(); });
-    }
-  }
-  const uint32_t n_groups = (uint32_t)g_pt_start.size() - 1, n_sg = (uint32_t)sg_start.size() - 1;
+  if ((rc = build_point_groups(p, c, ha, S, tick))) return rc;
   tick("  entry starts");
-  // destination blocks of the supergroups, per product family: (row block, column block) -> partial-block id
-  TripExt gext_pp, gext_pi, gext_ii;
-  {
-    const size_t n_cb = (size_t)d.n_poses + d.n_intr;
-    const uint32_t np_ = d.n_poses;
-    gext_pp.rows.resize(n_cb); gext_pi.rows.resize(n_cb); gext_ii.rows.resize(n_cb);
-    gext_pp.ext_row.assign((size_t)n_sg * kGroupPairsPP, kNoChunk);
-    gext_pi.ext_row.assign((size_t)n_sg * kGroupPairsPI, kNoChunk);
-    gext_ii.ext_row.assign((size_t)n_sg * kGroupPairsII, kNoChunk);
-    for (uint32_t sgi = 0; sgi < n_sg; ++sgi) {
-      const uint32_t* cm = sg_cams.data() + (size_t)sgi * kGroupCams;
-      const uint32_t* im = sg_intrs.data() + (size_t)sgi * kGroupIntr;
-      for (int x = 0, t = 0; x < kGroupCams; ++x)
-        for (int y = x; y < kGroupCams; ++y, ++t)
-          if (sg_pp[(size_t)sgi * kGroupPairsPP + t]) gext_pp.rows[cm[x]].emplace_back(cm[y], sgi * kGroupPairsPP + t);
-      for (int x = 0; x < kGroupCams; ++x)
-        for (int k = 0; k < kGroupIntr; ++k)
-          if (sg_pi[(size_t)sgi * kGroupPairsPI + x * kGroupIntr + k]) gext_pi.rows[cm[x]].emplace_back(np_ + im[k], sgi * kGroupPairsPI + x * kGroupIntr + k);
-      for (int k = 0, t = 0; k < kGroupIntr; ++k)
-        for (int l = k; l < kGroupIntr; ++l, ++t)
-          if (sg_ii[(size_t)sgi * kGroupPairsII + t]) gext_ii.rows[np_ + im[k]].emplace_back(np_ + im[l], sgi * kGroupPairsII + t);
-    }
-    tick("  destination rows");
-    for (TripExt* e : {&gext_pp, &gext_pi, &gext_ii})
-      parallel_for_dynamic(n_cb, 16, T, [&](size_t r, unsigned) { std::sort(e->rows[r].begin(), e->rows[r].end()); });
-  }
+  build_group_destinations(p, c->sg_index_order, S, tick);
   tick("point groups");
-  // The observations of the points outside every group, ascending (counted per grain, then filled): the record-based path works
-  // on these alone. By pose (ascending observation inside a pose) they are the rows of the product lists; their (point, intrinsic)
-  // slots by intrinsic the rows of the intrinsic-intrinsic products.
-  uint32_t* ungrouped = nullptr;
-  size_t n_ungrouped = 0;
-  {
-    std::vector<uint32_t> cnt(n_grains + 1, 0);
-    parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
-      uint32_t n = 0;
-      for (uint64_t o = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); o < e; ++o) n += !in_group[opt_[o]];
-      cnt[g + 1] = n;
-    });
-    for (size_t g = 0; g < n_grains; ++g) cnt[g + 1] += cnt[g];
-    n_ungrouped = cnt[n_grains];
-    if ((rc = ha.array(&ungrouped, std::max<size_t>(n_ungrouped, 1)))) return rc;
-    if (n_ungrouped)
-      parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
-        uint32_t at = cnt[g];
-        if (at == cnt[g + 1]) return;
-        for (uint64_t o = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); o < e; ++o) if (!in_group[opt_[o]]) ungrouped[at++] = (uint32_t)o;
-      });
-  }
-  std::vector<uint32_t> urow_start, urow;   // [pose] -> positions in `ungrouped`
-  counting_sort_indices(n_ungrouped, d.n_poses, T, [&](uint64_t i) { return opose[ungrouped[i]]; }, urow_start, urow);
-  std::vector<uint32_t> uslots, islot_start, islot;   // slots of the points outside every group, by intrinsic (ascending slot)
-  for (uint32_t q = 0; q < (uint32_t)slot_intr.size(); ++q) if (!in_group[slot_point[q]]) uslots.push_back(q);
-  counting_sort_indices(uslots.size(), d.n_intr, T, [&](uint64_t i) { return slot_intr[uslots[i]]; }, islot_start, islot);
-  tick("lists of the ungrouped points");
-  {
-    const size_t n_cb = (size_t)d.n_poses + d.n_intr;
-    const uint32_t np = d.n_poses;
-    if ((rc = build_trip_list(n_cb, [&](uint32_t r, auto emit) {   // pose-pose: Z_a^T Z_b, pose(a) <= pose(b), same point
-          if (r >= np) return;
-          for (uint32_t q = urow_start[r]; q < urow_start[r + 1]; ++q) {   // (all products of a grouped point are formed by its group)
-            const uint32_t a = ungrouped[urow[q]], j = opt_[a];
-            for (uint32_t b = pt_start[j]; b < pt_start[j + 1]; ++b)
-              if (r <= opose[b] && (pt_free[j] || a == b)) emit(opose[b], a, b);
-          }
-        }, hpp, T, &gext_pp))) return rc;
-    tick("pose-pose products");
-    if ((rc = build_trip_list(n_cb, [&](uint32_t r, auto emit) {   // pose-intrinsic: Z_a^T Zint_slot
-          if (r >= np) return;
-          for (uint32_t q = urow_start[r]; q < urow_start[r + 1]; ++q) {
-            const uint32_t a = ungrouped[urow[q]], j = opt_[a];
-            for (uint32_t sl = ptk_start[j]; sl < ptk_start[j + 1]; ++sl)
-              if (pt_free[j] || sl == oslot[a]) emit(np + slot_intr[sl], a, sl);
-          }
-        }, hpi, T, &gext_pi))) return rc;
-    for (size_t b = 0; b < hpi.block_row.size(); ++b) {   // the (pose, intrinsic) pair whose Fc^T Fi belongs to the block
-      const uint32_t i = hpi.block_row[b], k = hpi.block_col[b] - d.n_poses;
-      for (uint32_t q = pose_pi_start[i]; q < pose_pi_start[i + 1]; ++q)
-        if (pi_intr[q] == k) hpi.block_own[b] = (int32_t)q;
-    }
-    if ((rc = build_trip_list(n_cb, [&](uint32_t r, auto emit) {   // intrinsic-intrinsic
-          if (r < np) return;
-          const uint32_t k = r - np;
-          for (uint32_t q = islot_start[k]; q < islot_start[k + 1]; ++q) {
-            const uint32_t sa = uslots[islot[q]], j = slot_point[sa];
-            for (uint32_t sb = ptk_start[j]; sb < ptk_start[j + 1]; ++sb)
-              if (k <= slot_intr[sb] && (pt_free[j] || sa == sb)) emit(np + slot_intr[sb], sa, sb);
-          }
-        }, hii, T, &gext_ii))) return rc;
-  }
-  for (const TripHost* h : {&hpp, &hpi, &hii})
-    for (size_t b = 0; b < h->block_row.size(); ++b) c->h_blocks.emplace_back(h->block_row[b], h->block_col[b]);
-  {   // does every camera block have a diagonal destination in the assemble lists? (then the LM diagonal can be applied there)
-    size_t n_diag = 0;
-    for (const TripHost* h : {&hpp, &hii})
-      for (size_t b = 0; b < h->block_row.size(); ++b) n_diag += h->block_row[b] == h->block_col[b];
-    c->diag_blocks_complete = n_diag == (size_t)d.n_poses + d.n_intr;
-  }
+  if ((rc = build_product_lists(p, ha, S, tick))) return rc;
   tick("pose-intr / intr-intr products");
-  // active / counted camera components
-  std::vector<uint8_t> cam_active, cam_counts;
-  c->h_pose_used = pose_used; c->h_intr_used = intr_used; c->h_pt_free = pt_free;
-  camera_component_flags(p, pose_used, intr_used, cam_active, cam_counts);
-  std::vector<double> h_pc(p->prior_center, p->prior_center + (size_t)d.n_priors * 3), h_pw(p->prior_weight, p->prior_weight + (size_t)d.n_priors * 3);
-  tick("masks, parameter copies");
-  UP(pt_start, pt_start); UP(ptk_start, ptk_start); UP(slot_intr, slot_intr); UP(slot_point, slot_point);
-  UP(cam_active, cam_active); UP(cam_counts, cam_counts); UP(pt_free, pt_free);
-  UP(pichunk_lo, pichunk_lo); UP(pichunk_hi, pichunk_hi); UP(pi_chunk0, pi_chunk0); UP(pose_pi_start, pose_pi_start);
-  UP(pichunk_pose, pichunk_pose); UP(pichunk_intr, pichunk_intr);
-  UP(intr_pichunk_start, intr_pichunk_start); UP(intr_pichunk, intr_pichunk);
-  UP(prior_pose, prior_pose); UP(pose_prior_start, pose_prior_start); UP(pose_prior_idx, pose_prior_idx);
-  UP(prior_center, h_pc); UP(prior_weight, h_pw); AL(Jprior, (size_t)d.n_priors * kPriorJ);
-  tick("small allocations + uploads");
-  // Jacobian records and stored Z blocks: only when some point is on the record-based path (they are indexed by observation:
-  // with point groups only the entries of the other points are ever touched)
-  const bool record_path = n_ungrouped != 0;
-  const uint64_t nrec = record_path ? no : 0;
-  AL(JA, (size_t)kJA * nrec); AL(JB, (size_t)kJB * nrec); AL(JC, (size_t)kJC * nrec);
-  AL(cn_cam, d.N); AL(g_cam, d.N); AL(scale_cam, d.N); AL(diag_cam, d.N);
-  AL(cn_pt, (size_t)d.n_pts * 3); AL(g_pt, (size_t)d.n_pts * 3); AL(scale_pt, (size_t)d.n_pts * 3); AL(diag_pt, (size_t)d.n_pts * 3);
-  AL(pichunk_part, (size_t)d.n_pichunks * kPiGram); AL(pi_gram, (size_t)d.n_pi * kPiGram); AL(pose_gram, (size_t)d.n_poses * kPoseGram);
-  AL(igram, (size_t)d.n_intr * kIntrGram);
-  AL(pichunk_ipart, (size_t)d.n_pichunks * kIntrGram);
-  AL(intr_slice_part, (size_t)d.n_intr * kIntrSlices * kIntrGram); AL(intr_arrivals, d.n_intr);
-  MVGX_HIP(hipMemsetAsync(d.intr_arrivals, 0, (size_t)std::max<uint32_t>(d.n_intr, 1) * sizeof(unsigned), c->stream));
-  AL(Linv3, (size_t)d.n_pts * 6); AL(hp, (size_t)d.n_pts * 3);
-  AL(Zpose, (size_t)nrec * 18); AL(Zint, (size_t)(record_path ? d.n_islots : 0) * 24);
-  AL(zsol, d.N); AL(step_cam, d.N); AL(step_pt, (size_t)d.n_pts * 3);
-  tick("large scratch allocations");
-  {
-    struct { TripHost* h; TripList* l; int nv; } lists[3] = {{&hpp, &d.tpp, 6 * 6 + 6}, {&hpi, &d.tpi, 6 * 8 + 6}, {&hii, &d.tii, 8 * 8 + 8}};
-    for (auto& e : lists) {
-      TripHost& h = *e.h; TripList& l = *e.l;
-      l.n_trips = (uint32_t)h.trips.size(); l.n_chunks = (uint32_t)h.chunk_lo.size(); l.n_blocks = (uint32_t)h.block_row.size();
-      if ((rc = dev_upload(c->pool, &l.trips, h.trips, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &l.chunk_lo, h.chunk_lo, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &l.chunk_hi, h.chunk_hi, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &l.chunk_diag, h.chunk_diag, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &l.block_row, h.block_row, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &l.block_col, h.block_col, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &l.block_chunk0, h.block_chunk0, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &l.block_own, h.block_own, c->stream))) return rc;
-      l.n_ext = h.n_ext;
-      if (h.n_ext && (rc = dev_upload(c->pool, &l.block_ext0, h.block_ext0, c->stream))) return rc;
-      if ((rc = dev_alloc(c->pool, &l.part, ((size_t)l.n_chunks + l.n_ext) * e.nv))) return rc;
-    }
-    tick("  trip lists");
-    d.grp.n_groups = n_groups; d.grp.n_sg = n_sg;
-    c->n_grouped_points = (uint32_t)g_pts.size();
-    c->all_points_grouped = d.n_pts != 0 && g_pts.size() == (size_t)d.n_pts;
-    if (n_sg) {
-      d.grp.n_ungrouped = (uint32_t)n_ungrouped;
-      if ((rc = dev_upload(c->pool, &d.grp.sg_start, sg_start, c->stream))) return rc;
-      c->h_sg_order.resize(n_sg);
-      for (uint32_t q = 0; q < (uint32_t)n_sg; ++q) c->h_sg_order[q] = q;
-      if (!getenv("MVGX_BA_SG_INDEX_ORDER"))   // (index order: the order of construction, for A/B runs)
-        std::stable_sort(c->h_sg_order.begin(), c->h_sg_order.end(), [&](uint32_t a, uint32_t b) {
-          return g_obs_start[sg_start[a + 1]] - g_obs_start[sg_start[a]] > g_obs_start[sg_start[b + 1]] - g_obs_start[sg_start[b]];
-        });
-      // ... the supergroups of the usual form first, the wide ones (a local pose beyond kNarrowCams in use) behind them: two launches
-      auto sg_is_wide = [&](uint32_t sgi) {
-        for (int x = kNarrowCams; x < kGroupCams; ++x)
-          if (sg_pp[(size_t)sgi * kGroupPairsPP + x * kGroupCams - x * (x - 1) / 2]) return true;
-        return false;
-      };
-      std::stable_partition(c->h_sg_order.begin(), c->h_sg_order.end(), [&](uint32_t sgi) { return !sg_is_wide(sgi); });
-      c->n_sg_wide = 0;
-      for (uint32_t sgi = 0; sgi < (uint32_t)n_sg; ++sgi) c->n_sg_wide += sg_is_wide(sgi) ? 1u : 0u;
-      if ((rc = dev_upload(c->pool, &d.grp.sg_order, c->h_sg_order, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.obs_start, g_obs_start, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.pt_start, g_pt_start, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.pts, g_pts, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.pt_estart, g_pt_estart, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.pt_ksplit, g_pt_ksplit, c->stream))) return rc;
-      if ((rc = dev_upload_n(c->pool, &d.grp.eq, g_eq, n_gentries, c->stream))) return rc;
-      if ((rc = dev_upload_n(c->pool, &d.grp.eobs, g_eobs, n_gentries, c->stream))) return rc;
-      // the image points of the entries: gathered on the device
-      if ((rc = dev_alloc(c->pool, &d.grp.exy, n_gentries))) return rc;
-      c->n_gentries = n_gentries;
-      if (n_gentries)
-        hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((n_gentries + 255) / 256)), dim3(256), 0, c->stream, d.grp.eobs, (uint32_t)n_gentries,
-                           d.opt, d.oxy, static_cast<uint32_t*>(nullptr), d.grp.exy);
-      if ((rc = dev_upload(c->pool, &d.grp.cams, sg_cams, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.intrs, sg_intrs, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.chunk_pp, gext_pp.ext_row, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.chunk_pi, gext_pi.ext_row, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.grp.chunk_ii, gext_ii.ext_row, c->stream))) return rc;
-      if ((rc = dev_upload_n(c->pool, &d.grp.ungrouped, ungrouped, n_ungrouped, c->stream))) return rc;
-      if ((rc = dev_upload(c->pool, &d.pt_grouped, in_group, c->stream))) return rc;
-      if ((rc = dev_alloc(c->pool, &d.grp.gmax_part, (size_t)n_sg))) return rc;
-      tick("  group uploads");
-    }
-  }
-  c->grid_obs = (int)std::max<uint64_t>(1, (no + 255) / 256);
-  c->grid_vec = (int)std::max<size_t>(1, (std::max<size_t>((size_t)d.N, (size_t)d.n_pts * 3) + 255) / 256);
-  AL(part, (size_t)6 * std::max(c->grid_obs, c->grid_vec) + 16);   // up to six partial sums per workgroup (ba_step_scalars_kernel)
-  AL(grp_part, (size_t)5 * d.grp.n_sg + 8);
-  AL(scalars, kSCount + 1);   // the fail word lives in the slot after the scalars: one D2H copy fetches both
-  if ((rc = dev_alloc(c->pool, &c->d_accept, (size_t)2))) return rc;
-  d.fail = reinterpret_cast<int*>(d.scalars + kSCount);
-#undef UP
-#undef UPN
-#undef UPS
-#undef AL
-#undef HA
-  MVGX_HIP(hipMemsetAsync(d.scalars, 0, kSCount * sizeof(double), c->stream));
-  MVGX_HIP(hipMemsetAsync(d.zsol, 0, (size_t)std::max(d.N, 1) * sizeof(double), c->stream));
-#define MVGX_GROUP_ATTR(mode, fam, wide_) MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_point_group_kernel<mode, fam, wide_>), hipFuncAttributeMaxDynamicSharedMemorySize, kGroupLds))
-  MVGX_GROUP_ATTR(kGroupNorms, false, false); MVGX_GROUP_ATTR(kGroupForward, false, false); MVGX_GROUP_ATTR(kGroupBacksub, false, false);
-  MVGX_GROUP_ATTR(kGroupNorms, true, false); MVGX_GROUP_ATTR(kGroupForward, true, false); MVGX_GROUP_ATTR(kGroupBacksub, true, false);
-  MVGX_GROUP_ATTR(kGroupNorms, false, true); MVGX_GROUP_ATTR(kGroupForward, false, true); MVGX_GROUP_ATTR(kGroupBacksub, false, true);
-  MVGX_GROUP_ATTR(kGroupNorms, true, true); MVGX_GROUP_ATTR(kGroupForward, true, true); MVGX_GROUP_ATTR(kGroupBacksub, true, true);
-#undef MVGX_GROUP_ATTR
-  c->pinhole_family = true;
-  for (uint32_t k = 0; k < d.n_intr; ++k) {
-    const int m = p->intr_model[k];
-    c->pinhole_family = c->pinhole_family && (m == mvgx_ba::kCamPinhole || m == mvgx_ba::kCamRadial1 || m == mvgx_ba::kCamRadial3 || m == mvgx_ba::kCamBrown);
-  }
-  if (const char* env = getenv("MVGX_BA_GENERIC_MODELS")) c->pinhole_family = c->pinhole_family && atoi(env) == 0;
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_diag_inv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sp_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sp_level_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_panel_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_update128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kUpd128Lds));
+  if ((rc = upload_structure(c, S, tick))) return rc;
+  if ((rc = set_kernel_attributes(c, p))) return rc;
   tick("product lists upload (enqueue)");
-  MVGX_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = bind_values(c, p, nullptr))) return rc;
   tick("stream drain");
   if (!mvgx::ba_create_plan_deferred() && (rc = plan_solver(c, c->h_blocks))) return rc;
   tick("reduced solve: symbolic phase");
-  if (timing) fprintf(stderr, "[mvgx_ba_create] %-36s %8.2f ms\n", "total (before the locals are released)", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count());
+  tick.total();
   guard.c = nullptr;
   *out = c;
   return MVGX_OK;
@@ -5338,10 +5518,9 @@ int mvgx_host_parallel_for(uint64_t n_items, unsigned max_workers, mvgx_host_ite
   return MVGX_OK;
 }
 
-// New values for the structure the context was built from (include/mvgx.h). What mvgx_ba_create derives from VALUES is exactly
-// what is redone here: the three parameter arrays, the image points (and their two re-ordered copies: (pose, intrinsic) order for
-// the camera Gram kernel, entry order for the point groups), weights, prior targets, the camera component flags, the loss scales.
-// Everything else in the context is a function of the fingerprinted structure. The LM state is reset by mvgx_ba_solve's start().
+// New values for the structure the context was built from (include/mvgx.h): the value path of mvgx_ba_create (upload_values,
+// bind_values) run again. Everything else in the context is a function of the fingerprinted structure. The LM state is reset by
+// mvgx_ba_solve's start().
 static int ba_update_impl(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_t* obs_enabled);
 int mvgx_ba_update(mvgx_ba_ctx* c, const mvgx_ba_problem* p) { return ba_update_impl(c, p, nullptr); }
 // ... and with a subset of the observations switched off (include/mvgx.h): the structure stays the context's; an observation that
@@ -5361,9 +5540,6 @@ static int ba_update_impl(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_
     return MVGX_ERR_STRUCTURE;
   }
   MVGX_HIP(hipSetDevice(c->device));
-  Dev& d = c->d;
-  const uint64_t no = d.n_obs;
-  const unsigned T = host_threads(no);
   mvgx::HostArena ha;   // page-locked sources of the copies; the stream is drained before it goes out of scope
   // ... on EVERY way out: an early return used to free the arena under copies still in flight. A failed update also leaves the
   // context half re-bound: it refuses to solve until an update has gone through (update_incomplete).
@@ -5371,112 +5547,8 @@ static int ba_update_impl(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_
     mvgx_ba_ctx* c; bool ok = false;
     ~Drain() { (void)hipStreamSynchronize(c->stream); c->update_incomplete = !ok; }
   } drain{c};
-  int rc = MVGX_OK;
-  auto staged_copy = [&](auto* dev, const auto* src, size_t n) -> int {
-    using E = std::remove_cv_t<std::remove_reference_t<decltype(*src)>>;
-    if (!n) return MVGX_OK;
-    if (n * sizeof(E) < (1u << 20)) { MVGX_HIP(hipMemcpyAsync(dev, src, n * sizeof(E), hipMemcpyHostToDevice, c->stream)); return MVGX_OK; }
-    E* st = nullptr;
-    const int rc_ = ha.array(&st, n);
-    if (rc_) return rc_;
-    const size_t per = (1u << 20) / sizeof(E), n_chunks = (n + per - 1) / per;
-    parallel_for_dynamic(n_chunks, 1, T, [&](size_t ch, unsigned) { memcpy(st + ch * per, src + ch * per, std::min(per, n - ch * per) * sizeof(E)); });
-    MVGX_HIP(hipMemcpyAsync(dev, st, n * sizeof(E), hipMemcpyHostToDevice, c->stream));
-    return MVGX_OK;
-  };
-  if ((rc = staged_copy(d.poses, p->poses, (size_t)d.n_poses * 6)) || (rc = staged_copy(d.intr, p->intrinsics, (size_t)d.n_intr * 8)) ||
-      (rc = staged_copy(d.pts, p->points, (size_t)d.n_pts * 3)))
-    return rc;
-  if (c->h_perm.empty()) {
-    if ((rc = staged_copy(d.oxy, p->obs_xy, (size_t)(2 * no)))) return rc;
-    if (p->obs_weight && (rc = staged_copy(d.oweight, p->obs_weight, (size_t)no))) return rc;
-  } else {   // the caller's list is not in point order: through the permutation mvgx_ba_create found
-    double* g_xy = nullptr; double* g_w = nullptr;
-    if ((rc = ha.array(&g_xy, (size_t)(2 * no))) || (p->obs_weight && (rc = ha.array(&g_w, (size_t)no)))) return rc;
-    constexpr size_t kGrain = 16384;
-    parallel_for_dynamic((size_t)((no + kGrain - 1) / kGrain), 1, T, [&](size_t g, unsigned) {
-      for (uint64_t k = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); k < e; ++k) {
-        const uint64_t s_ = c->h_perm[k];
-        g_xy[2 * k] = p->obs_xy[2 * s_]; g_xy[2 * k + 1] = p->obs_xy[2 * s_ + 1];
-        if (g_w) g_w[k] = p->obs_weight[s_];
-      }
-    });
-    if (no) MVGX_HIP(hipMemcpyAsync(d.oxy, g_xy, (size_t)(2 * no) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (g_w && no) MVGX_HIP(hipMemcpyAsync(d.oweight, g_w, (size_t)no * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  if (d.n_priors) {
-    MVGX_HIP(hipMemcpyAsync(d.prior_center, p->prior_center, (size_t)d.n_priors * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    MVGX_HIP(hipMemcpyAsync(d.prior_weight, p->prior_weight, (size_t)d.n_priors * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  // which blocks carry a residual: the structure's, or - with a subset - those of the observations that are on
-  std::vector<uint8_t> pose_used_sub, intr_used_sub, pt_free_sub, odis;
-  const std::vector<uint8_t>*pose_used = &c->h_pose_used, *intr_used = &c->h_intr_used, *pt_free = &c->h_pt_free;
-  double n_rmse = c->n_obs_rmse_all;
-  bool any_off = false;
-  if (obs_enabled) {
-    pose_used_sub.assign(d.n_poses, 0); intr_used_sub.assign(d.n_intr, 0);
-    std::vector<uint8_t> pt_seen(d.n_pts, 0);
-    odis.assign((size_t)std::max<uint64_t>(no, 1), 0);
-    n_rmse = 0;
-    {   // (host threads: the flags are bytes that only ever receive 1, the counts are summed per grain)
-      constexpr uint64_t kGrain = 1u << 15;
-      const size_t n_grains = (size_t)((no + kGrain - 1) / kGrain);
-      std::vector<double> cnt(n_grains, 0.0);
-      std::vector<uint8_t> off(n_grains, 0);
-      parallel_for_dynamic(n_grains, 1, T, [&](size_t g, unsigned) {
-        double n = 0; bool any = false;
-        for (uint64_t k = g * kGrain, e = std::min<uint64_t>(no, (g + 1) * kGrain); k < e; ++k) {   // k: position in point order; s_: the caller's index
-          const uint64_t s_ = c->h_perm.empty() ? k : c->h_perm[k];
-          if (obs_enabled[s_]) {
-            // (read before write: a few hundred flag bytes stored to by every thread for every observation bounce between the cores;
-            // relaxed atomic accesses: several host threads set the same byte - the only value it ever receives is 1)
-            auto set_flag = [](uint8_t& f) { if (!__atomic_load_n(&f, __ATOMIC_RELAXED)) __atomic_store_n(&f, (uint8_t)1, __ATOMIC_RELAXED); };
-            set_flag(pose_used_sub[p->obs_pose[s_]]);
-            set_flag(intr_used_sub[p->obs_intr[s_]]);
-            set_flag(pt_seen[p->obs_point[s_]]);
-            n += (p->obs_is_control && p->obs_is_control[s_]) ? 0.0 : 1.0;
-          } else {
-            odis[k] = 1; any = true;
-          }
-        }
-        cnt[g] = n; off[g] = any;
-      });
-      for (size_t g = 0; g < n_grains; ++g) { n_rmse += cnt[g]; any_off = any_off || off[g]; }
-    }
-    for (uint32_t k = 0; k < d.n_priors; ++k) pose_used_sub[p->prior_pose[k]] = 1;
-    pt_free_sub = c->h_pt_free;
-    for (uint32_t j = 0; j < d.n_pts; ++j) pt_free_sub[j] = pt_free_sub[j] && pt_seen[j];
-    pose_used = &pose_used_sub; intr_used = &intr_used_sub; pt_free = &pt_free_sub;
-  }
-  if (any_off) {
-    if (!c->odisabled_buf && (rc = dev_alloc(c->pool, &c->odisabled_buf, (size_t)no))) return rc;
-    MVGX_HIP(hipMemcpyAsync(c->odisabled_buf, odis.data(), (size_t)no, hipMemcpyHostToDevice, c->stream));
-    d.odisabled = c->odisabled_buf;
-  } else {
-    d.odisabled = nullptr;
-  }
-  c->n_obs_rmse_local = n_rmse;
-  c->n_obs_global = 0;   // (counted again by the next start() / mvgx_ba_evaluate: ADVICE r4 - evaluate() after an update divided by the old count)
-  if (d.n_pts) MVGX_HIP(hipMemcpyAsync(d.pt_free, pt_free->data(), (size_t)d.n_pts, hipMemcpyHostToDevice, c->stream));
-  std::vector<uint8_t> cam_active, cam_counts;
-  camera_component_flags(p, *pose_used, *intr_used, cam_active, cam_counts);
-  if (d.N) {
-    MVGX_HIP(hipMemcpyAsync(d.cam_active, cam_active.data(), cam_active.size(), hipMemcpyHostToDevice, c->stream));
-    MVGX_HIP(hipMemcpyAsync(d.cam_counts, cam_counts.data(), cam_counts.size(), hipMemcpyHostToDevice, c->stream));
-  }
-  d.huber_a = p->huber_a;
-  d.prior_huber_a = p->prior_huber_a;
-  // the two re-ordered copies of the image points
-  if (no) hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, c->stream, d.pi_obs, (uint32_t)no, d.opt, d.oxy,
-                             static_cast<uint32_t*>(nullptr), d.pi_xy);
-  if (c->n_gentries)
-    hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((c->n_gentries + 255) / 256)), dim3(256), 0, c->stream, d.grp.eobs, (uint32_t)c->n_gentries,
-                       d.opt, d.oxy, static_cast<uint32_t*>(nullptr), d.grp.exy);
-  BA_LAUNCH_CHECK();
-  // as a new context starts: no scalars, no reduced solution, no failure word left from the previous solve
-  MVGX_HIP(hipMemsetAsync(d.scalars, 0, (kSCount + 1) * sizeof(double), c->stream));
-  MVGX_HIP(hipMemsetAsync(d.zsol, 0, (size_t)std::max(d.N, 1) * sizeof(double), c->stream));
-  MVGX_HIP(hipStreamSynchronize(c->stream));
+  int rc;
+  if ((rc = upload_values(c, p, ha)) || (rc = bind_values(c, p, obs_enabled))) return rc;
   c->started = false; c->finished = false;
   c->gmax_pending = false; c->gmax_resolved = false; c->fail_clear = false; c->fold_cand_now = false; c->candidate_cost_done = false;
   drain.ok = true;
