@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the MI355X matching + BA hot path (contract: see the driver's prompt).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W            the headline leg alone: set up, warm up, time K steps, print the line
+  python bench.py --gpus N --steps K --warmup W --full     ... and every side record and check after the same timed steps
 
 One "step" = one pass of the matching hot path over this rank's shard of the exhaustive pair list (+ one BA LM
 iteration on the BA scene when the BA kernels are built). Workloads (BASELINE.json):
@@ -14,6 +15,11 @@ and configs[4] itself, point-sharded over the N ranks with the RCCL exchange, at
 `value` = descriptor pairs (distance evaluations) per second over all ranks, inputs resident in HBM when the clock
 starts, result lists delivered to host memory inside the timed region (streamed batch by batch through two pinned buffers
 per rank - mvgx_match_run_stream - so the host footprint does not depend on the size of the run).
+
+A plain run stops there: its line carries the headline fields, the workload and the roofline figures the timed steps' own kernel
+timers give. --full adds what takes runs of its own - the CPU reference beside the device with the sampled parity check, the N > 1
+self-check, the BA scenes, the Hamming / float / 144-byte matchers, the Matcher_Regions::Match boundary, the geometric filters and
+guided matching - and writes the full records to the side file; the timed steps and the headline are the same in both forms.
 """
 import argparse
 import json
@@ -67,6 +73,10 @@ def parse():
     ap.add_argument("--filter-shape", type=int, default=0, help="MFMA shape of the filter kernel: 16 (v_mfma_i32_16x16x64_i8, library default), 17 (the same with three workgroups per CU: l2_filter16h_kernel) or 32 (A/B runs)")
     ap.add_argument("--collect", action="store_true", help="keep the run's match lists in one pinned host buffer (mvgx_match_run) "
                                                            "instead of streaming them (default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else: the CPU baseline and the parity of a sample, "
+                         "the N > 1 self-check, the BA, Hamming, float / 144-byte L2, adapter-boundary, geometric-filter and guided-matching "
+                         "records (each can still be switched off by its --no-... option); without it only the headline leg runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--parity-seconds", type=float, default=2.0, help="N > 1: seconds of CPU matching per rank for the sampled parity check")
@@ -88,6 +98,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run is the headline leg alone: every side leg is one of these switches
+        args.no_cpu_baseline = args.no_selfcheck = args.no_ba = args.no_ba_c5 = args.no_hamming = True
     return args
 
 
@@ -219,7 +231,9 @@ def emit(out, args):
     import bench_line
     side_rel = os.path.join("gpurun_out", "bench_side.json")
     try:
-        if getattr(args, "rehearsal", False):
+        if not args.full:   # a plain run has no side records: the line is all of it, and a --full run's file stays as it is
+            side_rel = None
+        elif getattr(args, "rehearsal", False):
             # (the CPU test of the control flow must not replace the measurement the last GPU run left in gpurun_out/ - VERDICT r5 item 7)
             import tempfile
             fd, side_rel = tempfile.mkstemp(prefix="mvgx_bench_rehearsal_side_", suffix=".json")
@@ -245,6 +259,8 @@ class quiet_stderr:
     """fd 2 -> gpurun_out/bench_stderr.log while the reference's code runs (its logger writes `INFO: [Matcher_Regions.cpp:41] ...` and
     Ceres reports to stderr; on the driver's capture that chatter followed - and displaced - the bench line of round 4). Python-level
     tracebacks of this process still reach the real stderr: the redirection is undone on exit of the block."""
+    saved = None
+
     def __enter__(self):
         try:
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -470,7 +486,8 @@ def main():
     watchdog.daemon = True
     watchdog.start()
     quiet = quiet_stderr()   # the side legs run the reference beside the device: its stderr logging goes to gpurun_out/bench_stderr.log
-    quiet.__enter__()
+    if args.full:
+        quiet.__enter__()
     if not args.no_ba:   # every rank takes part (the BA leg has a real exchange step); rank 0 reports
         try:
             from bench_ba import ba_bench_record

@@ -1,6 +1,6 @@
 """bench.py --gpus 2 without the hardware: the driver's N > 1 launch line -
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 ... - with
---rehearsal: gloo instead of RCCL, the HIP emulation libraries (the same device source compiled for the host) instead of libmvgx_hip.so,
+--full (the self-check, the parity turns and the BA leg run only there) and --rehearsal: gloo instead of RCCL, the HIP emulation libraries (the same device source compiled for the host) instead of libmvgx_hip.so,
 the BA exchange through the library's callback transport over gloo, a tiny image set and BA scene. What runs is the control flow of
 bench.py / bench_ba.py / tools/scale_selfcheck.py that no box has ever executed with N > 1: the gloo wait group around the self-check
 subprocess, pair sharding, max-over-ranks timing, the per-rank parity turn-taking, the sharded BA leg beside the reference on the
@@ -28,7 +28,7 @@ def _run_bench(n, extra=()):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-           "--rehearsal", "--side-deadline", "600", *extra]
+           "--full", "--rehearsal", "--side-deadline", "600", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

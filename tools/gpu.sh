@@ -22,8 +22,8 @@ for mode in "$@"; do
   tests:*)    # tests:<pytest args>, e.g. tests:tests/test_real_images.py
     sel=${mode#tests:}; sel=${sel//+/ }   # ('+' separates several paths / arguments)
     timeout 1500 python -m pytest $sel -m gpu -q -s > "$O/pytest_sel.log" 2>&1; echo "pytest rc=$?"; tail -8 "$O/pytest_sel.log" ;;
-  bench)      # the driver's command
-    (time timeout 1500 python bench.py) > "$O/bench.json" 2> "$O/bench.err"; tail -4 "$O/bench.err"
+  bench)      # the whole benchmark: the headline leg and every side record
+    (time timeout 1500 python bench.py --full) > "$O/bench.json" 2> "$O/bench.err"; tail -4 "$O/bench.err"
     echo "stdout lines: $(wc -l < "$O/bench.json"), last line bytes: $(tail -1 "$O/bench.json" | wc -c)"
     cp gpurun_out/bench_side.json "$O/bench_full.json" 2>/dev/null; cp gpurun_out/bench_stderr.log "$O/bench_reference_stderr.log" 2>/dev/null
     python tools/bench_summary.py "$O/bench_full.json" ;;

@@ -8,7 +8,7 @@ the hot path inside THIS process and compares them with the one-device run:
              mvgx_comm.hip inside mvgx_ba_comm_init - and the peer-mapped sums over xGMI) against one device: same iteration
              counts, final RMSE equal to 1e-12.
 Prints one JSON line; exit status 0 iff everything agreed (or only one device is visible: {"devices": 1, "skipped": true}).
-bench.py --gpus N runs it from rank 0 before the timed region and copies the line into its record ("scale_selfcheck")."""
+bench.py --gpus N --full runs it from rank 0 before the timed region and copies the line into its record ("scale_selfcheck")."""
 import json
 import os
 import sys
