@@ -66,6 +66,7 @@ constexpr int kWinRows = kWinTiles * kTileRows;  // 256 -> 8 index bits in the p
 constexpr int kWaves = 4;                     // waves per workgroup
 constexpr int kNQ = 4;                        // query tiles per wave (register-resident)
 constexpr int kBlockQTiles = kWaves * kNQ;    // 16 tiles = 512 queries per workgroup
+constexpr int kRecQuads = 1 + kWaves;         // uint4 words of a wave-packed record (MatchParams::work8): the shared part + one part per wave
 constexpr int kStageBytes = kWinTiles * kTileBytes + kWinTiles * kTileRows * 4;  // 32768 + 1024
 constexpr int kRPad = INT_MIN + 512;
 constexpr int kCPad = -(1 << 27);             // accumulator init of pad slots (real values are > -2^22)
@@ -90,7 +91,9 @@ struct MatchParams {
   const uint2* pairs;              // batch-local (I, J)
   const uint2* work;               // (batch-local pair index, first query tile)
   const uint4* work8h;             // ... for l2_filter16h_kernel: one record per 8 query tiles (256 query slots)
-  const uint4* work8;              // the same items as 32-byte records for l2_filter16_kernel: (pair, first query tile, tileI0, tileJ0), (ntI, ntJpad, 0, 0)
+  const uint4* work8;              // wave-packed records of l2_filter16_kernel and its verify launch, kRecQuads words each: (tileI0, ntI, 0, 0) shared by
+                                   // the workgroup, then per wave (pair, tileJ0, first query tile, ntJpad) - a unit of kNQ query tiles of any pair with
+                                   // this database image; ntJpad = 0: an empty wave (loads and barriers as the others, stores nothing)
   uint32_t n_work;
   uint32_t* best;                  // [batch pairs][qstride], indexed by query SLOT: original index in I or kNoMatch
   int2* cd;                        // filter -> verify: (d0, upper bound of d1) of a candidate query slot
@@ -758,13 +761,16 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   const int g4 = lane >> 4, par = g4 & 1;
 
   const uint32_t w = xcd_remap(blockIdx.x, gridDim.x);
-  const uint4 wr0 = p.work8[2 * (size_t)w], wr1 = p.work8[2 * (size_t)w + 1];   // one 32-byte record: no dependent table walks before the first load of data
-  struct { uint32_t x, y; } wk = {wr0.x, wr0.y};
-  const uint32_t tileI0 = wr0.z, tileJ0 = wr0.w;
-  const uint32_t ntJpad = wr1.y;
-  const int ntI = (int)wr1.x;
+  // one record, two scalar loads issued together (the shared part and this wave's own): no dependent table walks before the first load
+  // of data. Everything the staging loads and the barriers depend on (tileI0, ntI) is in the shared part: the four waves may serve four
+  // different pairs, but they stream the same database image in step.
+  const uint4* rec = p.work8 + (size_t)kRecQuads * w;
+  const uint4 wsh = rec[0], wun = rec[1 + wave];
+  const uint32_t tileI0 = wsh.x;
+  const int ntI = (int)wsh.y;
+  const uint32_t pair = wun.x, tileJ0 = wun.y, qt0 = wun.z;
+  const uint32_t ntJpad = wun.w;   // 0: an empty wave of a record that was closed early
   const int nwin = (ntI + kWinTiles - 1) / kWinTiles;
-  const uint32_t qt0 = wk.y + (uint32_t)wave * kNQ;
 
   // byte offset of this lane's 16-byte chunk inside a tile, block 0, k-step 0 (see above)
   const int lane_chunk = ((lane >> 5) * 64 + ((lane >> 4) & 1) * 32 + (lane & 15)) * 16;
@@ -923,7 +929,7 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
       const int nq = qn[n];
       const int d0 = nq - W1, d1ub = nq - V2;
       const bool cand = valid && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));
-      const size_t o = (size_t)wk.x * p.qstride + q;
+      const size_t o = (size_t)pair * p.qstride + q;
       p.best[o] = cand ? (uint32_t)code : kNoMatch;
       if (cand) p.cd[o] = make_int2(d0, d1ub);
     }
@@ -1103,28 +1109,42 @@ __global__ __launch_bounds__(256, 3) void l2_filter16h_kernel(MatchParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// l2_verify (variant 4, stage 2): finishes the candidates of the filter. Same work items as the filter (a workgroup
-// owns 512 query slots of one pair). 16 lanes per candidate recompute the exact distances of the 16 slots of its
+// l2_verify (variant 4, stage 2): finishes the candidates of the filter. Same work items as the filter: kWaveUnits = false, a
+// workgroup owns 512 query slots of one pair (p.work); kWaveUnits = true (after l2_filter16_kernel), each WAVE owns the 128 query
+// slots of its own part of a wave-packed record (p.work8) - the waves never shared anything here, each adds to count[] by itself.
+// Either way exactly the slots of best[] that the filter launch before it wrote are read: the two batch slots reuse best[], and a
+// stale word is a valid candidate code of some other pair. 16 lanes per candidate recompute the exact distances of the 16 slots of its
 // (P-class, window, half) cell with v_dot4_i32_i8 on the tile bytes, take the cell's best (must equal d0) and its
 // runner-up, d1 = min(d1_ub, runner-up), and evaluate the reference's fp32 ratio test. best[] receives the ORIGINAL
 // index in I or kNoMatch; count[] the accepted queries of the pair.
 // ------------------------------------------------------------------------------------------------
+template <bool kWaveUnits>
 __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const uint2 wk = p.work[blockIdx.x];
-  const uint2 ij = p.pairs[wk.x];
-  const uint32_t I = ij.x, J = ij.y;
-  const uint32_t tileI0 = p.img_tile_off[I], tileJ0 = p.img_tile_off[J];
-  const uint32_t ntJpad = p.img_tile_off[J + 1] - tileJ0;
+  uint32_t pair, qt0, I, tileI0, tileJ0, ntJpad;
+  if constexpr (kWaveUnits) {
+    const uint4* rec = p.work8 + (size_t)kRecQuads * blockIdx.x;
+    const uint4 wun = rec[1 + __builtin_amdgcn_readfirstlane(wave)];   // wave-uniform: the unit stays in scalar registers
+    pair = wun.x; tileJ0 = wun.y; qt0 = wun.z; ntJpad = wun.w;   // an empty wave (ntJpad = 0) reads no slot below
+    tileI0 = rec[0].x;
+    I = p.pairs[pair].x;
+  } else {
+    const uint2 wk = p.work[blockIdx.x];
+    const uint2 ij = p.pairs[wk.x];
+    pair = wk.x; qt0 = wk.y + (uint32_t)wave * kNQ;
+    I = ij.x;
+    tileI0 = p.img_tile_off[I]; tileJ0 = p.img_tile_off[ij.y];
+    ntJpad = p.img_tile_off[ij.y + 1] - tileJ0;
+  }
   const uint32_t nEvenI = p.img_neven[I], nOddI = p.img_n[I] - nEvenI;
   const int l16 = lane & 15, sub = lane >> 4;
   uint32_t accepted = 0;
   for (int part = 0; part < 2; ++part) {
-    const uint32_t q0 = (wk.y + (uint32_t)wave * kNQ) * kTileRows + (uint32_t)part * 64;
+    const uint32_t q0 = qt0 * kTileRows + (uint32_t)part * 64;
     const uint32_t q = q0 + lane;
     const bool inb = q < ntJpad * kTileRows;
-    const uint32_t code = inb ? p.best[(size_t)wk.x * p.qstride + q] : kNoMatch;
+    const uint32_t code = inb ? p.best[(size_t)pair * p.qstride + q] : kNoMatch;
     unsigned long long todo = __ballot(code != kNoMatch);
     while (todo) {
       // the sub-th pending candidate of this round goes to lane group `sub`
@@ -1144,7 +1164,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
       const int mrow = slot_row(2 * s1 + rsel, hw);
       const size_t slot0 = (size_t)tileI0 * kTileRows + (active ? (size_t)g1 * kWinTiles * kTileRows + mrow : 0);
       const size_t slotQ = (size_t)tileJ0 * kTileRows + (active ? qs : 0);
-      const size_t o = (size_t)wk.x * p.qstride + (active ? qs : 0);
+      const size_t o = (size_t)pair * p.qstride + (active ? qs : 0);
       // the row this lane finally owns: rho = 2 * (l16 & 7) + (l16 >> 3)  (a permutation of 0..15)
       const uint32_t tt = (uint32_t)g1 * kWinTiles + (uint32_t)piece;
       const size_t slotI = active ? slot0 + (size_t)piece * kTileRows : slot0;
@@ -1210,7 +1230,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
       accepted += (uint32_t)__popcll(__ballot(ok));
     }
   }
-  if (lane == 0 && accepted) atomicAdd(&p.count[wk.x], accepted);
+  if (lane == 0 && accepted) atomicAdd(&p.count[pair], accepted);
 }
 
 // statistics (profile mode only): candidates the filter hands to the verify stage. One atomic per 16 K slots — a single
@@ -1230,6 +1250,25 @@ __global__ __launch_bounds__(256) void count_candidates_kernel(const uint32_t* _
   (void)m;
   for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_sum, c);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_sum) atomicAdd(counter, s_sum);
+}
+
+// ... after l2_filter16_kernel: the same count over the wave units of the records, i.e. over exactly the slots that launch wrote (the
+// sweep above would also count what an earlier batch left in the tiles between 4 * ceil(ntJ / 4) and ntJpad). One atomic per record.
+__global__ __launch_bounds__(256) void count_candidates_units_kernel(MatchParams p, uint32_t* __restrict__ counter) {
+  __shared__ uint32_t s_sum;
+  if (threadIdx.x == 0) s_sum = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint4 wun = p.work8[(size_t)kRecQuads * blockIdx.x + 1 + wave];
+  uint32_t c = 0;
+  for (int part = 0; part < 2; ++part) {
+    const uint32_t q = wun.z * kTileRows + (uint32_t)part * 64 + (uint32_t)lane;
+    const bool cand = q < wun.w * kTileRows && p.best[(size_t)wun.x * p.qstride + q] != kNoMatch;
+    c += (uint32_t)__popcll(__ballot(cand));
+  }
+  if (lane == 0 && c) atomicAdd(&s_sum, c);
   __syncthreads();
   if (threadIdx.x == 0 && s_sum) atomicAdd(counter, s_sum);
 }
@@ -1832,10 +1871,12 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     if ((rc = sl.hp_work.ensure((size_t)nb * max_blocks_per_pair))) return rc;
     const bool records = c->variant == 4 && c->filter_shape == 16 && c->stage == 3 && !c->debug_filter;
     const bool records_h = c->variant == 4 && c->filter_shape == 17 && c->stage == 3 && !c->debug_filter;
-    if (records && (rc = sl.hp_work8.ensure((size_t)nb * max_blocks_per_pair * 2))) return rc;
+    // wave-packed records: the units of a pair are consecutive and share I, so they leave at most one record part-filled per pair
+    if (records && (rc = sl.hp_work8.ensure((size_t)nb * max_blocks_per_pair * kRecQuads))) return rc;
     if (records_h && (rc = sl.hp_work8h.ensure((size_t)nb * max_blocks_per_pair * 4))) return rc;
     uint32_t n_work_h = 0;
     uint32_t n_work = 0;
+    uint32_t n_rec = 0, rec_used = kWaves, rec_I = 0;   // records written; waves taken in the open one (kWaves: none is open) and its database image
     for (uint32_t k = 0; k < nb; ++k) {
       const uint32_t I = pairs_IJ[2 * (p0 + k)], J = pairs_IJ[2 * (p0 + k) + 1];
       sl.hp_pairs.p[k] = make_uint2(I, J);
@@ -1843,11 +1884,21 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
       // matcher_brute_force.hpp:108-113: NN(=2) > rows  -> no result; Matcher_Regions.cpp:65-69,85-90: empty regions skipped
       if (nI < 2 || nJ == 0) continue;
       const uint32_t ntJ = c->h_ntiles[J];   // occupied tiles of the query image
-      for (uint32_t qt = 0; qt < ntJ; qt += kBlockQTiles) {
-        if (records) {   // everything the filter's workgroup needs to start, in ONE scalar load (it used to walk work -> pairs -> three per-image tables)
-          sl.hp_work8.p[2 * n_work] = make_uint4(k, qt, c->h_tile_off[I], c->h_tile_off[J]);
-          sl.hp_work8.p[2 * n_work + 1] = make_uint4(c->h_ntiles[I], c->h_tile_off[J + 1] - c->h_tile_off[J], 0, 0);
+      // l2_filter16_kernel: units of kNQ query tiles, one per wave, packed four to a workgroup across the pairs that share I - a pair costs
+      // ceil(ntJ / 4) waves, not 4 * ceil(ntJ / 16). A record holds everything its workgroup needs to start (no walk work -> pairs -> three
+      // per-image tables). It is closed when it is full, when I changes and at the end of the batch; its unused waves are empty units
+      // (ntJpad = 0: nothing stored) whose query pointer is aimed at I's own first tiles.
+      if (records)
+        for (uint32_t qt = 0; qt < ntJ; qt += kNQ) {
+          if (rec_used == kWaves || rec_I != I) {
+            uint4* r = sl.hp_work8.p + (size_t)kRecQuads * n_rec++;
+            r[0] = make_uint4(c->h_tile_off[I], c->h_ntiles[I], 0, 0);
+            for (int w = 0; w < kWaves; ++w) r[1 + w] = make_uint4(0, c->h_tile_off[I], 0, 0);
+            rec_used = 0; rec_I = I;
+          }
+          sl.hp_work8.p[(size_t)kRecQuads * (n_rec - 1) + 1 + rec_used++] = make_uint4(k, c->h_tile_off[J], qt, c->h_tile_off[J + 1] - c->h_tile_off[J]);
         }
+      for (uint32_t qt = 0; qt < ntJ; qt += kBlockQTiles) {
         if (records_h)
           for (uint32_t q2 = qt; q2 < std::min(ntJ, qt + (uint32_t)kBlockQTiles); q2 += kBlockQTilesH) {
             sl.hp_work8h.p[2 * n_work_h] = make_uint4(k, q2, c->h_tile_off[I], c->h_tile_off[J]);
@@ -1861,7 +1912,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     }
     if ((rc = sl.d_pairs.ensure(nb))) return rc;
     if ((rc = sl.d_work.ensure(std::max<uint32_t>(n_work, 1)))) return rc;
-    if (records && (rc = sl.d_work8.ensure((size_t)std::max<uint32_t>(n_work, 1) * 2))) return rc;
+    if (records && (rc = sl.d_work8.ensure((size_t)std::max<uint32_t>(n_rec, 1) * kRecQuads))) return rc;
     if (records_h && (rc = sl.d_work8h.ensure((size_t)std::max<uint32_t>(n_work_h, 1) * 2))) return rc;
     if ((rc = sl.d_best.ensure((size_t)nb * c->qstride))) return rc;
     if (c->variant == 4) {
@@ -1871,10 +1922,10 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     if ((rc = sl.d_offsets.ensure((size_t)nb + 1))) return rc;
     if ((rc = sl.hp_offsets.ensure((size_t)nb + 1))) return rc;
     MVGX_HIP(hipMemcpyAsync(sl.d_pairs.p, sl.hp_pairs.p, nb * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    if (n_work)
+    if (n_work && !records)   // (with records no kernel reads the 16-tile list: it only counts the pairs' work here)
       MVGX_HIP(hipMemcpyAsync(sl.d_work.p, sl.hp_work.p, n_work * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    if (n_work && records)
-      MVGX_HIP(hipMemcpyAsync(sl.d_work8.p, sl.hp_work8.p, (size_t)n_work * 2 * sizeof(uint4), hipMemcpyHostToDevice, stream));
+    if (n_rec)
+      MVGX_HIP(hipMemcpyAsync(sl.d_work8.p, sl.hp_work8.p, (size_t)n_rec * kRecQuads * sizeof(uint4), hipMemcpyHostToDevice, stream));
     if (n_work_h && records_h)
       MVGX_HIP(hipMemcpyAsync(sl.d_work8h.p, sl.hp_work8h.p, (size_t)n_work_h * 2 * sizeof(uint4), hipMemcpyHostToDevice, stream));
     MVGX_HIP(hipMemsetAsync(sl.d_count.p, 0, nb * sizeof(uint32_t), stream));
@@ -1906,7 +1957,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
       } else if (c->variant == 3) {
         hipLaunchKernelGGL(l2_top2_ratio_kernel<kStageGldsAsm>, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
       } else if (c->filter_shape == 16 && c->stage == 3 && !c->debug_filter) {
-        hipLaunchKernelGGL(l2_filter16_kernel, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
+        hipLaunchKernelGGL(l2_filter16_kernel, dim3(n_rec), dim3(256), 2 * kStageBytes, stream, mp);
       } else if (c->filter_shape == 17 && c->stage == 3 && !c->debug_filter) {
         hipLaunchKernelGGL(l2_filter16h_kernel, dim3(n_work_h), dim3(256), 2 * kHalfStageBytes, stream, mp);
       } else if (c->stage == 1) {
@@ -1931,10 +1982,16 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
       if (c->variant == 4 && !(c->debug_filter & 7)) {
         if (c->profile >= 2) {   // statistics pass (0.13 ms per batch): only on request, not in the timed runs of bench.py ("profile" 1)
           const size_t nslots = (size_t)nb * c->qstride;
-          hipLaunchKernelGGL(count_candidates_kernel, dim3((unsigned)((nslots + 16383) / 16384)), dim3(256), 0, stream,
-                             sl.d_best.p, nslots, c->d_err.p + 1);
+          if (records)
+            hipLaunchKernelGGL(count_candidates_units_kernel, dim3(n_rec), dim3(256), 0, stream, mp, c->d_err.p + 1);
+          else
+            hipLaunchKernelGGL(count_candidates_kernel, dim3((unsigned)((nslots + 16383) / 16384)), dim3(256), 0, stream,
+                               sl.d_best.p, nslots, c->d_err.p + 1);
         }
-        hipLaunchKernelGGL(l2_verify_kernel, dim3(n_work), dim3(256), 0, stream, mp);
+        if (records)   // the verify stage walks the units the filter just wrote, nothing else of best[]
+          hipLaunchKernelGGL(l2_verify_kernel<true>, dim3(n_rec), dim3(256), 0, stream, mp);
+        else
+          hipLaunchKernelGGL(l2_verify_kernel<false>, dim3(n_work), dim3(256), 0, stream, mp);
         MVGX_HIP(hipGetLastError());
       }
       if (c->verify_alone) MVGX_HIP(hipEventRecord(sl.ev_filter, stream));
