@@ -100,7 +100,9 @@ int mvgx_match_set_regions(mvgx_match_ctx* ctx, const uint8_t* const* desc_rows,
                            uint32_t n_images, uint32_t dim);
 
 /* Same, descriptors already resident on the device: one concatenated (sum n_desc) x 128 row-major uint8
- * buffer (device pointer), image k starting at row sum_{m<k} n_desc[m]. */
+ * buffer (device pointer), image k starting at row sum_{m<k} n_desc[m]. The buffer is NOT copied: it stays the
+ * caller's and must remain valid and unchanged until the regions are replaced or the context is destroyed (the runs
+ * read query rows from it). */
 int mvgx_match_set_regions_device(mvgx_match_ctx* ctx, const void* d_desc_concat, const uint32_t* n_desc,
                                   uint32_t n_images, uint32_t dim);
 

@@ -26,6 +26,9 @@
 //   cinit  : int32 per slot, C = -floor(|a'|^2 / 2); pad slots hold kCPad     (filter kernel, variant 4)
 //   qnorm  : int32 per slot, |a'|^2.
 //   perm   : uint32 per slot, original row index (kNoMatch for pad slots); rowpos: slot of each original row.
+//   qtiles : int8, a SECOND fragment-major tile set for the query role of l2_filter16_kernel: the rows in their original order,
+//            ceil(n / 32) tiles per image (the parity split inflates the count above to ceil(max(n_even, n_odd) / 16), which only the
+//            database role needs); qtnorm: |a'|^2 per slot of it. A query slot of that kernel's best[] / cd[] is the original row.
 //
 // Kernel l2_top2_ratio: one 256-thread workgroup = 4 waves = 512 queries of image J against all of image I.
 // Each wave keeps 4 query tiles (128 queries, 64 VGPRs) resident as MFMA B operands for its whole life and
@@ -88,14 +91,17 @@ struct MatchParams {
   const uint32_t* img_n;           // descriptors per image
   const uint32_t* img_ntiles;      // occupied tiles per image
   const uint32_t* img_neven;       // rows of even squared norm per image (slots of a parity half are filled in rank order)
+  const int8_t* qtiles;            // dense query tiles (l2_filter16_kernel): query slot q of an image IS its original row q
+  const int* qtnorm;               // |a'|^2 per dense query slot
   const uint2* pairs;              // batch-local (I, J)
   const uint2* work;               // (batch-local pair index, first query tile)
   const uint4* work8h;             // ... for l2_filter16h_kernel: one record per 8 query tiles (256 query slots)
   const uint4* work8;              // wave-packed records of l2_filter16_kernel and its verify launch, kRecQuads words each: (tileI0, ntI, 0, 0) shared by
-                                   // the workgroup, then per wave (pair, tileJ0, first query tile, ntJpad) - a unit of kNQ query tiles of any pair with
-                                   // this database image; ntJpad = 0: an empty wave (loads and barriers as the others, stores nothing)
+                                   // the workgroup, then per wave (pair, tileJ0, first query tile, nJ) - a unit of kNQ DENSE query tiles (qtiles: tileJ0
+                                   // is J's first one, nJ its rows) of any pair with this database image; nJ = 0: an empty wave (loads and barriers
+                                   // as the others, stores nothing)
   uint32_t n_work;
-  uint32_t* best;                  // [batch pairs][qstride], indexed by query SLOT: original index in I or kNoMatch
+  uint32_t* best;                  // [batch pairs][qstride], indexed by query SLOT (l2_filter16_kernel and after it: dense slot = row): original index in I or kNoMatch
   int2* cd;                        // filter -> verify: (d0, upper bound of d1) of a candidate query slot
   uint32_t* count;                 // [batch pairs]: accepted matches
   uint32_t* errflag;               // internal-consistency violations seen by the verify kernel (must stay 0)
@@ -211,6 +217,36 @@ __global__ __launch_bounds__(256) void build_tiles_kernel(const uint8_t* __restr
   *reinterpret_cast<uint4*>(tiles + (size_t)gt * kTileBytes + c * 16) = v;
   // the same int8 bytes once more, row-major in slot order (128 contiguous bytes per slot): what the verify stage reads
   *reinterpret_cast<uint4*>(rows_slot + ((size_t)gt * kTileRows + m) * kDim + (s * 2 + h) * 16) = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// prep, dense query set: the rows of an image in their ORIGINAL order as fragment-major int8 tiles, ceil(n / 32) tiles per image (no parity
+// split: a query is a column of the distance tile, its norm is added after the merge and its parity is never used), and |a'|^2 per slot.
+// Same bytes, chunk order and centring as build_tiles_kernel; only the row-to-slot map differs (slot = row). Slots past n are zero rows.
+// grid = (max dense tiles per image, n_images), block = 256 (one 16-byte chunk per thread)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void build_qtiles_kernel(const uint8_t* __restrict__ rows,
+                                                           const uint64_t* __restrict__ img_row_off,
+                                                           const uint32_t* __restrict__ img_qtile_off,
+                                                           const uint32_t* __restrict__ img_n,
+                                                           const int* __restrict__ rownorm, int8_t* __restrict__ qtiles,
+                                                           int* __restrict__ qtnorm) {
+  const uint32_t img = blockIdx.y;
+  const uint32_t t = blockIdx.x;
+  if (t >= img_qtile_off[img + 1] - img_qtile_off[img]) return;
+  const uint32_t gt = img_qtile_off[img] + t;
+  const int c = threadIdx.x;        // chunk id = s*64 + lane
+  const int s = c >> 6, lane = c & 63;
+  const int m = lane & 31, h = lane >> 5;
+  const uint32_t r = t * kTileRows + (uint32_t)m;
+  const bool real = r < img_n[img];
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (real) {
+    v = *reinterpret_cast<const uint4*>(rows + (img_row_off[img] + r) * kDim + (s * 2 + h) * 16);
+    v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
+  }
+  *reinterpret_cast<uint4*>(qtiles + (size_t)gt * kTileBytes + c * 16) = v;
+  if (c < kTileRows) qtnorm[(size_t)gt * kTileRows + m] = real ? rownorm[img_row_off[img] + r] : 0;
 }
 
 __global__ __launch_bounds__(256) void fill_i32_kernel(int* __restrict__ p, size_t n, int value) {
@@ -769,14 +805,15 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   const uint32_t tileI0 = wsh.x;
   const int ntI = (int)wsh.y;
   const uint32_t pair = wun.x, tileJ0 = wun.y, qt0 = wun.z;
-  const uint32_t ntJpad = wun.w;   // 0: an empty wave of a record that was closed early
+  const uint32_t nJ = wun.w;   // rows of the query image; 0: an empty wave of a record that was closed early
   const int nwin = (ntI + kWinTiles - 1) / kWinTiles;
 
   // byte offset of this lane's 16-byte chunk inside a tile, block 0, k-step 0 (see above)
   const int lane_chunk = ((lane >> 5) * 64 + ((lane >> 4) & 1) * 32 + (lane & 15)) * 16;
   v4i b[kNB16][2];
   {
-    const int8_t* qsrc = p.tiles + (size_t)(tileJ0 + qt0) * kTileBytes + lane_chunk;
+    // the query fragments come from the dense set (slot = original row): a unit covers 128 rows of J, not 64 of each norm parity
+    const int8_t* qsrc = p.qtiles + (size_t)(tileJ0 + qt0) * kTileBytes + lane_chunk;
 #pragma unroll
     for (int n = 0; n < kNB16; ++n)
 #pragma unroll
@@ -786,16 +823,13 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   const int8_t* gI = p.tiles + (size_t)tileI0 * kTileBytes;
   const int* gC = p.cinit + (size_t)tileI0 * kTileRows;
 
-  // validity and squared norm of the lane's eight query slots: fetched now, used after the last window (they used to be loaded there,
-  // one more trip to memory at the end of every workgroup)
-  uint32_t qperm[kNB16];
+  // squared norm of the lane's eight query slots: fetched now, used after the last window (they used to be loaded there, one more trip
+  // to memory at the end of every workgroup). A dense slot is valid iff it is below nJ: no table says so.
   int qn[kNB16];
 #pragma unroll
   for (int n = 0; n < kNB16; ++n) {
-    const bool inb = lane < 16 && qt0 + (uint32_t)(n >> 1) < ntJpad;
-    const size_t qs = (size_t)tileJ0 * kTileRows + (qt0 + (uint32_t)(n >> 1)) * kTileRows + (uint32_t)(n & 1) * 16 + (uint32_t)(lane & 15);
-    qperm[n] = inb ? p.perm[qs] : kNoMatch;
-    qn[n] = inb ? p.qnorm[qs] : 0;
+    const uint32_t q = (qt0 + (uint32_t)(n >> 1)) * kTileRows + (uint32_t)(n & 1) * 16 + (uint32_t)(lane & 15);
+    qn[n] = (lane < 16 && q < nJ) ? p.qtnorm[(size_t)tileJ0 * kTileRows + q] : 0;
   }
 
   int TP[kNB16][4];                         // P-class maxima of the run
@@ -813,7 +847,7 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   for (int n = 0; n < kNB16; ++n) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) asm volatile("" : "+v"(b[n][ks]));
-    asm volatile("" : "+v"(qperm[n]), "+v"(qn[n]));
+    asm volatile("" : "+v"(qn[n]));
   }
 
   for (int win = 0; win < nwin; ++win) {
@@ -923,12 +957,11 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
       code = mine ? code : oc;
       W1 = mine ? W1 : o1;
     }
-    const uint32_t q = (qt0 + (uint32_t)(n >> 1)) * kTileRows + (uint32_t)(n & 1) * 16 + (uint32_t)(lane & 15);   // query slot within J
-    if (lane < 16 && qt0 + (uint32_t)(n >> 1) < ntJpad) {
-      const bool valid = qperm[n] != kNoMatch;
+    const uint32_t q = (qt0 + (uint32_t)(n >> 1)) * kTileRows + (uint32_t)(n & 1) * 16 + (uint32_t)(lane & 15);   // query row of J = its dense slot
+    if (lane < 16 && q < nJ) {
       const int nq = qn[n];
       const int d0 = nq - W1, d1ub = nq - V2;
-      const bool cand = valid && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));
+      const bool cand = __int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub));
       const size_t o = (size_t)pair * p.qstride + q;
       p.best[o] = cand ? (uint32_t)code : kNoMatch;
       if (cand) p.cd[o] = make_int2(d0, d1ub);
@@ -1122,20 +1155,23 @@ template <bool kWaveUnits>
 __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  uint32_t pair, qt0, I, tileI0, tileJ0, ntJpad;
+  uint32_t pair, qt0, I, tileI0, tileJ0, qend;   // qend: query slots of J in the layout of the filter that ran
+  const uint8_t* rowsJ = nullptr;                // kWaveUnits: J's original rows (query slot = row)
   if constexpr (kWaveUnits) {
     const uint4* rec = p.work8 + (size_t)kRecQuads * blockIdx.x;
     const uint4 wun = rec[1 + __builtin_amdgcn_readfirstlane(wave)];   // wave-uniform: the unit stays in scalar registers
-    pair = wun.x; tileJ0 = wun.y; qt0 = wun.z; ntJpad = wun.w;   // an empty wave (ntJpad = 0) reads no slot below
+    pair = wun.x; tileJ0 = wun.y; qt0 = wun.z; qend = wun.w;   // an empty wave (nJ = 0) reads no slot below
     tileI0 = rec[0].x;
-    I = p.pairs[pair].x;
+    const uint2 ij = p.pairs[pair];
+    I = ij.x;
+    rowsJ = p.rows_u8 + p.img_row_off[ij.y] * kDim;
   } else {
     const uint2 wk = p.work[blockIdx.x];
     const uint2 ij = p.pairs[wk.x];
     pair = wk.x; qt0 = wk.y + (uint32_t)wave * kNQ;
     I = ij.x;
     tileI0 = p.img_tile_off[I]; tileJ0 = p.img_tile_off[ij.y];
-    ntJpad = p.img_tile_off[ij.y + 1] - tileJ0;
+    qend = (p.img_tile_off[ij.y + 1] - tileJ0) * kTileRows;
   }
   const uint32_t nEvenI = p.img_neven[I], nOddI = p.img_n[I] - nEvenI;
   const int l16 = lane & 15, sub = lane >> 4;
@@ -1143,7 +1179,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
   for (int part = 0; part < 2; ++part) {
     const uint32_t q0 = qt0 * kTileRows + (uint32_t)part * 64;
     const uint32_t q = q0 + lane;
-    const bool inb = q < ntJpad * kTileRows;
+    const bool inb = q < qend;
     const uint32_t code = inb ? p.best[(size_t)pair * p.qstride + q] : kNoMatch;
     unsigned long long todo = __ballot(code != kNoMatch);
     while (todo) {
@@ -1174,7 +1210,13 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
 #pragma unroll
       for (int c = 0; c < 8; ++c)
         va[c] = *reinterpret_cast<const int4*>(p.rows_slot + (slot0 + (active ? (size_t)c * kTileRows : 0)) * kDim + piece * 16);
-      const int4 vb = *reinterpret_cast<const int4*>(p.rows_slot + slotQ * kDim + piece * 16);
+      int4 vb;
+      if constexpr (kWaveUnits) {   // the dense query slot is the original row: its uint8 bytes, centred here
+        vb = *reinterpret_cast<const int4*>(rowsJ + (size_t)(active ? qs : 0) * kDim + piece * 16);
+        vb.x ^= (int)0x80808080u; vb.y ^= (int)0x80808080u; vb.z ^= (int)0x80808080u; vb.w ^= (int)0x80808080u;
+      } else {
+        vb = *reinterpret_cast<const int4*>(p.rows_slot + slotQ * kDim + piece * 16);
+      }
       const int2 f = p.cd[o];
       const int f_d0 = f.x, f_d1 = f.y;
       // |b'|^2 from the query piece itself (sum over the 8 lanes holding its pieces)
@@ -1265,7 +1307,7 @@ __global__ __launch_bounds__(256) void count_candidates_units_kernel(MatchParams
   uint32_t c = 0;
   for (int part = 0; part < 2; ++part) {
     const uint32_t q = wun.z * kTileRows + (uint32_t)part * 64 + (uint32_t)lane;
-    const bool cand = q < wun.w * kTileRows && p.best[(size_t)wun.x * p.qstride + q] != kNoMatch;
+    const bool cand = q < wun.w && p.best[(size_t)wun.x * p.qstride + q] != kNoMatch;
     c += (uint32_t)__popcll(__ballot(cand));
   }
   if (lane == 0 && c) atomicAdd(&s_sum, c);
@@ -1351,11 +1393,12 @@ __global__ __launch_bounds__(256) void compact_matches_kernel(const uint32_t* __
   if (offsets[pidx + 1] == off) return;
   const uint32_t J = pairs[pidx].y;
   const uint32_t nJ = img_n[J];
-  const uint32_t* pos = rowpos + img_row_off[J];   // original query row -> slot (best[] is slot-indexed)
+  // original query row -> slot (best[] is slot-indexed); no table: the dense query slots of l2_filter16_kernel, slot = row
+  const uint32_t* pos = rowpos ? rowpos + img_row_off[J] : nullptr;
   uint32_t run = off;
   for (uint32_t q0 = 0; q0 < nJ; q0 += 64) {
     const uint32_t q = q0 + lane;
-    const uint32_t v = (q < nJ) ? best[(size_t)pidx * qstride + pos[q]] : kNoMatch;
+    const uint32_t v = (q < nJ) ? best[(size_t)pidx * qstride + (pos ? pos[q] : q)] : kNoMatch;
     const bool ok = v != kNoMatch;
     const unsigned long long m = __ballot(ok);
     if (ok) {
@@ -1443,14 +1486,15 @@ struct mvgx_match_ctx {
   uint32_t max_tiles_pad = 0;
   uint32_t qstride = 0;
   std::vector<uint32_t> h_n, h_tile_off, h_ntiles;
+  std::vector<uint32_t> h_qtile_off;   // first dense query tile of each image: ceil(n / 32) tiles per image, no padding between images
   std::vector<uint64_t> h_row_off;
   DevBuf<uint8_t> d_rows;
   bool rows_owned = true;
   const uint8_t* d_rows_view = nullptr;
-  DevBuf<int8_t> d_tiles, d_rows_slot;
-  DevBuf<int> d_rconst, d_cinit, d_qnorm, d_rownorm;
+  DevBuf<int8_t> d_tiles, d_rows_slot, d_qtiles;
+  DevBuf<int> d_rconst, d_cinit, d_qnorm, d_rownorm, d_qtnorm;
   DevBuf<uint64_t> d_row_off;
-  DevBuf<uint32_t> d_tile_off, d_n, d_ntiles, d_perm, d_rowpos, d_neven, d_err;
+  DevBuf<uint32_t> d_tile_off, d_qtile_off, d_n, d_ntiles, d_perm, d_rowpos, d_neven, d_err;
   // batch scratch, two slots: while the filter kernel of batch b runs, batch b-1 is verified, scanned, compacted and
   // copied out on the other slot's stream
   struct Slot {
@@ -1500,15 +1544,18 @@ int prep_regions(mvgx_match_ctx* c) {
   c->h_tile_off.assign(n_images + 1, 0);
   c->h_row_off.assign(n_images + 1, 0);
   c->h_ntiles.assign(n_images + 1, 0);
+  c->h_qtile_off.assign(n_images + 1, 0);
   uint32_t max_n = 0;
   for (uint32_t k = 0; k < n_images; ++k) {
     c->h_row_off[k + 1] = c->h_row_off[k] + c->h_n[k];
+    c->h_qtile_off[k + 1] = c->h_qtile_off[k] + (c->h_n[k] + kTileRows - 1) / kTileRows;
     max_n = std::max(max_n, c->h_n[k]);
   }
   const uint64_t total_rows = c->h_row_off[n_images];
   int rc;
   if ((rc = c->d_row_off.ensure(n_images + 1))) return rc;
   if ((rc = c->d_tile_off.ensure(n_images + 1))) return rc;
+  if ((rc = c->d_qtile_off.ensure(n_images + 1))) return rc;
   if ((rc = c->d_n.ensure(n_images + 1))) return rc;
   if ((rc = c->d_ntiles.ensure(n_images + 1))) return rc;
   if ((rc = c->d_neven.ensure(n_images + 1))) return rc;
@@ -1550,6 +1597,14 @@ int prep_regions(mvgx_match_ctx* c) {
   if ((rc = c->d_cinit.ensure(alloc_slots))) return rc;
   if ((rc = c->d_qnorm.ensure(alloc_slots))) return rc;
   if ((rc = c->d_perm.ensure(alloc_slots))) return rc;
+  // the dense query set: a wave unit reads kNQ tiles from a multiple of kNQ below ceil(n / 32), i.e. up to kNQ - 1 tiles past its image -
+  // into the next image's tiles or the zeroed slack after the last one (the results of those columns are not stored)
+  const size_t total_qtiles = c->h_qtile_off[n_images];
+  if ((rc = c->d_qtiles.ensure((total_qtiles + kTailTiles) * kTileBytes))) return rc;
+  if ((rc = c->d_qtnorm.ensure((total_qtiles + kTailTiles) * kTileRows))) return rc;
+  MVGX_HIP(hipMemcpyAsync(c->d_qtile_off.p, c->h_qtile_off.data(), (n_images + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  MVGX_HIP(hipMemsetAsync(c->d_qtiles.p + total_qtiles * kTileBytes, 0, (size_t)kTailTiles * kTileBytes, c->stream));
+  MVGX_HIP(hipMemsetAsync(c->d_qtnorm.p + total_qtiles * kTileRows, 0, (size_t)kTailTiles * kTileRows * sizeof(int), c->stream));
   MVGX_HIP(hipMemcpyAsync(c->d_tile_off.p, c->h_tile_off.data(), (n_images + 1) * sizeof(uint32_t),
                           hipMemcpyHostToDevice, c->stream));
   MVGX_HIP(hipMemcpyAsync(c->d_ntiles.p, c->h_ntiles.data(), (n_images + 1) * sizeof(uint32_t),
@@ -1572,6 +1627,10 @@ int prep_regions(mvgx_match_ctx* c) {
     dim3 grid(max_pad, n_images);
     hipLaunchKernelGGL(build_tiles_kernel, grid, dim3(256), 0, c->stream, c->d_rows_view, c->d_row_off.p,
                        c->d_tile_off.p, c->d_perm.p, c->d_tiles.p, c->d_rows_slot.p);
+    MVGX_HIP(hipGetLastError());
+    dim3 qgrid((max_n + kTileRows - 1) / kTileRows, n_images);
+    hipLaunchKernelGGL(build_qtiles_kernel, qgrid, dim3(256), 0, c->stream, c->d_rows_view, c->d_row_off.p, c->d_qtile_off.p, c->d_n.p,
+                       c->d_rownorm.p, c->d_qtiles.p, c->d_qtnorm.p);
     MVGX_HIP(hipGetLastError());
   }
   MVGX_HIP(hipStreamSynchronize(c->stream));
@@ -1677,7 +1736,7 @@ int mvgx_match_destroy(mvgx_match_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   c->d_rows.release(); c->d_tiles.release(); c->d_rconst.release(); c->d_qnorm.release();
   c->d_rows_slot.release(); c->d_cinit.release(); c->d_rownorm.release(); c->d_ntiles.release(); c->d_perm.release(); c->d_rowpos.release();
-  c->d_neven.release(); c->d_err.release();
+  c->d_neven.release(); c->d_err.release(); c->d_qtiles.release(); c->d_qtnorm.release(); c->d_qtile_off.release();
   c->d_row_off.release(); c->d_tile_off.release(); c->d_n.release();
   for (auto& r : c->results) r.ij.release();
   for (auto& sl : c->slot) {
@@ -1861,6 +1920,8 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
   MVGX_HIP(hipEventRecord(c->ev_total0, c->slot[0].stream));
 
   // Stage 1 of a batch on its slot's stream: work list -> filter (+ verify) -> per-pair counts -> exclusive scan -> offsets to host
+  // l2_filter16_kernel and what follows it index best[] / cd[] by DENSE query slot (= original row of J); every other kernel by parity slot
+  const bool dense_queries = c->variant == 4 && c->filter_shape == 16 && c->stage == 3 && !c->debug_filter;
   auto issue = [&](mvgx_match_ctx::Slot& sl, mvgx_match_ctx::Slot* prev, uint64_t p0, uint32_t nb) -> int {
     int rc;
     hipStream_t stream = sl.stream;
@@ -1869,7 +1930,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     // worst-case work items: ceil(max tiles / 16) per pair
     const uint32_t max_blocks_per_pair = std::max<uint32_t>(1, (c->max_tiles_pad + kBlockQTiles - 1) / kBlockQTiles);
     if ((rc = sl.hp_work.ensure((size_t)nb * max_blocks_per_pair))) return rc;
-    const bool records = c->variant == 4 && c->filter_shape == 16 && c->stage == 3 && !c->debug_filter;
+    const bool records = dense_queries;
     const bool records_h = c->variant == 4 && c->filter_shape == 17 && c->stage == 3 && !c->debug_filter;
     // wave-packed records: the units of a pair are consecutive and share I, so they leave at most one record part-filled per pair
     if (records && (rc = sl.hp_work8.ensure((size_t)nb * max_blocks_per_pair * kRecQuads))) return rc;
@@ -1884,19 +1945,20 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
       // matcher_brute_force.hpp:108-113: NN(=2) > rows  -> no result; Matcher_Regions.cpp:65-69,85-90: empty regions skipped
       if (nI < 2 || nJ == 0) continue;
       const uint32_t ntJ = c->h_ntiles[J];   // occupied tiles of the query image
+      const uint32_t ntJq = c->h_qtile_off[J + 1] - c->h_qtile_off[J];   // ... in the dense query set: ceil(nJ / 32) <= ntJ
       // l2_filter16_kernel: units of kNQ query tiles, one per wave, packed four to a workgroup across the pairs that share I - a pair costs
-      // ceil(ntJ / 4) waves, not 4 * ceil(ntJ / 16). A record holds everything its workgroup needs to start (no walk work -> pairs -> three
+      // ceil(ntJq / 4) waves, not 4 * ceil(ntJ / 16), and no more of them than nJ rows need whatever their norm parities are. A record holds everything its workgroup needs to start (no walk work -> pairs -> three
       // per-image tables). It is closed when it is full, when I changes and at the end of the batch; its unused waves are empty units
-      // (ntJpad = 0: nothing stored) whose query pointer is aimed at I's own first tiles.
+      // (nJ = 0: nothing stored) whose query pointer is aimed at I's own first dense tiles.
       if (records)
-        for (uint32_t qt = 0; qt < ntJ; qt += kNQ) {
+        for (uint32_t qt = 0; qt < ntJq; qt += kNQ) {
           if (rec_used == kWaves || rec_I != I) {
             uint4* r = sl.hp_work8.p + (size_t)kRecQuads * n_rec++;
             r[0] = make_uint4(c->h_tile_off[I], c->h_ntiles[I], 0, 0);
-            for (int w = 0; w < kWaves; ++w) r[1 + w] = make_uint4(0, c->h_tile_off[I], 0, 0);
+            for (int w = 0; w < kWaves; ++w) r[1 + w] = make_uint4(0, c->h_qtile_off[I], 0, 0);
             rec_used = 0; rec_I = I;
           }
-          sl.hp_work8.p[(size_t)kRecQuads * (n_rec - 1) + 1 + rec_used++] = make_uint4(k, c->h_tile_off[J], qt, c->h_tile_off[J + 1] - c->h_tile_off[J]);
+          sl.hp_work8.p[(size_t)kRecQuads * (n_rec - 1) + 1 + rec_used++] = make_uint4(k, c->h_qtile_off[J], qt, nJ);
         }
       for (uint32_t qt = 0; qt < ntJ; qt += kBlockQTiles) {
         if (records_h)
@@ -1932,7 +1994,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
 
     MatchParams mp;
     mp.tiles = c->d_tiles.p; mp.rows_slot = c->d_rows_slot.p; mp.rconst = c->d_rconst.p; mp.cinit = c->d_cinit.p; mp.qnorm = c->d_qnorm.p;
-    mp.perm = c->d_perm.p; mp.rowpos = c->d_rowpos.p;
+    mp.perm = c->d_perm.p; mp.rowpos = c->d_rowpos.p; mp.qtiles = c->d_qtiles.p; mp.qtnorm = c->d_qtnorm.p;
     mp.rows_u8 = c->d_rows_view; mp.img_row_off = c->d_row_off.p;
     mp.img_tile_off = c->d_tile_off.p; mp.img_n = c->d_n.p; mp.img_ntiles = c->d_ntiles.p;
     mp.cd = sl.d_cd.p; mp.img_neven = c->d_neven.p; mp.errflag = c->d_err.p;
@@ -2023,7 +2085,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     if (total) {
       if ((rc = sl.d_ij.ensure(total))) return rc;
       hipLaunchKernelGGL(compact_matches_kernel, dim3((nb + 3) / 4), dim3(256), 0, sl.stream, sl.d_best.p,
-                         sl.d_offsets.p, sl.d_pairs.p, c->d_n.p, c->d_row_off.p, c->d_rowpos.p, nb, c->qstride,
+                         sl.d_offsets.p, sl.d_pairs.p, c->d_n.p, c->d_row_off.p, dense_queries ? nullptr : c->d_rowpos.p, nb, c->qstride,
                          sl.d_ij.p);
       MVGX_HIP(hipGetLastError());
       if (sink) {
