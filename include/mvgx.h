@@ -89,7 +89,15 @@ int mvgx_match_destroy(mvgx_match_ctx* ctx);
  * "pinned_stream" (default 1: the batch buffers of mvgx_match_run_stream are pinned; 0: plain memory, for one-shot use).
  * "stream_reserve" (uint32 words per buffer): page-locks the stream's host buffers ahead of the run - callable from another thread
  *   while mvgx_match_set_regions uploads (pinning ~100 MB takes tens of milliseconds the first batches would otherwise wait for).
- * "batch_pairs" (default 32 768): image pairs per device batch. */
+ * "batch_pairs" (default 32 768): image pairs per device batch.
+ * Kernel selection (cross-checks and A/B runs; every combination returns the same lists): "variant" 0 = one thread per query, 1 / 2 / 3 =
+ *   the exact top-2 kernel with the database window staged through registers / LDS-DMA builtin / LDS-DMA asm, 4 (default) = filter +
+ *   verify. Under 4 only: "stage" 1 / 2 / 3 (default 3) = the same three staging modes, "filter_shape" 16 (default; 16x16x64 MFMA), 17
+ *   (the same at three workgroups per CU) or 32 (32x32x32), "debug_filter" 0 (default), 8 or 16 = epilogue form of the 32x32x32 filter
+ *   (anything else: MVGX_ERR_ARG; the environment variable MVGX_MATCH_FILTER sets it at create, other values are ignored there).
+ *   The 16x16x64 kernels exist for stage 3 with debug_filter 0 only: shape 16 / 17 with stage 1 or 2, or with debug_filter 8 / 16, runs
+ *   the 32x32x32 filter; stage 1 or 2 ignores debug_filter. Variants 0..3 ignore all three.
+ * "verify_alone" (default 0; 1: a batch's filter kernel also waits for the verify kernel of the batch before). */
 int mvgx_match_set_option(mvgx_match_ctx* ctx, const char* key, int64_t value);
 
 /* Load the descriptor arrays of n_images images into HBM (replaces Regions_Provider::get +

@@ -30,13 +30,18 @@
 //            ceil(n / 32) tiles per image (the parity split inflates the count above to ceil(max(n_even, n_odd) / 16), which only the
 //            database role needs); qtnorm: |a'|^2 per slot of it. A query slot of that kernel's best[] / cd[] is the original row.
 //
-// Kernel l2_top2_ratio: one 256-thread workgroup = 4 waves = 512 queries of image J against all of image I.
-// Each wave keeps 4 query tiles (128 queries, 64 VGPRs) resident as MFMA B operands for its whole life and
-// streams I through a double-buffered 33 KiB LDS window. Per 32x32 distance tile the epilogue costs three
-// VALU ops per element:  T = (acc << 9) + R  (v_lshl_add_u32: -(d' << 8) - idx, d' = |a'|^2 - 2 a'.b'),
-// T2 = med3(T1, T2, T), T1 = max(T1, T)  — an exact running top-2 of packed (distance, index) keys.
-// Windows are folded into full-width (d0', argmin, d1') state; the two half-waves that share a query column
-// are merged at the end, |b'|^2 is added, the ratio test is evaluated in fp32 exactly like the reference.
+// What ships (option "variant" 4, the default): a FILTER launch and a VERIFY launch per batch of image pairs.
+//   l2_filter16_kernel   one workgroup = 4 waves, each wave 128 queries (4 dense query tiles, register-resident MFMA B operands) of any
+//                        pair whose database image I the workgroup streams through a double-buffered 33 KiB LDS window. On
+//                        v_mfma_i32_16x16x64_i8, one v_max3 per two distances: running maxima of two partitions of the rows bound the
+//                        second-nearest distance from below, so most queries are rejected exactly and the rest leave as candidates
+//                        (see l2_filter_kernel for the argument, l2_filter16_kernel for the shape).
+//   l2_verify_kernel     16 lanes per candidate recompute the 16 rows of its cell exactly and finish the reference's fp32 ratio test.
+// Cross-check and A/B forms, selected by the options "variant", "filter_shape", "stage" and "debug_filter" (the table above resolve_form
+// says which options reach which kernel): the naive kernel (one thread per query, no tiles), the exact top-2 kernel l2_top2_ratio_kernel
+// (32x32x32 MFMA, three VALU per distance, no verify stage) in three staging modes, the 32x32x32 filter l2_filter_kernel in three staging
+// modes and three epilogue forms, and l2_filter16h_kernel (the 16x16x64 filter at three workgroups per CU). The tests run them against
+// each other and against the reference.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -100,7 +105,7 @@ struct MatchParams {
                                    // the workgroup, then per wave (pair, tileJ0, first query tile, nJ) - a unit of kNQ DENSE query tiles (qtiles: tileJ0
                                    // is J's first one, nJ its rows) of any pair with this database image; nJ = 0: an empty wave (loads and barriers
                                    // as the others, stores nothing)
-  uint32_t n_work;
+  uint32_t n_work;                 // entries of the list the first kernel of the batch walks (= its grid; no kernel reads it)
   uint32_t* best;                  // [batch pairs][qstride], indexed by query SLOT (l2_filter16_kernel and after it: dense slot = row): original index in I or kNoMatch
   int2* cd;                        // filter -> verify: (d0, upper bound of d1) of a candidate query slot
   uint32_t* count;                 // [batch pairs]: accepted matches
@@ -353,7 +358,78 @@ __device__ __forceinline__ void stage_commit(char* buf, const StageRegs& sr, int
 }
 
 // ------------------------------------------------------------------------------------------------
-// l2_top2_ratio: the hot kernel
+// What the two 32x32x32 kernels (l2_top2_ratio_kernel, l2_filter_kernel) share: a workgroup = 4 waves = 512 query slots of image J
+// (16 parity tiles from the work item's first one) against all of image I, which streams through a double-buffered window in LDS.
+// ------------------------------------------------------------------------------------------------
+struct Item32 {
+  uint32_t pair, tileI0, tileJ0, ntJpad, qt0;   // qt0: the WAVE's first query tile within J
+  int ntI, nwin;
+};
+// decodes the workgroup's 16-tile work item and fetches the wave's register-resident query fragments (B operands): 4 tiles x 4 k-steps x
+// 16 B per lane
+__device__ __forceinline__ Item32 load_item32(const MatchParams& p, int wave, int lane, v4i (&b)[kNQ][4]) {
+  const uint32_t w = xcd_remap(blockIdx.x, gridDim.x);
+  const uint2 wk = p.work[w];
+  const uint2 ij = p.pairs[wk.x];
+  const uint32_t I = ij.x, J = ij.y;
+  Item32 it;
+  it.pair = wk.x;
+  it.tileI0 = p.img_tile_off[I]; it.tileJ0 = p.img_tile_off[J];
+  it.ntJpad = p.img_tile_off[J + 1] - it.tileJ0;
+  it.ntI = (int)p.img_ntiles[I];
+  it.nwin = (it.ntI + kWinTiles - 1) / kWinTiles;
+  it.qt0 = wk.y + (uint32_t)wave * kNQ;
+  const int8_t* qsrc = p.tiles + (size_t)(it.tileJ0 + it.qt0) * kTileBytes + lane * 16;
+#pragma unroll
+  for (int n = 0; n < kNQ; ++n)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[n][s] = *reinterpret_cast<const v4i*>(qsrc + n * kTileBytes + s * 1024);
+  return it;
+}
+// Pins the query fragments: the compiler must retire their loads BEFORE the window loop, so no s_waitcnt vmcnt lands inside the tile loop
+// where it would also drain the next window's prefetch.
+__device__ __forceinline__ void pin_fragments32(v4i (&b)[kNQ][4]) {
+#pragma unroll
+  for (int n = 0; n < kNQ; ++n)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(b[n][s]));
+}
+// window 0 into the first buffer, before the window loop (gC: the per-slot constants of the kernel, rconst or cinit)
+template <int kMode>
+__device__ __forceinline__ void stage_first(char* smem, StageRegs& sr, const int8_t* __restrict__ gI, const int* __restrict__ gC, int wave, int lane) {
+  if constexpr (kMode == kStageGlds) {
+    stage_window_glds(smem, gI, gC, wave, lane);
+  } else if constexpr (kMode == kStageGldsAsm) {
+    stage_window_glds_asm(smem, gI, gC, wave, lane);
+  } else {
+    stage_issue(sr, gI, gC, wave, lane);
+    stage_commit(smem, sr, wave, lane);
+  }
+}
+// At the head of window `win`, behind its barrier: prefetch the next window. Register mode: the loads only (the kernel commits them to
+// nbuf after the window's MFMA work); the last iteration re-fetches its own window into the idle buffer (no conditional around the loads
+// keeps the staging registers out of scratch). LDS-DMA modes: nothing may be in flight towards LDS when the workgroup retires, so the last
+// iteration issues nothing.
+template <int kMode>
+__device__ __forceinline__ void stage_next(char* nbuf, StageRegs& sr, const int8_t* __restrict__ gI, const int* __restrict__ gC, int win, int nwin,
+                                           int wave, int lane) {
+  if constexpr (kMode == kStageRegs) {
+    const int wn = (win + 1 < nwin) ? win + 1 : win;
+    stage_issue(sr, gI + (size_t)wn * kWinTiles * kTileBytes, gC + wn * kWinRows, wave, lane);
+  } else if (win + 1 < nwin) {
+    const int8_t* gt = gI + (size_t)(win + 1) * kWinTiles * kTileBytes;
+    const int* gc = gC + (win + 1) * kWinRows;
+    if constexpr (kMode == kStageGlds) stage_window_glds(nbuf, gt, gc, wave, lane);
+    else stage_window_glds_asm(nbuf, gt, gc, wave, lane);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// l2_top2_ratio (variants 1-3): the exact kernel, no verify stage. Each wave keeps 4 query tiles (128 queries, 64 VGPRs) resident as MFMA B
+// operands for its whole life. Per 32x32 distance tile the epilogue costs three VALU ops per element:
+// T = (acc << 9) + R  (v_lshl_add_u32: -(d' << 8) - idx, d' = |a'|^2 - 2 a'.b'), T2 = med3(T1, T2, T), T1 = max(T1, T)  — an exact running
+// top-2 of packed (distance, index) keys. Windows are folded into full-width (d0', argmin, d1') state; the two half-waves that share a
+// query column are merged at the end, |b'|^2 is added, the ratio test is evaluated in fp32 exactly like the reference.
 // ------------------------------------------------------------------------------------------------
 template <int kMode>
 __global__ __launch_bounds__(256, 2) void l2_top2_ratio_kernel(MatchParams p) {
@@ -363,25 +439,10 @@ __global__ __launch_bounds__(256, 2) void l2_top2_ratio_kernel(MatchParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = lane >> 5;
 
-  const uint32_t w = xcd_remap(blockIdx.x, gridDim.x);
-  const uint2 wk = p.work[w];
-  const uint2 ij = p.pairs[wk.x];
-  const uint32_t I = ij.x, J = ij.y;
-  const uint32_t tileI0 = p.img_tile_off[I], tileJ0 = p.img_tile_off[J];
-  const uint32_t ntJpad = p.img_tile_off[J + 1] - tileJ0;
-  const int ntI = (int)p.img_ntiles[I];
-  const int nwin = (ntI + kWinTiles - 1) / kWinTiles;
-  const uint32_t qt0 = wk.y + (uint32_t)wave * kNQ;
-
-  // register-resident query fragments (B operands): 4 tiles x 4 k-steps x 16 B per lane
   v4i b[kNQ][4];
-  {
-    const int8_t* qsrc = p.tiles + (size_t)(tileJ0 + qt0) * kTileBytes + lane * 16;
-#pragma unroll
-    for (int n = 0; n < kNQ; ++n)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) b[n][s] = *reinterpret_cast<const v4i*>(qsrc + n * kTileBytes + s * 1024);
-  }
+  const Item32 it = load_item32(p, wave, lane, b);
+  const uint32_t tileI0 = it.tileI0, tileJ0 = it.tileJ0, ntJpad = it.ntJpad, qt0 = it.qt0;
+  const int ntI = it.ntI, nwin = it.nwin;
 
   const int8_t* gI = p.tiles + (size_t)tileI0 * kTileBytes;
   const int* gR = p.rconst + (size_t)tileI0 * kTileRows;
@@ -391,21 +452,8 @@ __global__ __launch_bounds__(256, 2) void l2_top2_ratio_kernel(MatchParams p) {
   for (int n = 0; n < kNQ; ++n) { G1[n] = INT_MAX; G2[n] = INT_MAX; Gi[n] = 0; }
 
   StageRegs sr;
-  if constexpr (kMode == kStageGlds) {
-    stage_window_glds(smem, gI, gR, wave, lane);
-  } else if constexpr (kMode == kStageGldsAsm) {
-    stage_window_glds_asm(smem, gI, gR, wave, lane);
-  } else {
-    stage_issue(sr, gI, gR, wave, lane);
-    stage_commit(smem, sr, wave, lane);
-  }
-
-  // Pin the query fragments here: the compiler must retire their loads BEFORE the window loop, so no
-  // s_waitcnt vmcnt lands inside the tile loop where it would also drain the next window's prefetch.
-#pragma unroll
-  for (int n = 0; n < kNQ; ++n)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(b[n][s]));
+  stage_first<kMode>(smem, sr, gI, gR, wave, lane);
+  pin_fragments32(b);
 
   for (int win = 0; win < nwin; ++win) {
     // stage `win` has landed for every wave; everybody is done reading the other buffer
@@ -413,18 +461,7 @@ __global__ __launch_bounds__(256, 2) void l2_top2_ratio_kernel(MatchParams p) {
     __syncthreads();
     char* buf = smem + (win & 1) * kStageBytes;
     char* nbuf = smem + ((win + 1) & 1) * kStageBytes;
-    // Prefetch the next window. Register mode: the last iteration re-fetches its own window into the idle
-    // buffer (no conditional around the loads keeps the staging registers out of scratch). LDS-DMA modes:
-    // nothing may be in flight towards LDS when the workgroup retires, so the last iteration issues nothing.
-    if constexpr (kMode == kStageRegs) {
-      const int wn = (win + 1 < nwin) ? win + 1 : win;
-      stage_issue(sr, gI + (size_t)wn * kWinTiles * kTileBytes, gR + wn * kWinRows, wave, lane);
-    } else if (win + 1 < nwin) {
-      const int8_t* gt = gI + (size_t)(win + 1) * kWinTiles * kTileBytes;
-      const int* gr = gR + (win + 1) * kWinRows;
-      if constexpr (kMode == kStageGlds) stage_window_glds(nbuf, gt, gr, wave, lane);
-      else stage_window_glds_asm(nbuf, gt, gr, wave, lane);
-    }
+    stage_next<kMode>(nbuf, sr, gI, gR, win, nwin, wave, lane);
 
     int T1[kNQ], T2[kNQ];
 #pragma unroll
@@ -494,10 +531,10 @@ __global__ __launch_bounds__(256, 2) void l2_top2_ratio_kernel(MatchParams p) {
       const int nq = p.qnorm[(size_t)tileJ0 * kTileRows + q];
       const int d0 = G1[n] + nq, d1 = G2[n] + nq;
       ok = valid && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1)));
-      p.best[(size_t)wk.x * p.qstride + q] = ok ? p.perm[(size_t)tileI0 * kTileRows + (uint32_t)Gi[n]] : kNoMatch;
+      p.best[(size_t)it.pair * p.qstride + q] = ok ? p.perm[(size_t)tileI0 * kTileRows + (uint32_t)Gi[n]] : kNoMatch;
     }
     const unsigned long long m = __ballot(ok);
-    if (lane == 0 && m) atomicAdd(&p.count[wk.x], (uint32_t)__popcll(m));
+    if (lane == 0 && m) atomicAdd(&p.count[it.pair], (uint32_t)__popcll(m));
   }
 }
 
@@ -520,10 +557,34 @@ __global__ __launch_bounds__(256, 2) void l2_top2_ratio_kernel(MatchParams p) {
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
 
-// kDbg bits 0..2: timing experiments only (results are wrong): bit 0 drops the epilogue, bit 1 the per-tile LDS fragment loads,
-// bit 2 the per-window wait + barrier + staging - what each costs is the difference to kDbg = 0 (tools/filter_breakdown.py).
-// kDbg = 8 / 16: earlier forms of the epilogue with valid results (see kFold below).
-template <int kMode, int kDbg = 0>
+// Folds the maximum v of window `win` into the running (best, second best, best window) of one query block.
+__device__ __forceinline__ void fold_window_max(int v, int& Q1, int& Q2, int& Qg, int win) {
+  const bool better = v > Q1;
+  Q2 = better ? Q1 : max(Q2, v);
+  Qg = better ? win : Qg;
+  Q1 = better ? v : Q1;
+}
+// End of a window for one query block: the window's P-class maxima TW join the run-long ones TP and are reset; their maximum is the window
+// maximum (20 VALU per block of 8 classes and window instead of a second v_max3 per chain).
+template <int kClasses>
+__device__ __forceinline__ void fold_window(int (&TW)[kClasses], int (&TP)[kClasses], int& Q1, int& Q2, int& Qg, int win) {
+  int v = TW[0];
+#pragma unroll
+  for (int c = 1; c < kClasses; ++c) v = max(v, TW[c]);
+#pragma unroll
+  for (int c = 0; c < kClasses; ++c) { TP[c] = max(TP[c], TW[c]); TW[c] = kNegInit; }
+  fold_window_max(v, Q1, Q2, Qg, win);
+}
+
+// The epilogue forms of l2_filter_kernel, all with valid results (option "debug_filter" 0 / 16 / 8). The P-class maxima are kept per window
+// (TW) and folded into the run-long maxima TP and into the window maximum once per window: 8 v_max3 per chain instead of 16 (13.08 ->
+// 12.77 ms per launch in one run, profiles/round2_filter_epilogue_forms_call28.json); TW takes 32 registers (248 of 256 in use).
+// kEpiFoldOneCv single-buffers the accumulator initialiser under that (re-fetched behind its last use in a tile: 235 registers,
+// 12.85 ms); kEpiPerChain is the earlier epilogue that updates both partitions per chain. The two are kept for comparison and as
+// cross-checks of each other in the tests.
+enum FilterEpilogue { kEpiFold = 0, kEpiFoldOneCv = 1, kEpiPerChain = 2 };
+
+template <int kMode, int kEpi = kEpiFold>
 __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x kStageBytes
 
@@ -531,36 +592,16 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = lane >> 5;
 
-  const uint32_t w = xcd_remap(blockIdx.x, gridDim.x);
-  const uint2 wk = p.work[w];
-  const uint2 ij = p.pairs[wk.x];
-  const uint32_t I = ij.x, J = ij.y;
-  const uint32_t tileI0 = p.img_tile_off[I], tileJ0 = p.img_tile_off[J];
-  const uint32_t ntJpad = p.img_tile_off[J + 1] - tileJ0;
-  const int ntI = (int)p.img_ntiles[I];
-  const int nwin = (ntI + kWinTiles - 1) / kWinTiles;
-  const uint32_t qt0 = wk.y + (uint32_t)wave * kNQ;
-
   v4i b[kNQ][4];
-  {
-    const int8_t* qsrc = p.tiles + (size_t)(tileJ0 + qt0) * kTileBytes + lane * 16;
-#pragma unroll
-    for (int n = 0; n < kNQ; ++n)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) b[n][s] = *reinterpret_cast<const v4i*>(qsrc + n * kTileBytes + s * 1024);
-  }
+  const Item32 it = load_item32(p, wave, lane, b);
+  const uint32_t tileI0 = it.tileI0, tileJ0 = it.tileJ0, ntJpad = it.ntJpad, qt0 = it.qt0;
+  const int ntI = it.ntI, nwin = it.nwin;
 
   const int8_t* gI = p.tiles + (size_t)tileI0 * kTileBytes;
   const int* gC = p.cinit + (size_t)tileI0 * kTileRows;
 
-  // The P-class maxima are kept per window (TW) and folded into the run-long maxima TP and into the window maximum once per
-  // window: 8 v_max3 per chain instead of 16, +20 VALU per query tile and window (13.08 -> 12.77 ms per launch in one run,
-  // profiles/round2_filter_epilogue_forms_call28.json). TW takes 32 registers (248 of 256 in use).
-  // kDbg bit 3 (results VALID) selects the earlier epilogue (both partitions updated per chain); bit 4 single-buffers the
-  // accumulator initialiser under the new one (re-fetched behind its last use in a tile: 235 registers, 12.85 ms). Both are
-  // kept for comparison and as cross-checks of each other in the tests.
-  constexpr bool kFold = (kDbg & 8) == 0;
-  constexpr bool kOneCv = kFold && (kDbg & 16) != 0;
+  constexpr bool kFold = kEpi != kEpiPerChain;
+  constexpr bool kOneCv = kEpi == kEpiFoldOneCv;
   int TP[kNQ][8];                      // P-class maxima
   int TW[kNQ][8];                      // kFold: P-class maxima of the current window
   int Q1[kNQ], Q2[kNQ], Qg[kNQ];       // best / second-best window maximum, best window
@@ -572,36 +613,17 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
   }
 
   StageRegs sr;
-  if constexpr (kMode == kStageGlds) {
-    stage_window_glds(smem, gI, gC, wave, lane);
-  } else if constexpr (kMode == kStageGldsAsm) {
-    stage_window_glds_asm(smem, gI, gC, wave, lane);
-  } else {
-    stage_issue(sr, gI, gC, wave, lane);
-    stage_commit(smem, sr, wave, lane);
-  }
-#pragma unroll
-  for (int n = 0; n < kNQ; ++n)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(b[n][s]));
+  stage_first<kMode>(smem, sr, gI, gC, wave, lane);
+  pin_fragments32(b);
 
   for (int win = 0; win < nwin; ++win) {
-    if constexpr (!(kDbg & 4) && kMode == kStageGldsAsm) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (!(kDbg & 4)) __syncthreads();
+    if constexpr (kMode == kStageGldsAsm) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     char* buf = smem + (win & 1) * kStageBytes;
     char* nbuf = smem + ((win + 1) & 1) * kStageBytes;
-    if constexpr (kDbg & 4) {
-    } else if constexpr (kMode == kStageRegs) {
-      const int wn = (win + 1 < nwin) ? win + 1 : win;
-      stage_issue(sr, gI + (size_t)wn * kWinTiles * kTileBytes, gC + wn * kWinRows, wave, lane);
-    } else if (win + 1 < nwin) {
-      const int8_t* gt = gI + (size_t)(win + 1) * kWinTiles * kTileBytes;
-      const int* gc = gC + (win + 1) * kWinRows;
-      if constexpr (kMode == kStageGlds) stage_window_glds(nbuf, gt, gc, wave, lane);
-      else stage_window_glds_asm(nbuf, gt, gc, wave, lane);
-    }
+    stage_next<kMode>(nbuf, sr, gI, gC, win, nwin, wave, lane);
 
-    int TQ[kNQ];
+    int TQ[kNQ];                       // !kFold: the window maximum
 #pragma unroll
     for (int n = 0; n < kNQ; ++n) TQ[n] = kNegInit;
 
@@ -624,13 +646,12 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) accB[r] = kNegInit;
 
+    // (macros, not functions: the schedule barriers of MVGX_INTERLEAVE count the instructions of the chain and the epilogue around them)
 #define MVGX_EPILOGUE(ACC, N)                                          \
-  if constexpr (kDbg & 1) { asm volatile("" : "+v"(ACC)); TQ[N] = max(TQ[N], ACC[0]); } else \
   if constexpr (kFold) {                                               \
     _Pragma("unroll") for (int s = 0; s < 8; ++s)                      \
       TW[N][s] = max(max(TW[N][s], ACC[2 * s]), ACC[2 * s + 1]);       \
-  } else                                                               \
-  {                                                                    \
+  } else {                                                             \
     int tq = TQ[N];                                                    \
     _Pragma("unroll") for (int s = 0; s < 8; ++s) {                    \
       TP[N][s] = max(max(TP[N][s], ACC[2 * s]), ACC[2 * s + 1]);       \
@@ -648,24 +669,21 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
     __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);                                         \
     __builtin_amdgcn_sched_group_barrier(0x2, kFold ? 2 : 4, 0);                             \
   }
-
+#define MVGX_LOAD_CINIT(CV, TN)                                                                    \
+  _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                  \
+    const int4 c4 = *reinterpret_cast<const int4*>(wc + (TN) * (kTileRows * 4) + g * 32);          \
+    CV[g * 4 + 0] = c4.x; CV[g * 4 + 1] = c4.y; CV[g * 4 + 2] = c4.z; CV[g * 4 + 3] = c4.w;       \
+  }
 #define MVGX_TILE(A, CV, AN, CN, TN)                                                              \
   {                                                                                                \
     const int tn_ = (TN);                                                                          \
     MVGX_CHAIN(accA, 0, A, CV)                                                                     \
-    if constexpr (kDbg & 2) { _Pragma("unroll") for (int s = 0; s < 4; ++s) AN[s] = A[s]; CN = CV; } else { \
     _Pragma("unroll") for (int s = 0; s < 4; ++s)                                                  \
-        AN[s] = *reinterpret_cast<const v4i*>(wb + tn_ * kTileBytes + s * 1024);                   \
-    }                                                                                              \
+      AN[s] = *reinterpret_cast<const v4i*>(wb + tn_ * kTileBytes + s * 1024);                     \
     MVGX_EPILOGUE(accB, 3)                                                                         \
     MVGX_INTERLEAVE()                                                                              \
     MVGX_CHAIN(accB, 1, A, CV)                                                                     \
-    if constexpr (!(kDbg & 2) && !kOneCv) {                                                        \
-    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                \
-      const int4 c4 = *reinterpret_cast<const int4*>(wc + tn_ * (kTileRows * 4) + g * 32);        \
-      CN[g * 4 + 0] = c4.x; CN[g * 4 + 1] = c4.y; CN[g * 4 + 2] = c4.z; CN[g * 4 + 3] = c4.w;     \
-    }                                                                                              \
-    }                                                                                              \
+    if constexpr (!kOneCv) { MVGX_LOAD_CINIT(CN, tn_) }                                            \
     MVGX_EPILOGUE(accA, 0)                                                                         \
     MVGX_INTERLEAVE()                                                                              \
     MVGX_CHAIN(accA, 2, A, CV)                                                                     \
@@ -673,11 +691,7 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
     MVGX_INTERLEAVE()                                                                              \
     if constexpr (kOneCv) {  /* CV is dead after the first MFMA of the tile's last chain: fetch the next tile's */ \
       accB = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[0], b[3][0], CV, 0, 0, 0);                   \
-      if constexpr (!(kDbg & 2))                                                                   \
-      _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                              \
-        const int4 c4 = *reinterpret_cast<const int4*>(wc + tn_ * (kTileRows * 4) + g * 32);      \
-        CV[g * 4 + 0] = c4.x; CV[g * 4 + 1] = c4.y; CV[g * 4 + 2] = c4.z; CV[g * 4 + 3] = c4.w;   \
-      }                                                                                            \
+      MVGX_LOAD_CINIT(CV, tn_)                                                                     \
       accB = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[1], b[3][1], accB, 0, 0, 0);                 \
       accB = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[2], b[3][2], accB, 0, 0, 0);                 \
       accB = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[3], b[3][3], accB, 0, 0, 0);                 \
@@ -708,28 +722,14 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
     MVGX_EPILOGUE(accB, 3)   // drain
 #undef MVGX_EPILOGUE
 #undef MVGX_CHAIN
+#undef MVGX_LOAD_CINIT
 #undef MVGX_TILE
 #undef MVGX_INTERLEAVE
     if constexpr (kMode == kStageRegs) stage_commit(nbuf, sr, wave, lane);
-    if constexpr (kFold) {   // the window's class maxima: their maximum is the window maximum, then they join the run-long maxima
-#pragma unroll
-      for (int n = 0; n < kNQ; ++n) {
-        int tq = max(max(TW[n][0], TW[n][1]), TW[n][2]);
-        tq = max(max(tq, TW[n][3]), TW[n][4]);
-        tq = max(max(tq, TW[n][5]), TW[n][6]);
-        TQ[n] = max(tq, TW[n][7]);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) { TP[n][s] = max(TP[n][s], TW[n][s]); TW[n][s] = kNegInit; }
-      }
-    }
-    // fold the window maximum into the running (best, best window, second best) over windows
 #pragma unroll
     for (int n = 0; n < kNQ; ++n) {
-      const int v = TQ[n];
-      const bool better = v > Q1[n];
-      Q2[n] = better ? Q1[n] : max(Q2[n], v);
-      Qg[n] = better ? win : Qg[n];
-      Q1[n] = better ? v : Q1[n];
+      if constexpr (kFold) fold_window<8>(TW[n], TP[n], Q1[n], Q2[n], Qg[n], win);
+      else fold_window_max(TQ[n], Q1[n], Q2[n], Qg[n], win);
     }
   }
 
@@ -760,7 +760,7 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
       const int nq = p.qnorm[(size_t)tileJ0 * kTileRows + q];
       const int d0 = nq - W1, d1ub = nq - V2;
       const bool cand = valid && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));
-      const size_t o = (size_t)wk.x * p.qstride + q;
+      const size_t o = (size_t)it.pair * p.qstride + q;
       p.best[o] = cand ? ((uint32_t)s1 | ((uint32_t)hw << 3) | ((uint32_t)g1 << 4)) : kNoMatch;
       if (cand) p.cd[o] = make_int2(d0, d1ub);
     }
@@ -789,6 +789,68 @@ __global__ __launch_bounds__(256, 2) void l2_filter_kernel(MatchParams p) {
 // Exactness argument: the one of l2_filter_kernel with "half" read as "lane group" (other groups' best rows bound d1 from their side).
 // ------------------------------------------------------------------------------------------------
 constexpr int kNB16 = 2 * kNQ;   // query blocks of 16 per wave
+
+// The MFMA stream of the two 16x16x64 kernels, as macros because the schedule barriers of MVGX_MIX16 count the instructions around them.
+// They read the kernel's query fragments b[][2] and window maxima TW[][4]; N0 is the first of the four query blocks a group serves.
+// One 16-row block against four query blocks: 8 MFMAs; the eight v_max3 of the group before run in their shadow
+#define MVGX_GROUP16(ACC, N0, A, CV)                                                                       \
+  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                          \
+    ACC[i_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], b[(N0) + i_][0], CV, 0, 0, 0);                    \
+  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                          \
+    ACC[i_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1], b[(N0) + i_][1], ACC[i_], 0, 0, 0);
+#define MVGX_EPI16(ACC, N0, BLK)                                                                            \
+  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
+    TW[(N0) + i_][2 * (BLK)] = max(max(TW[(N0) + i_][2 * (BLK)], ACC[i_][0]), ACC[i_][1]);                  \
+    TW[(N0) + i_][2 * (BLK) + 1] = max(max(TW[(N0) + i_][2 * (BLK) + 1], ACC[i_][2]), ACC[i_][3]);          \
+  }
+// the schedule of one group: eight (MFMA, v_max3) pairs with the LDS reads issued beside it (NDS of them) right behind the first pairs -
+// left to itself the compiler sinks a fragment load to just in front of its first use and waits there
+#define MVGX_MIX16(NDS)                                                                                     \
+  _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                        \
+    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);                                                        \
+    __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);                                                        \
+    if (i_ < (NDS)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                      \
+  }
+
+// Finishes query block N of a 16x16x64 kernel after the last window: the lane's class top-2, the code word of its best row's cell, the merge
+// of the four lane groups that share the query column, the fp32 pre-test and the store of best[] / cd[]. Lane l < 16 owns slot
+// q = 32 (qt0 + N / 2) + 16 (N % 2) + l in the kernel's own numbering of best[]; the kernel says whether J has that slot (INB) and whether it
+// holds a row (VALID). A macro although no schedule barrier needs one: as a __forceinline__ function - whole, or only its top-2 loop,
+// its merge loop or its store - it changes the order and number of l2_filter16_kernel's instructions (1 402 -> 1 396..1 408).
+#define MVGX_FINISH16(N, INB, VALID)                                                                                                      \
+  {                                                                                                                                       \
+    int p1 = kNegInit, p2 = kNegInit, pc = 0;   /* best / second-best P-class of this lane */                                             \
+    _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                                                       \
+      const int v = TP[N][c];                                                                                                             \
+      const bool better = v > p1;                                                                                                         \
+      p2 = better ? p1 : max(p2, v);                                                                                                      \
+      pc = better ? c : pc;                                                                                                               \
+      p1 = better ? v : p1;                                                                                                               \
+    }                                                                                                                                     \
+    /* exact w = |b'|^2 - d of the lane's best row; V2: its runner-up outside the best row's (class, window) cell */                      \
+    int W1 = 2 * p1 - par, V2 = max(2 * p2 - par, 2 * Q2[N] - par);                                                                       \
+    int code = (4 * (pc >> 1) + 2 * (g4 >> 1) + (pc & 1)) | (par << 3) | (Qg[N] << 4);   /* (s1, half, window) of the 32x32 kernel's cells */ \
+    /* merge the four lane groups that share the query column: the winner's runner-up also has to beat the other groups' best rows. */    \
+    /* (groups g and g ^ 2 have the same parity, so their best values can be equal: then V2 >= W1, d1_ub <= d0 and the query is */        \
+    /* rejected, as the reference rejects a tie for the first place) */                                                                   \
+    _Pragma("unroll") for (int x = 16; x <= 32; x <<= 1) {                                                                                \
+      const int o1 = __shfl_xor(W1, x), o2 = __shfl_xor(V2, x), oc = __shfl_xor(code, x);                                                 \
+      const bool mine = W1 > o1;                                                                                                          \
+      V2 = mine ? max(V2, o1) : max(o2, W1);                                                                                              \
+      code = mine ? code : oc;                                                                                                            \
+      W1 = mine ? W1 : o1;                                                                                                                \
+    }                                                                                                                                     \
+    const uint32_t q = (qt0 + (uint32_t)((N) >> 1)) * kTileRows + (uint32_t)((N) & 1) * 16 + (uint32_t)(lane & 15);                       \
+    if (lane < 16 && (INB)) {                                                                                                             \
+      const int nq = qn[N];                                                                                                               \
+      const int d0 = nq - W1, d1ub = nq - V2;                                                                                             \
+      const bool cand = (VALID) && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));                                    \
+      const size_t o = (size_t)pair * p.qstride + q;                                                                                      \
+      p.best[o] = cand ? (uint32_t)code : kNoMatch;                                                                                       \
+      if (cand) p.cd[o] = make_int2(d0, d1ub);                                                                                            \
+    }                                                                                                                                     \
+  }
+
 __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x kStageBytes
 
@@ -867,24 +929,6 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
     for (int i = 0; i < 4; ++i) accB[i] = v4i{kNegInit, kNegInit, kNegInit, kNegInit};
 
     // one 16-row block = 16 MFMAs in two groups of four query blocks; the eight v_max3 of the previous group run in the shadow of a group
-#define MVGX_GROUP16(ACC, N0, A, CV)                                                                       \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                          \
-    ACC[i_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], b[(N0) + i_][0], CV, 0, 0, 0);                    \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                          \
-    ACC[i_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1], b[(N0) + i_][1], ACC[i_], 0, 0, 0);
-#define MVGX_EPI16(ACC, N0, BLK)                                                                            \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
-    TW[(N0) + i_][2 * (BLK)] = max(max(TW[(N0) + i_][2 * (BLK)], ACC[i_][0]), ACC[i_][1]);                  \
-    TW[(N0) + i_][2 * (BLK) + 1] = max(max(TW[(N0) + i_][2 * (BLK) + 1], ACC[i_][2]), ACC[i_][3]);          \
-  }
-// the schedule of half a block: eight (MFMA, v_max3) pairs with the half's LDS reads (NDS of them) right behind the first pairs - left to
-// itself the compiler sinks a fragment load to just in front of its first use and waits there
-#define MVGX_MIX16(NDS)                                                                                     \
-  _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);                                                        \
-    if (i_ < (NDS)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                      \
-  }
 #define MVGX_BLOCK16(A, CV, AN, CN, BLK, NEXT_OFF, NEXT_COFF)                                               \
   {                                                                                                         \
     MVGX_GROUP16(accA, 0, A, CV)                                                                            \
@@ -914,59 +958,13 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
     }
     MVGX_EPI16(accB, 4, 1)   // drain: the second group of the window's last block
     __builtin_amdgcn_s_setprio(0);
-#undef MVGX_GROUP16
-#undef MVGX_EPI16
-#undef MVGX_MIX16
 #undef MVGX_BLOCK16
-    // the window's class maxima: their maximum is the window maximum, then they join the run-long maxima
 #pragma unroll
-    for (int n = 0; n < kNB16; ++n) {
-      const int v = max(max(max(TW[n][0], TW[n][1]), TW[n][2]), TW[n][3]);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { TP[n][c] = max(TP[n][c], TW[n][c]); TW[n][c] = kNegInit; }
-      const bool better = v > Q1[n];
-      Q2[n] = better ? Q1[n] : max(Q2[n], v);
-      Qg[n] = better ? win : Qg[n];
-      Q1[n] = better ? v : Q1[n];
-    }
+    for (int n = 0; n < kNB16; ++n) fold_window<4>(TW[n], TP[n], Q1[n], Q2[n], Qg[n], win);
   }
 
 #pragma unroll
-  for (int n = 0; n < kNB16; ++n) {
-    // best / second-best P-class of this lane
-    int p1 = kNegInit, p2 = kNegInit, pc = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int v = TP[n][c];
-      const bool better = v > p1;
-      p2 = better ? p1 : max(p2, v);
-      pc = better ? c : pc;
-      p1 = better ? v : p1;
-    }
-    // exact w = |b'|^2 - d of the lane's best row; v2: its runner-up outside the best row's (class, window) cell
-    int W1 = 2 * p1 - par, V2 = max(2 * p2 - par, 2 * Q2[n] - par);
-    int code = (4 * (pc >> 1) + 2 * (g4 >> 1) + (pc & 1)) | (par << 3) | (Qg[n] << 4);   // (s1, half, window) of the 32x32 kernel's cells
-    // merge the four lane groups that share the query column: the winner's runner-up also has to beat the other groups' best rows.
-    // (groups g and g ^ 2 have the same parity, so their best values can be equal: then V2 >= W1, d1_ub <= d0 and the query is
-    // rejected, as the reference rejects a tie for the first place)
-#pragma unroll
-    for (int x = 16; x <= 32; x <<= 1) {
-      const int o1 = __shfl_xor(W1, x), o2 = __shfl_xor(V2, x), oc = __shfl_xor(code, x);
-      const bool mine = W1 > o1;
-      V2 = mine ? max(V2, o1) : max(o2, W1);
-      code = mine ? code : oc;
-      W1 = mine ? W1 : o1;
-    }
-    const uint32_t q = (qt0 + (uint32_t)(n >> 1)) * kTileRows + (uint32_t)(n & 1) * 16 + (uint32_t)(lane & 15);   // query row of J = its dense slot
-    if (lane < 16 && q < nJ) {
-      const int nq = qn[n];
-      const int d0 = nq - W1, d1ub = nq - V2;
-      const bool cand = __int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub));
-      const size_t o = (size_t)pair * p.qstride + q;
-      p.best[o] = cand ? (uint32_t)code : kNoMatch;
-      if (cand) p.cd[o] = make_int2(d0, d1ub);
-    }
-  }
+  for (int n = 0; n < kNB16; ++n) MVGX_FINISH16(n, q < nJ, true)   // a dense slot is a row of J: every one below nJ holds a row
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1051,22 +1049,6 @@ __global__ __launch_bounds__(256, 3) void l2_filter16h_kernel(MatchParams p) {
     v4i accA[4], accB[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) accB[i] = v4i{kNegInit, kNegInit, kNegInit, kNegInit};
-#define MVGX_GROUPH(ACC, A, CV)                                                                              \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                          \
-    ACC[i_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], b[i_][0], CV, 0, 0, 0);                           \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                          \
-    ACC[i_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1], b[i_][1], ACC[i_], 0, 0, 0);
-#define MVGX_EPIH(ACC, BLK)                                                                                  \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
-    TW[i_][2 * (BLK)] = max(max(TW[i_][2 * (BLK)], ACC[i_][0]), ACC[i_][1]);                                \
-    TW[i_][2 * (BLK) + 1] = max(max(TW[i_][2 * (BLK) + 1], ACC[i_][2]), ACC[i_][3]);                        \
-  }
-#define MVGX_MIXH(NDS)                                                                                       \
-  _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);                                                        \
-    if (i_ < (NDS)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                      \
-  }
     v4i a0[2], a1[2], c0, c1;
     a0[0] = *reinterpret_cast<const v4i*>(wb);
     a0[1] = *reinterpret_cast<const v4i*>(wb + 2048);
@@ -1074,72 +1056,34 @@ __global__ __launch_bounds__(256, 3) void l2_filter16h_kernel(MatchParams p) {
     for (int t = 0; t < nt; ++t) {
       const int tn = min(t + 1, nt - 1);   // the fetch past the last tile re-reads it (no branch around the loads)
       // block 0 of tile t (accA); the maxima of the block before (block 1, accB) folded beside it
-      MVGX_GROUPH(accA, a0, c0)
+      MVGX_GROUP16(accA, 0, a0, c0)
       a1[0] = *reinterpret_cast<const v4i*>(wb + t * kTileBytes + 256);
       a1[1] = *reinterpret_cast<const v4i*>(wb + t * kTileBytes + 256 + 2048);
       c1 = *reinterpret_cast<const v4i*>(wc + t * (kTileRows * 4) + 64);
-      MVGX_EPIH(accB, 1)
-      MVGX_MIXH(3)
+      MVGX_EPI16(accB, 0, 1)
+      MVGX_MIX16(3)
       // block 1 of tile t (accB); block 0's maxima folded
-      MVGX_GROUPH(accB, a1, c1)
+      MVGX_GROUP16(accB, 0, a1, c1)
       a0[0] = *reinterpret_cast<const v4i*>(wb + tn * kTileBytes);
       a0[1] = *reinterpret_cast<const v4i*>(wb + tn * kTileBytes + 2048);
       c0 = *reinterpret_cast<const v4i*>(wc + tn * (kTileRows * 4));
-      MVGX_EPIH(accA, 0)
-      MVGX_MIXH(3)
+      MVGX_EPI16(accA, 0, 0)
+      MVGX_MIX16(3)
     }
-    MVGX_EPIH(accB, 1)   // drain: block 1 of the half window's last tile
-#undef MVGX_GROUPH
-#undef MVGX_EPIH
-#undef MVGX_MIXH
-    if ((hw & 1) || hw + 1 == nhalf) {   // (uniform) an 8-tile window is complete: its class maxima join the run-long ones, their maximum is the window maximum
-      const int win = hw >> 1;
+    MVGX_EPI16(accB, 0, 1)   // drain: block 1 of the half window's last tile
+    if ((hw & 1) || hw + 1 == nhalf) {   // (uniform) an 8-tile window is complete
 #pragma unroll
-      for (int n = 0; n < kNBh; ++n) {
-        const int v = max(max(max(TW[n][0], TW[n][1]), TW[n][2]), TW[n][3]);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { TP[n][c] = max(TP[n][c], TW[n][c]); TW[n][c] = kNegInit; }
-        const bool better = v > Q1[n];
-        Q2[n] = better ? Q1[n] : max(Q2[n], v);
-        Qg[n] = better ? win : Qg[n];
-        Q1[n] = better ? v : Q1[n];
-      }
+      for (int n = 0; n < kNBh; ++n) fold_window<4>(TW[n], TP[n], Q1[n], Q2[n], Qg[n], hw >> 1);
     }
   }
 
 #pragma unroll
-  for (int n = 0; n < kNBh; ++n) {
-    int p1 = kNegInit, p2 = kNegInit, pc = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int v = TP[n][c];
-      const bool better = v > p1;
-      p2 = better ? p1 : max(p2, v);
-      pc = better ? c : pc;
-      p1 = better ? v : p1;
-    }
-    int W1 = 2 * p1 - par, V2 = max(2 * p2 - par, 2 * Q2[n] - par);
-    int code = (4 * (pc >> 1) + 2 * (g4 >> 1) + (pc & 1)) | (par << 3) | (Qg[n] << 4);
-#pragma unroll
-    for (int x = 16; x <= 32; x <<= 1) {
-      const int o1 = __shfl_xor(W1, x), o2 = __shfl_xor(V2, x), oc = __shfl_xor(code, x);
-      const bool mine = W1 > o1;
-      V2 = mine ? max(V2, o1) : max(o2, W1);
-      code = mine ? code : oc;
-      W1 = mine ? W1 : o1;
-    }
-    const uint32_t q = (qt0 + (uint32_t)(n >> 1)) * kTileRows + (uint32_t)(n & 1) * 16 + (uint32_t)(lane & 15);
-    if (lane < 16 && qt0 + (uint32_t)(n >> 1) < ntJpad) {
-      const bool valid = qperm[n] != kNoMatch;
-      const int nq = qn[n];
-      const int d0 = nq - W1, d1ub = nq - V2;
-      const bool cand = valid && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));
-      const size_t o = (size_t)pair * p.qstride + q;
-      p.best[o] = cand ? (uint32_t)code : kNoMatch;
-      if (cand) p.cd[o] = make_int2(d0, d1ub);
-    }
-  }
+  for (int n = 0; n < kNBh; ++n) MVGX_FINISH16(n, qt0 + (uint32_t)(n >> 1) < ntJpad, qperm[n] != kNoMatch)   // parity slots: pad slots among them
 }
+#undef MVGX_FINISH16
+#undef MVGX_GROUP16
+#undef MVGX_EPI16
+#undef MVGX_MIX16
 
 // ------------------------------------------------------------------------------------------------
 // l2_verify (variant 4, stage 2): finishes the candidates of the filter. Same work items as the filter: kWaveUnits = false, a
@@ -1151,6 +1095,22 @@ __global__ __launch_bounds__(256, 3) void l2_filter16h_kernel(MatchParams p) {
 // runner-up, d1 = min(d1_ub, runner-up), and evaluate the reference's fp32 ratio test. best[] receives the ORIGINAL
 // index in I or kNoMatch; count[] the accepted queries of the pair.
 // ------------------------------------------------------------------------------------------------
+// sum over the 8 lanes of a half row (DPP butterfly: xor 1, xor 2, half-row mirror), in every lane
+__device__ __forceinline__ int sum8_dpp(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
+  return v;
+}
+// minimum over the 16 lanes of a row (the same butterfly and the row mirror), in every lane
+__device__ __forceinline__ int min16_dpp(int v) {
+  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0xB1, 0xF, 0xF, false));
+  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x4E, 0xF, 0xF, false));
+  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x141, 0xF, 0xF, false));
+  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x140, 0xF, 0xF, false));
+  return v;
+}
+
 template <bool kWaveUnits>
 __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
   const int lane = threadIdx.x & 63;
@@ -1224,9 +1184,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
       nb = __builtin_amdgcn_sdot4(vb.y, vb.y, nb, false);
       nb = __builtin_amdgcn_sdot4(vb.z, vb.z, nb, false);
       nb = __builtin_amdgcn_sdot4(vb.w, vb.w, nb, false);
-      nb += __builtin_amdgcn_update_dpp(0, nb, 0xB1, 0xF, 0xF, true);
-      nb += __builtin_amdgcn_update_dpp(0, nb, 0x4E, 0xF, 0xF, true);
-      nb += __builtin_amdgcn_update_dpp(0, nb, 0x141, 0xF, 0xF, true);
+      nb = sum8_dpp(nb);
       int dot = 0, na = 0;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
@@ -1234,34 +1192,21 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
         part = __builtin_amdgcn_sdot4(va[c].y, vb.y, part, false);
         part = __builtin_amdgcn_sdot4(va[c].z, vb.z, part, false);
         part = __builtin_amdgcn_sdot4(va[c].w, vb.w, part, false);
-        // sum over the 8 lanes holding the 8 pieces of this row (DPP butterfly: xor 1, xor 2, half-row mirror)
-        part += __builtin_amdgcn_update_dpp(0, part, 0xB1, 0xF, 0xF, true);
-        part += __builtin_amdgcn_update_dpp(0, part, 0x4E, 0xF, 0xF, true);
-        part += __builtin_amdgcn_update_dpp(0, part, 0x141, 0xF, 0xF, true);
+        part = sum8_dpp(part);   // over the 8 lanes holding the 8 pieces of this row
         dot = (c == piece) ? part : dot;   // lane keeps the row whose tile index equals its piece index
         // |a'|^2 of the same row, same way (cheaper than a scattered load of the per-slot norm)
         int sq = __builtin_amdgcn_sdot4(va[c].x, va[c].x, 0, false);
         sq = __builtin_amdgcn_sdot4(va[c].y, va[c].y, sq, false);
         sq = __builtin_amdgcn_sdot4(va[c].z, va[c].z, sq, false);
         sq = __builtin_amdgcn_sdot4(va[c].w, va[c].w, sq, false);
-        sq += __builtin_amdgcn_update_dpp(0, sq, 0xB1, 0xF, 0xF, true);
-        sq += __builtin_amdgcn_update_dpp(0, sq, 0x4E, 0xF, 0xF, true);
-        sq += __builtin_amdgcn_update_dpp(0, sq, 0x141, 0xF, 0xF, true);
+        sq = sum8_dpp(sq);
         na = (c == piece) ? sq : na;
       }
       const int d = valid ? na + nb - 2 * dot : INT_MAX;
-      // best of the cell (key = distance, lane) and runner-up over the 16 lanes of the group (DPP min butterfly)
-      int key = valid ? ((d << 4) | l16) : INT_MAX;
-      key = min(key, __builtin_amdgcn_update_dpp(INT_MAX, key, 0xB1, 0xF, 0xF, false));
-      key = min(key, __builtin_amdgcn_update_dpp(INT_MAX, key, 0x4E, 0xF, 0xF, false));
-      key = min(key, __builtin_amdgcn_update_dpp(INT_MAX, key, 0x141, 0xF, 0xF, false));
-      key = min(key, __builtin_amdgcn_update_dpp(INT_MAX, key, 0x140, 0xF, 0xF, false));
+      // best of the cell (key = distance, lane) and runner-up over the 16 lanes of the group
+      const int key = min16_dpp(valid ? ((d << 4) | l16) : INT_MAX);
       const int wl = key & 15, dbest = key >> 4;
-      int second = (l16 == wl) ? INT_MAX : d;
-      second = min(second, __builtin_amdgcn_update_dpp(INT_MAX, second, 0xB1, 0xF, 0xF, false));
-      second = min(second, __builtin_amdgcn_update_dpp(INT_MAX, second, 0x4E, 0xF, 0xF, false));
-      second = min(second, __builtin_amdgcn_update_dpp(INT_MAX, second, 0x141, 0xF, 0xF, false));
-      second = min(second, __builtin_amdgcn_update_dpp(INT_MAX, second, 0x140, 0xF, 0xF, false));
+      const int second = min16_dpp((l16 == wl) ? INT_MAX : d);
       bool ok = false;
       if (active && l16 == wl) {   // the winner's lane finishes the test and translates its slot to the original row
         if (key == INT_MAX || dbest != f_d0) atomicAdd(p.errflag, 1u);
@@ -1470,14 +1415,16 @@ struct mvgx_match_ctx {
   // options
   int variant = 4;          // 0 naive; exact top-2 kernel: 1 register-staged LDS, 2 LDS-DMA builtin, 3 LDS-DMA asm;
                             // 4 = filter (1 VALU / distance) + verify, LDS staging mode in `stage`
-  int filter_shape = 16;    // MFMA shape of the variant-4 filter: 16 = v_mfma_i32_16x16x64_i8 (l2_filter16_kernel, round 5), 32 = 32x32x32
+  int filter_shape = 16;    // MFMA shape of the variant-4 filter: 16 = v_mfma_i32_16x16x64_i8 (l2_filter16_kernel, round 5), 17 = the same at three
+                            // workgroups per CU (l2_filter16h_kernel), 32 = 32x32x32
   int stage = 3;            // staging mode of variant 4 (1 / 2 / 3 as above); 3 measured fastest (sweep call 5)
+                            // (how the four options combine: the table above resolve_form)
   int profile = 0;
   int64_t batch_pairs = 1 << 15;   // 16 batches on the 1k-image set: short pipeline fill/drain, 262k workgroups per filter launch
   int keep_host_results = 1;
   int overlap = 1;   // 1: batch b's filter runs beside batch b-1's verify/scan/compaction/copies (two slots)
   int verify_alone = 0;   // 1: the next filter kernel also waits for this batch's verify kernel (the two never share the device)
-  int debug_filter = 0;     // 1..7: timing experiments of l2_filter_kernel (see its kDbg), results invalid; 8, 16: earlier forms (valid)
+  int debug_filter = 0;     // epilogue form of l2_filter_kernel (FilterEpilogue): 0 kEpiFold, 16 kEpiFoldOneCv, 8 kEpiPerChain
   int stream_hold = 0;      // mvgx_match_run_stream: 1 = a batch's buffers survive two further sink calls (see Slot)
   int pinned_stream = 1;    // host buffers of the stream mode: pinned (contexts that are run repeatedly) or plain memory (one-shot)
   // regions
@@ -1538,6 +1485,121 @@ struct mvgx_match_ctx {
 };
 
 namespace {
+
+// ------------------------------------------------------------------------------------------------
+// The kernels of a run. The options "variant", "filter_shape", "stage" and "debug_filter" are resolved ONCE per run into a KernelForm;
+// nothing after resolve_form looks at them again. Rows are tried from the top, so "anything else" means: whatever the rows above left.
+//
+//   options                                             | kernel that fills best[]                          | its work list | slots of best[] | verify launch
+//   ----------------------------------------------------+---------------------------------------------------+---------------+-----------------+------------------------
+//   variant 0                                           | l2_top2_ratio_naive_kernel                        | work          | parity          | none
+//   variant 1 / 2 / 3 (the three other options ignored) | l2_top2_ratio_kernel<Regs / Glds / GldsAsm>       | work          | parity          | none
+//   variant 4, shape 16, stage 3, debug_filter 0        | l2_filter16_kernel (the default)                  | work8         | dense           | <true> over the records
+//   variant 4, shape 17, stage 3, debug_filter 0        | l2_filter16h_kernel, 2 * kHalfStageBytes of LDS   | work8h        | parity          | <false> over work
+//   variant 4, stage 1, anything else                   | l2_filter_kernel<Regs>                            | work          | parity          | <false> over work
+//   variant 4, stage 2, anything else                   | l2_filter_kernel<Glds>                            | work          | parity          | <false> over work
+//   variant 4, stage 3, debug_filter 8 / 16, any shape  | l2_filter_kernel<GldsAsm, PerChain / FoldOneCv>   | work          | parity          | <false> over work
+//   variant 4, stage 3, shape 32, debug_filter 0        | l2_filter_kernel<GldsAsm>                         | work          | parity          | <false> over work
+//
+// So the 16x16x64 kernels exist with LDS-DMA staging and the default epilogue only: shape 16 / 17 with stage 1 or 2 runs the 32x32x32 filter with
+// that staging, stage 1 or 2 ignores debug_filter, and debug_filter 8 / 16 ignores the shape. Every kernel but the naive one takes
+// 2 * kStageBytes of dynamic LDS where the table does not say otherwise.
+// ------------------------------------------------------------------------------------------------
+enum WorkList { kListItems16 = 0, kListItems8h = 1, kListRecords = 2 };   // MatchParams::work, work8h, work8: one workgroup per entry
+using MatchKernel = void (*)(MatchParams);
+struct KernelForm {
+  MatchKernel filter;       // fills best[] (final results, or candidate codes and cd[] when a verify launch follows)
+  uint32_t lds_bytes;       // its dynamic LDS
+  WorkList list;            // the work list it walks
+  bool dense_slots;         // best[] / cd[] are numbered by J's original row (else by its parity slot, MatchParams::rowpos)
+  MatchKernel verify;       // finishes the candidates; nullptr: the first kernel is exact
+  WorkList verify_list;     // ... walking this list
+  bool count_units;         // "profile" 2 counts the candidates over the records (count_candidates_units_kernel), else over all of best[]
+  bool reads(WorkList l) const { return list == l || (verify && verify_list == l); }
+};
+
+KernelForm form_for(int variant, int filter_shape, int stage, int debug_filter) {
+  constexpr uint32_t kTwoWindows = 2 * kStageBytes;
+  auto exact = [](MatchKernel k, uint32_t lds) { return KernelForm{k, lds, kListItems16, false, nullptr, kListItems16, false}; };
+  auto filter32 = [](MatchKernel k) { return KernelForm{k, kTwoWindows, kListItems16, false, &l2_verify_kernel<false>, kListItems16, false}; };
+  if (variant == 0) return exact(&l2_top2_ratio_naive_kernel, 0);
+  if (variant == 1) return exact(&l2_top2_ratio_kernel<kStageRegs>, kTwoWindows);
+  if (variant == 2) return exact(&l2_top2_ratio_kernel<kStageGlds>, kTwoWindows);
+  if (variant == 3) return exact(&l2_top2_ratio_kernel<kStageGldsAsm>, kTwoWindows);
+  if (filter_shape == 16 && stage == 3 && !debug_filter)
+    return KernelForm{&l2_filter16_kernel, kTwoWindows, kListRecords, true, &l2_verify_kernel<true>, kListRecords, true};
+  if (filter_shape == 17 && stage == 3 && !debug_filter)
+    return KernelForm{&l2_filter16h_kernel, 2 * kHalfStageBytes, kListItems8h, false, &l2_verify_kernel<false>, kListItems16, false};
+  if (stage == 1) return filter32(&l2_filter_kernel<kStageRegs>);
+  if (stage == 2) return filter32(&l2_filter_kernel<kStageGlds>);
+  if (debug_filter == 8) return filter32(&l2_filter_kernel<kStageGldsAsm, kEpiPerChain>);
+  if (debug_filter == 16) return filter32(&l2_filter_kernel<kStageGldsAsm, kEpiFoldOneCv>);
+  return filter32(&l2_filter_kernel<kStageGldsAsm>);
+}
+KernelForm resolve_form(const mvgx_match_ctx* c) { return form_for(c->variant, c->filter_shape, c->stage, c->debug_filter); }
+
+// The three work lists of a batch of nb pairs ij[2 k], ij[2 k + 1]; each builder returns the entries it wrote. A pair with nJ > 0 and nI >= 2
+// has at least one entry in every list, any other pair none:
+// matcher_brute_force.hpp:108-113: NN(=2) > rows -> no result; Matcher_Regions.cpp:65-69,85-90: empty regions skipped
+bool pair_has_work(const mvgx_match_ctx* c, uint32_t I, uint32_t J) { return c->h_n[I] >= 2 && c->h_n[J] != 0; }
+
+// MatchParams::work: (batch-local pair, first query tile) per kBlockQTiles occupied parity tiles of J
+uint32_t build_items16(const mvgx_match_ctx* c, const uint32_t* ij, uint32_t nb, uint2* out) {
+  uint32_t n = 0;
+  for (uint32_t k = 0; k < nb; ++k) {
+    const uint32_t I = ij[2 * k], J = ij[2 * k + 1];
+    if (!pair_has_work(c, I, J)) continue;
+    for (uint32_t qt = 0; qt < c->h_ntiles[J]; qt += kBlockQTiles) out[n++] = make_uint2(k, qt);
+  }
+  return n;
+}
+// MatchParams::work8h: two words per kBlockQTilesH occupied parity tiles of J, with everything l2_filter16h_kernel needs to start
+uint32_t build_items8h(const mvgx_match_ctx* c, const uint32_t* ij, uint32_t nb, uint4* out) {
+  uint32_t n = 0;
+  for (uint32_t k = 0; k < nb; ++k) {
+    const uint32_t I = ij[2 * k], J = ij[2 * k + 1];
+    if (!pair_has_work(c, I, J)) continue;
+    for (uint32_t qt = 0; qt < c->h_ntiles[J]; qt += kBlockQTilesH) {
+      out[2 * n] = make_uint4(k, qt, c->h_tile_off[I], c->h_tile_off[J]);
+      out[2 * n + 1] = make_uint4(c->h_ntiles[I], c->h_tile_off[J + 1] - c->h_tile_off[J], 0, 0);
+      ++n;
+    }
+  }
+  return n;
+}
+// MatchParams::work8: units of kNQ DENSE query tiles (ceil(nJ / 32) of them in J, never more than its parity tiles), one per wave, packed
+// four to a workgroup across the pairs that share I - a pair costs ceil(dense tiles / 4) waves, and no more of them than nJ rows need
+// whatever their norm parities are. A record holds everything its workgroup needs to start (no walk work -> pairs -> three per-image
+// tables). It is closed when it is full, when I changes and at the end of the batch; its unused waves are empty units (nJ = 0: nothing
+// stored) whose query pointer is aimed at I's own first dense tiles. The units of a pair are consecutive and share I, so they leave at most
+// one record part-filled per pair.
+uint32_t build_records(const mvgx_match_ctx* c, const uint32_t* ij, uint32_t nb, uint4* out) {
+  uint32_t n_rec = 0, rec_used = kWaves, rec_I = 0;   // records written; waves taken in the open one (kWaves: none is open) and its database image
+  for (uint32_t k = 0; k < nb; ++k) {
+    const uint32_t I = ij[2 * k], J = ij[2 * k + 1];
+    if (!pair_has_work(c, I, J)) continue;
+    const uint32_t ntJq = c->h_qtile_off[J + 1] - c->h_qtile_off[J];
+    for (uint32_t qt = 0; qt < ntJq; qt += kNQ) {
+      if (rec_used == kWaves || rec_I != I) {
+        uint4* r = out + (size_t)kRecQuads * n_rec++;
+        r[0] = make_uint4(c->h_tile_off[I], c->h_ntiles[I], 0, 0);
+        for (int w = 0; w < kWaves; ++w) r[1 + w] = make_uint4(0, c->h_qtile_off[I], 0, 0);
+        rec_used = 0; rec_I = I;
+      }
+      out[(size_t)kRecQuads * (n_rec - 1) + 1 + rec_used++] = make_uint4(k, c->h_qtile_off[J], qt, c->h_n[J]);
+    }
+  }
+  return n_rec;
+}
+
+// host list -> device, n elements (the device buffer exists even for an empty list)
+template <typename T>
+int upload_list(DevBuf<T>& d, const PinnedBuf<T>& h, size_t n, hipStream_t stream) {
+  const int rc = d.ensure(std::max<size_t>(n, 1));
+  if (rc) return rc;
+  if (n) MVGX_HIP(hipMemcpyAsync(d.p, h.p, n * sizeof(T), hipMemcpyHostToDevice, stream));
+  return MVGX_OK;
+}
 
 int prep_regions(mvgx_match_ctx* c) {
   const uint32_t n_images = c->n_images;
@@ -1692,32 +1754,21 @@ int mvgx_match_create(int device, mvgx_match_ctx** out) {
     MVGX_HIP(hipEventCreateWithFlags(&sl.ev_filter, hipEventDisableTiming));
     MVGX_HIP(hipEventCreateWithFlags(&sl.ev_copy, hipEventDisableTiming));
   }
-  // 2 x 33 KiB dynamic LDS for both MFMA variants
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_top2_ratio_kernel<kStageRegs>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_top2_ratio_kernel<kStageGlds>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_top2_ratio_kernel<kStageGldsAsm>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_filter16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_filter_kernel<kStageRegs>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_filter_kernel<kStageGlds>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_filter_kernel<kStageGldsAsm>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-#define MVGX_DBG_ATTR(D) MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_filter_kernel<kStageGldsAsm, D>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-  MVGX_DBG_ATTR(1) MVGX_DBG_ATTR(2) MVGX_DBG_ATTR(3) MVGX_DBG_ATTR(4) MVGX_DBG_ATTR(5) MVGX_DBG_ATTR(6) MVGX_DBG_ATTR(7) MVGX_DBG_ATTR(8) MVGX_DBG_ATTR(16)
-#undef MVGX_DBG_ATTR
-  if (const char* e = getenv("MVGX_MATCH_FILTER")) {   // experiments: see l2_filter_kernel's kDbg; the same values the option accepts
+  // dynamic LDS above the default limit: every kernel some combination of the options reaches (resolve_form's table)
+  std::vector<MatchKernel> seen;
+  for (int variant = 0; variant <= 4; ++variant)
+    for (int shape : {16, 17, 32})
+      for (int stage = 1; stage <= 3; ++stage)
+        for (int dbg : {0, 8, 16}) {
+          const KernelForm f = form_for(variant, shape, stage, dbg);
+          if (!f.lds_bytes || std::find(seen.begin(), seen.end(), f.filter) != seen.end()) continue;
+          seen.push_back(f.filter);
+          MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f.filter), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes));
+        }
+  if (const char* e = getenv("MVGX_MATCH_FILTER")) {   // the epilogue forms of l2_filter_kernel; the same values the option "debug_filter" accepts
     const int v = atoi(e);
-#ifdef MVGX_FILTER_TIMING_VARIANTS
-    const bool ok = (v >= 0 && v <= 8) || v == 16;
-#else
-    const bool ok = v == 0 || v == 8 || v == 16;
-#endif
-    if (ok) c->debug_filter = v;
-    else fprintf(stderr, "[mvgx] MVGX_MATCH_FILTER=%s ignored (not a form this build of the library has)\n", e);
+    if (v == 0 || v == 8 || v == 16) c->debug_filter = v;
+    else fprintf(stderr, "[mvgx] MVGX_MATCH_FILTER=%s ignored (0, 8 or 16)\n", e);
   }
   guard.c = nullptr;
   *out = c;
@@ -1785,13 +1836,9 @@ int mvgx_match_set_option(mvgx_match_ctx* c, const char* key, int64_t value) {
   } else if (!strcmp(key, "verify_alone")) {
     c->verify_alone = value != 0;
   } else if (!strcmp(key, "debug_filter")) {
-#ifdef MVGX_FILTER_TIMING_VARIANTS
-    MVGX_REQUIRE((value >= 0 && value <= 8) || value == 16, MVGX_ERR_ARG, "debug_filter must be 0..8 or 16");
-#else
     MVGX_REQUIRE(value == 0 || value == 8 || value == 16, MVGX_ERR_ARG,
-                 "debug_filter must be 0, 8 or 16 (the timing variants 1..7 return wrong lists and exist only in a library built with "
-                 "-DMVGX_FILTER_TIMING_VARIANTS)");
-#endif
+                 "debug_filter must be 0, 8 or 16 (the epilogue forms of l2_filter_kernel: window fold, both partitions per chain, "
+                 "window fold with a single-buffered initialiser)");
     c->debug_filter = (int)value;
   } else if (!strcmp(key, "stream_hold")) {
     c->stream_hold = value != 0;
@@ -1919,77 +1966,47 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
 
   MVGX_HIP(hipEventRecord(c->ev_total0, c->slot[0].stream));
 
+  const KernelForm form = resolve_form(c);
   // Stage 1 of a batch on its slot's stream: work list -> filter (+ verify) -> per-pair counts -> exclusive scan -> offsets to host
-  // l2_filter16_kernel and what follows it index best[] / cd[] by DENSE query slot (= original row of J); every other kernel by parity slot
-  const bool dense_queries = c->variant == 4 && c->filter_shape == 16 && c->stage == 3 && !c->debug_filter;
   auto issue = [&](mvgx_match_ctx::Slot& sl, mvgx_match_ctx::Slot* prev, uint64_t p0, uint32_t nb) -> int {
     int rc;
     hipStream_t stream = sl.stream;
     sl.p0 = p0; sl.nb = nb;
+    const uint32_t* ij = pairs_IJ + 2 * p0;
     if ((rc = sl.hp_pairs.ensure(nb))) return rc;
-    // worst-case work items: ceil(max tiles / 16) per pair
-    const uint32_t max_blocks_per_pair = std::max<uint32_t>(1, (c->max_tiles_pad + kBlockQTiles - 1) / kBlockQTiles);
-    if ((rc = sl.hp_work.ensure((size_t)nb * max_blocks_per_pair))) return rc;
-    const bool records = dense_queries;
-    const bool records_h = c->variant == 4 && c->filter_shape == 17 && c->stage == 3 && !c->debug_filter;
-    // wave-packed records: the units of a pair are consecutive and share I, so they leave at most one record part-filled per pair
-    if (records && (rc = sl.hp_work8.ensure((size_t)nb * max_blocks_per_pair * kRecQuads))) return rc;
-    if (records_h && (rc = sl.hp_work8h.ensure((size_t)nb * max_blocks_per_pair * 4))) return rc;
-    uint32_t n_work_h = 0;
-    uint32_t n_work = 0;
-    uint32_t n_rec = 0, rec_used = kWaves, rec_I = 0;   // records written; waves taken in the open one (kWaves: none is open) and its database image
     for (uint32_t k = 0; k < nb; ++k) {
-      const uint32_t I = pairs_IJ[2 * (p0 + k)], J = pairs_IJ[2 * (p0 + k) + 1];
+      const uint32_t I = ij[2 * k], J = ij[2 * k + 1];
       sl.hp_pairs.p[k] = make_uint2(I, J);
-      const uint32_t nI = c->h_n[I], nJ = c->h_n[J];
-      // matcher_brute_force.hpp:108-113: NN(=2) > rows  -> no result; Matcher_Regions.cpp:65-69,85-90: empty regions skipped
-      if (nI < 2 || nJ == 0) continue;
-      const uint32_t ntJ = c->h_ntiles[J];   // occupied tiles of the query image
-      const uint32_t ntJq = c->h_qtile_off[J + 1] - c->h_qtile_off[J];   // ... in the dense query set: ceil(nJ / 32) <= ntJ
-      // l2_filter16_kernel: units of kNQ query tiles, one per wave, packed four to a workgroup across the pairs that share I - a pair costs
-      // ceil(ntJq / 4) waves, not 4 * ceil(ntJ / 16), and no more of them than nJ rows need whatever their norm parities are. A record holds everything its workgroup needs to start (no walk work -> pairs -> three
-      // per-image tables). It is closed when it is full, when I changes and at the end of the batch; its unused waves are empty units
-      // (nJ = 0: nothing stored) whose query pointer is aimed at I's own first dense tiles.
-      if (records)
-        for (uint32_t qt = 0; qt < ntJq; qt += kNQ) {
-          if (rec_used == kWaves || rec_I != I) {
-            uint4* r = sl.hp_work8.p + (size_t)kRecQuads * n_rec++;
-            r[0] = make_uint4(c->h_tile_off[I], c->h_ntiles[I], 0, 0);
-            for (int w = 0; w < kWaves; ++w) r[1 + w] = make_uint4(0, c->h_qtile_off[I], 0, 0);
-            rec_used = 0; rec_I = I;
-          }
-          sl.hp_work8.p[(size_t)kRecQuads * (n_rec - 1) + 1 + rec_used++] = make_uint4(k, c->h_qtile_off[J], qt, nJ);
-        }
-      for (uint32_t qt = 0; qt < ntJ; qt += kBlockQTiles) {
-        if (records_h)
-          for (uint32_t q2 = qt; q2 < std::min(ntJ, qt + (uint32_t)kBlockQTiles); q2 += kBlockQTilesH) {
-            sl.hp_work8h.p[2 * n_work_h] = make_uint4(k, q2, c->h_tile_off[I], c->h_tile_off[J]);
-            sl.hp_work8h.p[2 * n_work_h + 1] = make_uint4(c->h_ntiles[I], c->h_tile_off[J + 1] - c->h_tile_off[J], 0, 0);
-            ++n_work_h;
-          }
-        sl.hp_work.p[n_work++] = make_uint2(k, qt);
-      }
+      if (!pair_has_work(c, I, J)) continue;
       st.n_pairs += 1;
-      st.n_desc_pairs += (uint64_t)nI * nJ;
+      st.n_desc_pairs += (uint64_t)c->h_n[I] * c->h_n[J];
     }
+    // the lists the form's kernels walk; worst case ceil(max tiles / 16) 16-tile items per pair, two 8-tile items or one record for each
+    const size_t max_items16 = (size_t)nb * std::max<uint32_t>(1, (c->max_tiles_pad + kBlockQTiles - 1) / kBlockQTiles);
+    uint32_t n_list[3] = {0, 0, 0};   // entries per WorkList
+    if (form.reads(kListItems16)) {
+      if ((rc = sl.hp_work.ensure(max_items16))) return rc;
+      n_list[kListItems16] = build_items16(c, ij, nb, sl.hp_work.p);
+    }
+    if (form.reads(kListItems8h)) {
+      if ((rc = sl.hp_work8h.ensure(max_items16 * 4))) return rc;
+      n_list[kListItems8h] = build_items8h(c, ij, nb, sl.hp_work8h.p);
+    }
+    if (form.reads(kListRecords)) {
+      if ((rc = sl.hp_work8.ensure(max_items16 * kRecQuads))) return rc;
+      n_list[kListRecords] = build_records(c, ij, nb, sl.hp_work8.p);
+    }
+    const uint32_t n_filter = n_list[form.list], n_verify = n_list[form.verify_list];   // grids
     if ((rc = sl.d_pairs.ensure(nb))) return rc;
-    if ((rc = sl.d_work.ensure(std::max<uint32_t>(n_work, 1)))) return rc;
-    if (records && (rc = sl.d_work8.ensure((size_t)std::max<uint32_t>(n_rec, 1) * kRecQuads))) return rc;
-    if (records_h && (rc = sl.d_work8h.ensure((size_t)std::max<uint32_t>(n_work_h, 1) * 2))) return rc;
     if ((rc = sl.d_best.ensure((size_t)nb * c->qstride))) return rc;
-    if (c->variant == 4) {
-      if ((rc = sl.d_cd.ensure((size_t)nb * c->qstride))) return rc;
-    }
+    if (form.verify && (rc = sl.d_cd.ensure((size_t)nb * c->qstride))) return rc;
     if ((rc = sl.d_count.ensure(nb))) return rc;
     if ((rc = sl.d_offsets.ensure((size_t)nb + 1))) return rc;
     if ((rc = sl.hp_offsets.ensure((size_t)nb + 1))) return rc;
     MVGX_HIP(hipMemcpyAsync(sl.d_pairs.p, sl.hp_pairs.p, nb * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    if (n_work && !records)   // (with records no kernel reads the 16-tile list: it only counts the pairs' work here)
-      MVGX_HIP(hipMemcpyAsync(sl.d_work.p, sl.hp_work.p, n_work * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    if (n_rec)
-      MVGX_HIP(hipMemcpyAsync(sl.d_work8.p, sl.hp_work8.p, (size_t)n_rec * kRecQuads * sizeof(uint4), hipMemcpyHostToDevice, stream));
-    if (n_work_h && records_h)
-      MVGX_HIP(hipMemcpyAsync(sl.d_work8h.p, sl.hp_work8h.p, (size_t)n_work_h * 2 * sizeof(uint4), hipMemcpyHostToDevice, stream));
+    if (form.reads(kListItems16) && (rc = upload_list(sl.d_work, sl.hp_work, n_list[kListItems16], stream))) return rc;
+    if (form.reads(kListItems8h) && (rc = upload_list(sl.d_work8h, sl.hp_work8h, (size_t)n_list[kListItems8h] * 2, stream))) return rc;
+    if (form.reads(kListRecords) && (rc = upload_list(sl.d_work8, sl.hp_work8, (size_t)n_list[kListRecords] * kRecQuads, stream))) return rc;
     MVGX_HIP(hipMemsetAsync(sl.d_count.p, 0, nb * sizeof(uint32_t), stream));
 
     MatchParams mp;
@@ -1998,67 +2015,39 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     mp.rows_u8 = c->d_rows_view; mp.img_row_off = c->d_row_off.p;
     mp.img_tile_off = c->d_tile_off.p; mp.img_n = c->d_n.p; mp.img_ntiles = c->d_ntiles.p;
     mp.cd = sl.d_cd.p; mp.img_neven = c->d_neven.p; mp.errflag = c->d_err.p;
-    mp.pairs = sl.d_pairs.p; mp.work = sl.d_work.p; mp.work8 = sl.d_work8.p; mp.work8h = sl.d_work8h.p; mp.n_work = n_work;
+    mp.pairs = sl.d_pairs.p; mp.work = sl.d_work.p; mp.work8 = sl.d_work8.p; mp.work8h = sl.d_work8h.p; mp.n_work = n_filter;
     mp.best = sl.d_best.p; mp.count = sl.d_count.p; mp.qstride = c->qstride; mp.ratio_sq = ratio_sq;
 
     // filter kernels run one after the other (each fills the device); everything else of batch b-1 runs beside filter b
     if (prev) MVGX_HIP(hipStreamWaitEvent(stream, prev->ev_filter, 0));
-    if (n_work) {
+    if (n_filter) {
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (c->profile) {
         e0 = get_event(c, n_ev++); e1 = get_event(c, n_ev++);
         MVGX_REQUIRE(e0 && e1, MVGX_ERR_HIP, "hipEventCreate failed");
         MVGX_HIP(hipEventRecord(e0, stream));
       }
-      if (c->variant == 0) {
-        hipLaunchKernelGGL(l2_top2_ratio_naive_kernel, dim3(n_work), dim3(256), 0, stream, mp);
-      } else if (c->variant == 1) {
-        hipLaunchKernelGGL(l2_top2_ratio_kernel<kStageRegs>, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
-      } else if (c->variant == 2) {
-        hipLaunchKernelGGL(l2_top2_ratio_kernel<kStageGlds>, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
-      } else if (c->variant == 3) {
-        hipLaunchKernelGGL(l2_top2_ratio_kernel<kStageGldsAsm>, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
-      } else if (c->filter_shape == 16 && c->stage == 3 && !c->debug_filter) {
-        hipLaunchKernelGGL(l2_filter16_kernel, dim3(n_rec), dim3(256), 2 * kStageBytes, stream, mp);
-      } else if (c->filter_shape == 17 && c->stage == 3 && !c->debug_filter) {
-        hipLaunchKernelGGL(l2_filter16h_kernel, dim3(n_work_h), dim3(256), 2 * kHalfStageBytes, stream, mp);
-      } else if (c->stage == 1) {
-        hipLaunchKernelGGL(l2_filter_kernel<kStageRegs>, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
-      } else if (c->stage == 2) {
-        hipLaunchKernelGGL(l2_filter_kernel<kStageGlds>, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
-      } else if (c->debug_filter) {   // timing experiments (wrong results; verify is skipped below)
-#define MVGX_DBG_CASE(D) case D: hipLaunchKernelGGL((l2_filter_kernel<kStageGldsAsm, D>), dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp); break;
-        switch (c->debug_filter) {
-#ifdef MVGX_FILTER_TIMING_VARIANTS   // parts of the kernel compiled out (wrong results): only in a build made for tools/filter_breakdown.py
-          MVGX_DBG_CASE(1) MVGX_DBG_CASE(2) MVGX_DBG_CASE(3) MVGX_DBG_CASE(4) MVGX_DBG_CASE(5) MVGX_DBG_CASE(6) MVGX_DBG_CASE(7)
-#endif
-          MVGX_DBG_CASE(8) MVGX_DBG_CASE(16) default: break; }
-#undef MVGX_DBG_CASE
-      } else {
-        hipLaunchKernelGGL(l2_filter_kernel<kStageGldsAsm>, dim3(n_work), dim3(256), 2 * kStageBytes, stream, mp);
-      }
+      hipLaunchKernelGGL(form.filter, dim3(n_filter), dim3(256), form.lds_bytes, stream, mp);
       MVGX_HIP(hipGetLastError());
       if (c->profile) MVGX_HIP(hipEventRecord(e1, stream));
       if (!c->verify_alone) MVGX_HIP(hipEventRecord(sl.ev_filter, stream));
       st.n_kernel_launches += 1;
-      if (c->variant == 4 && !(c->debug_filter & 7)) {
+      if (form.verify) {
         if (c->profile >= 2) {   // statistics pass (0.13 ms per batch): only on request, not in the timed runs of bench.py ("profile" 1)
           const size_t nslots = (size_t)nb * c->qstride;
-          if (records)
-            hipLaunchKernelGGL(count_candidates_units_kernel, dim3(n_rec), dim3(256), 0, stream, mp, c->d_err.p + 1);
+          if (form.count_units)
+            hipLaunchKernelGGL(count_candidates_units_kernel, dim3(n_verify), dim3(256), 0, stream, mp, c->d_err.p + 1);
           else
             hipLaunchKernelGGL(count_candidates_kernel, dim3((unsigned)((nslots + 16383) / 16384)), dim3(256), 0, stream,
                                sl.d_best.p, nslots, c->d_err.p + 1);
         }
-        if (records)   // the verify stage walks the units the filter just wrote, nothing else of best[]
-          hipLaunchKernelGGL(l2_verify_kernel<true>, dim3(n_rec), dim3(256), 0, stream, mp);
-        else
-          hipLaunchKernelGGL(l2_verify_kernel<false>, dim3(n_work), dim3(256), 0, stream, mp);
+        // the verify stage walks what the filter just wrote, nothing else of best[]
+        hipLaunchKernelGGL(form.verify, dim3(n_verify), dim3(256), 0, stream, mp);
         MVGX_HIP(hipGetLastError());
       }
       if (c->verify_alone) MVGX_HIP(hipEventRecord(sl.ev_filter, stream));
     }
-    if (!n_work) MVGX_HIP(hipEventRecord(sl.ev_filter, stream));
+    if (!n_filter) MVGX_HIP(hipEventRecord(sl.ev_filter, stream));
     hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, stream, sl.d_count.p, nb, sl.d_offsets.p);
     MVGX_HIP(hipGetLastError());
     MVGX_HIP(hipMemcpyAsync(sl.hp_offsets.p, sl.d_offsets.p, ((size_t)nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -2085,7 +2074,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     if (total) {
       if ((rc = sl.d_ij.ensure(total))) return rc;
       hipLaunchKernelGGL(compact_matches_kernel, dim3((nb + 3) / 4), dim3(256), 0, sl.stream, sl.d_best.p,
-                         sl.d_offsets.p, sl.d_pairs.p, c->d_n.p, c->d_row_off.p, dense_queries ? nullptr : c->d_rowpos.p, nb, c->qstride,
+                         sl.d_offsets.p, sl.d_pairs.p, c->d_n.p, c->d_row_off.p, form.dense_slots ? nullptr : c->d_rowpos.p, nb, c->qstride,
                          sl.d_ij.p);
       MVGX_HIP(hipGetLastError());
       if (sink) {
@@ -2145,7 +2134,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
   float ms = 0.f;
   MVGX_HIP(hipEventElapsedTime(&ms, c->ev_total0, c->ev_total1));
   st.total_ms = ms;
-  if (c->variant == 4 && !(c->debug_filter & 7)) {   // the verify kernel cross-checks the filter's d0 against its own exact recomputation
+  if (form.verify) {   // the verify kernel cross-checks the filter's d0 against its own exact recomputation
     uint32_t flags[2] = {0, 0};
     MVGX_HIP(hipMemcpy(flags, c->d_err.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     (void)hipMemset(c->d_err.p, 0, 2 * sizeof(uint32_t));

@@ -10,8 +10,9 @@ another query's code and trips it), so "run() returned" is "the flag is zero".""
 import functools
 
 import numpy as np
+import pytest
 
-from openmvg_amd import matching, synth
+from openmvg_amd import _capi, matching, synth
 from tests import _oracle
 from tests._match_wave_cases import force_norm_parity
 
@@ -151,3 +152,46 @@ def check_cross_check_shapes(kind="both"):
             assert np.array_equal(off, want_off) and np.array_equal(ij, want_ij), shape
     finally:
         ctx.close()
+
+
+# (variant, filter_shape, stage, debug_filter). The matcher resolves the four options into one kernel form per run (the table above
+# resolve_form in openmvg_amd/csrc/mvgx_match.hip, include/mvgx.h): every combination the filter accepts, and the exact kernel with the
+# filter's options set, which it must ignore ...
+FORMS_ALL = [(4, shape, stage, dbg) for shape in (16, 17, 32) for stage in (1, 2, 3) for dbg in (0, 8, 16)] + [(1, 17, 3, 16)]
+# ... and, for the slow emulation, the rows of that table that no other test reaches: a 16x16x64 shape with register or builtin staging
+# (the 32x32x32 filter runs), an earlier epilogue with shape 17 (the shape is ignored) and with stage 1 (the epilogue is)
+FORMS_UNREACHED = [(4, 17, 1, 0), (4, 16, 2, 0), (4, 17, 3, 8), (4, 16, 1, 16), (1, 17, 3, 16)]
+
+
+def check_form_resolution(forms, kind="sorted"):
+    """every combination of the options reaches a kernel form whose lists equal the reference's, on one context: best[] holds the words of
+    the run before, often in the other slot numbering, and each form reads only what its own filter launch wrote"""
+    want_off, want_ij = reference(kind)
+    ctx = context(batch_pairs=7)
+    try:
+        for variant, shape, stage, dbg in forms:
+            for key, value in (("variant", variant), ("filter_shape", shape), ("stage", stage), ("debug_filter", dbg)):
+                ctx.set_option(key, value)
+            off, ij = _run(ctx, kind)
+            assert np.array_equal(off, want_off) and np.array_equal(ij, want_ij), (variant, shape, stage, dbg)
+    finally:
+        ctx.close()
+
+
+def check_debug_filter_values():
+    """the option takes the three epilogue forms the library has and refuses everything else, the removed timing forms 1..7 included"""
+    ctx = matching.MatchContext(0)
+    try:
+        for value in (0, 8, 16):
+            ctx.set_option("debug_filter", value)
+        for value in (1, 2, 3, 4, 5, 6, 7, 9, 17):
+            with pytest.raises(_capi.MvgxError) as e:
+                ctx.set_option("debug_filter", value)
+            assert e.value.code == _capi.MVGX_ERR_ARG, value
+    finally:
+        ctx.close()
+
+
+def check_env_filter_ignored(kind="sorted"):
+    """call with MVGX_MATCH_FILTER=3 in the environment: the context is created all the same and runs the default form"""
+    check_default_equals_reference(kind)

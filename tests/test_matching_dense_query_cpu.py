@@ -27,3 +27,19 @@ def test_batch_seams_and_reused_slots(batch_pairs):
 def test_parity_slot_filters_agree_and_layouts_alternate_on_one_context():
     with _emu.emulated():
         cases.check_cross_check_shapes("sorted")
+
+
+def test_option_combinations_no_other_test_reaches_resolve_to_forms_that_equal_the_reference():
+    with _emu.emulated():
+        cases.check_form_resolution(cases.FORMS_UNREACHED)
+
+
+def test_debug_filter_accepts_the_three_epilogue_forms_only():
+    with _emu.emulated():
+        cases.check_debug_filter_values()
+
+
+def test_unknown_filter_form_in_the_environment_is_ignored(monkeypatch):
+    monkeypatch.setenv("MVGX_MATCH_FILTER", "3")
+    with _emu.emulated():
+        cases.check_env_filter_ignored()

@@ -26,3 +26,16 @@ def test_batch_seams_and_reused_slots(batch_pairs):
 
 def test_parity_slot_filters_agree_and_layouts_alternate_on_one_context():
     cases.check_cross_check_shapes()
+
+
+def test_every_option_combination_resolves_to_a_form_that_equals_the_reference():
+    cases.check_form_resolution(cases.FORMS_ALL)
+
+
+def test_debug_filter_accepts_the_three_epilogue_forms_only():
+    cases.check_debug_filter_values()
+
+
+def test_unknown_filter_form_in_the_environment_is_ignored(monkeypatch):
+    monkeypatch.setenv("MVGX_MATCH_FILTER", "3")
+    cases.check_env_filter_ignored()
