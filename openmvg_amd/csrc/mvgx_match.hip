@@ -308,6 +308,35 @@ __device__ __forceinline__ void stage_window_glds_asm(char* buf, const int8_t* _
   glds4_asm(grconst + wave * 64 + lane, __builtin_amdgcn_readfirstlane(lds0 + kWinTiles * kTileBytes + wave * 256));
 }
 
+// The same pieces with a SCALAR base (l2_filter16_kernel): the global address is an SGPR pair that the scalar unit advances per piece and
+// per window, plus one 32-bit offset per lane that never changes (lane * 16 + wave * 1024; a quarter of it for the constants) - no 64-bit
+// vector add per piece. M0, the statement's shape and the wait in front of the barrier are those of glds16_asm.
+#define MVGX_GLDS_SBASE 1   // (a build that replaces this block of staging statements by copies defines none: see stage_window16)
+__device__ __forceinline__ void glds16_sasm(const void* sbase, unsigned voff, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_dst)
+      : "memory");
+}
+__device__ __forceinline__ void glds4_sasm(const void* sbase, unsigned voff, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_dst)
+      : "memory");
+}
+__device__ __forceinline__ void stage_window_glds_sasm(char* buf, const int8_t* __restrict__ gtiles, const int* __restrict__ grconst,
+                                                       unsigned voff16, unsigned voff4, int wave) {
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)buf;
+#pragma unroll
+  for (int i = 0; i < kWinTiles; ++i)
+    glds16_sasm(gtiles + i * kTileBytes, voff16, __builtin_amdgcn_readfirstlane(lds0 + i * kTileBytes + wave * 1024));
+  glds4_sasm(grconst, voff4, __builtin_amdgcn_readfirstlane(lds0 + kWinTiles * kTileBytes + wave * 256));
+}
+
 // A HALF window = 4 tiles (16 KiB) + their cinit (512 B) for l2_filter16h_kernel: every wave moves a quarter of each tile, waves 0 and 1 half of the
 // constants each.
 constexpr int kHalfTiles = kWinTiles / 2;
@@ -851,6 +880,81 @@ constexpr int kNB16 = 2 * kNQ;   // query blocks of 16 per wave
     }                                                                                                                                     \
   }
 
+// ---- what only l2_filter16_kernel uses (l2_filter16h_kernel keeps the macros above and fold_window): the vector instructions beside its
+// MFMA stream that the lists do not depend on are taken out ("vector issue beside the MFMA stream").
+// A window's FIRST epilogue of a (query block, class) writes its maximum instead of folding into a reset value: nothing re-initialises TW
+// or a neutral accumulator per window.
+#define MVGX_EPI16_FIRST(ACC, N0, BLK)                                                                      \
+  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
+    TW[(N0) + i_][2 * (BLK)] = max(ACC[i_][0], ACC[i_][1]);                                                 \
+    TW[(N0) + i_][2 * (BLK) + 1] = max(ACC[i_][2], ACC[i_][3]);                                             \
+  }
+#define MVGX_EPI16_NONE(ACC, N0, BLK)   // the window's first group: no group before it
+// MVGX_MIX16 for that first group: eight MFMAs with the LDS reads behind the first ones, no v_max to pair them with
+#define MVGX_MIX16_NOEPI(NDS)                                                                               \
+  _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                        \
+    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);                                                        \
+    if (i_ < (NDS)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                      \
+  }
+
+// Stages a window through the scalar-base pieces. Without them (the staging statements replaced by per-lane copies, as the host build of
+// the tests does) the vector-address form moves the same bytes to the same places.
+__device__ __forceinline__ void stage_window16(char* buf, const int8_t* __restrict__ gtiles, const int* __restrict__ grconst,
+                                               unsigned voff16, unsigned voff4, int wave, int lane) {
+#ifdef MVGX_GLDS_SBASE
+  stage_window_glds_sasm(buf, gtiles, grconst, voff16, voff4, wave);
+#else
+  stage_window_glds_asm(buf, gtiles, grconst, wave, lane);
+#endif
+}
+
+// fold_window for l2_filter16_kernel: TW is not reset (the next window's first epilogues overwrite it), and the running top-2 of the window
+// maxima takes two instructions. With Q2 <= Q1 (true at the start, both kNegInit, and kept by every step since max(Q1, v) >= any median):
+//   v >  Q1: Q2 <= Q1 < v, the median of (Q1, v, Q2) is Q1           = what "better ? Q1 : ..." gives;
+//   v <= Q1: Q1 is a maximum of the three, the median is max(v, Q2)  = what "... : max(Q2, v)" gives, ties (v == Q1, v == Q2) included.
+// Qg keeps its strict compare: an equal later window does not take the place of the first one.
+__device__ __forceinline__ void fold_window16(const int (&TW)[4], int (&TP)[4], int& Q1, int& Q2, int& Qg, int win) {
+  const int v = max(max3i(TW[0], TW[1], TW[2]), TW[3]);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) TP[c] = max(TP[c], TW[c]);
+  Qg = v > Q1 ? win : Qg;
+  Q2 = med3i(Q1, v, Q2);
+  asm volatile("" : "+v"(Q1));   // the last reader of the old Q1 is behind us: the maximum is taken in place, no copy at the loop's back edge
+  Q1 = max(Q1, v);
+}
+
+// MVGX_FINISH16 with the same two-instruction top-2 over the lane's four classes (p2 <= p1 throughout, as in fold_window16)
+#define MVGX_FINISH16_MED3(N, INB, VALID)                                                                                                 \
+  {                                                                                                                                       \
+    int p1 = kNegInit, p2 = kNegInit, pc = 0;   /* best / second-best P-class of this lane */                                             \
+    _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                                                       \
+      const int v = TP[N][c];                                                                                                             \
+      pc = v > p1 ? c : pc;                                                                                                               \
+      p2 = med3i(p1, v, p2);                                                                                                              \
+      p1 = max(p1, v);                                                                                                                    \
+    }                                                                                                                                     \
+    /* exact w = |b'|^2 - d of the lane's best row; V2: its runner-up outside the best row's (class, window) cell */                      \
+    int W1 = 2 * p1 - par, V2 = max(2 * p2 - par, 2 * Q2[N] - par);                                                                       \
+    int code = (4 * (pc >> 1) + 2 * (g4 >> 1) + (pc & 1)) | (par << 3) | (Qg[N] << 4);   /* (s1, half, window) of the 32x32 kernel's cells */ \
+    /* the merge of the four lane groups that share the query column: as in MVGX_FINISH16 */                                              \
+    _Pragma("unroll") for (int x = 16; x <= 32; x <<= 1) {                                                                                \
+      const int o1 = __shfl_xor(W1, x), o2 = __shfl_xor(V2, x), oc = __shfl_xor(code, x);                                                 \
+      const bool mine = W1 > o1;                                                                                                          \
+      V2 = mine ? max(V2, o1) : max(o2, W1);                                                                                              \
+      code = mine ? code : oc;                                                                                                            \
+      W1 = mine ? W1 : o1;                                                                                                                \
+    }                                                                                                                                     \
+    const uint32_t q = (qt0 + (uint32_t)((N) >> 1)) * kTileRows + (uint32_t)((N) & 1) * 16 + (uint32_t)(lane & 15);                       \
+    if (lane < 16 && (INB)) {                                                                                                             \
+      const int nq = qn[N];                                                                                                               \
+      const int d0 = nq - W1, d1ub = nq - V2;                                                                                             \
+      const bool cand = (VALID) && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));                                    \
+      const size_t o = (size_t)pair * p.qstride + q;                                                                                      \
+      p.best[o] = cand ? (uint32_t)code : kNoMatch;                                                                                       \
+      if (cand) p.cd[o] = make_int2(d0, d1ub);                                                                                            \
+    }                                                                                                                                     \
+  }
+
 __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x kStageBytes
 
@@ -895,16 +999,18 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   }
 
   int TP[kNB16][4];                         // P-class maxima of the run
-  int TW[kNB16][4];                         // ... of the current window
+  int TW[kNB16][4];                         // ... of the current window: every one written by the window's first tile, never reset
   int Q1[kNB16], Q2[kNB16], Qg[kNB16];      // best / second-best window maximum, best window
 #pragma unroll
   for (int n = 0; n < kNB16; ++n) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) { TP[n][c] = kNegInit; TW[n][c] = kNegInit; }
+    for (int c = 0; c < 4; ++c) TP[n][c] = kNegInit;
     Q1[n] = kNegInit; Q2[n] = kNegInit; Qg[n] = 0;
   }
 
-  stage_window_glds_asm(smem, gI, gC, wave, lane);
+  // the lane's part of every staging address, once per workgroup (the rest is scalar): 16 bytes of a wave's KiB of a tile, one constant
+  const unsigned voff16 = (unsigned)(lane * 16 + wave * 1024), voff4 = (unsigned)(lane * 4 + wave * 256);
+  stage_window16(smem, gI, gC, voff16, voff4, wave, lane);
 #pragma unroll
   for (int n = 0; n < kNB16; ++n) {
 #pragma unroll
@@ -918,53 +1024,86 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
     char* buf = smem + (win & 1) * kStageBytes;
     char* nbuf = smem + ((win + 1) & 1) * kStageBytes;
     if (win + 1 < nwin)
-      stage_window_glds_asm(nbuf, gI + (size_t)(win + 1) * kWinTiles * kTileBytes, gC + (win + 1) * kWinRows, wave, lane);
+      stage_window16(nbuf, gI + (size_t)(win + 1) * kWinTiles * kTileBytes, gC + (win + 1) * kWinRows, voff16, voff4, wave, lane);
 
     const int nt = min(kWinTiles, ntI - win * kWinTiles);
     const char* wb = buf + lane_chunk;
     const char* wc = buf + kWinTiles * kTileBytes + g4 * 16;
-    // accB starts as the neutral element of max: its first epilogue is a no-op
     v4i accA[4], accB[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) accB[i] = v4i{kNegInit, kNegInit, kNegInit, kNegInit};
 
-    // one 16-row block = 16 MFMAs in two groups of four query blocks; the eight v_max3 of the previous group run in the shadow of a group
-#define MVGX_BLOCK16(A, CV, AN, CN, BLK, NEXT_OFF, NEXT_COFF)                                               \
+    // one 16-row block = 16 MFMAs in two groups of four query blocks; the eight v_max3 of the previous group run in the shadow of a group.
+    // EPI_B / MIX_B: the form of the first group's epilogue (of the group BEFORE the block) and its schedule, EPI_A: of the second's;
+    // LD (a constant): whether the block fetches the next one's fragments and constants
+#define MVGX_BLOCK16(A, CV, AN, CN, BLK, LD, NEXT_OFF, NEXT_COFF, EPI_B, MIX_B, EPI_A)                      \
   {                                                                                                         \
     MVGX_GROUP16(accA, 0, A, CV)                                                                            \
-    AN[0] = *reinterpret_cast<const v4i*>(wb + (NEXT_OFF));                                                 \
-    AN[1] = *reinterpret_cast<const v4i*>(wb + (NEXT_OFF) + 2048);                                          \
-    MVGX_EPI16(accB, 4, 1 - (BLK))                                                                          \
-    MVGX_MIX16(2)                                                                                           \
+    if (LD) {                                                                                               \
+      AN[0] = *reinterpret_cast<const v4i*>(wb + (NEXT_OFF));                                               \
+      AN[1] = *reinterpret_cast<const v4i*>(wb + (NEXT_OFF) + 2048);                                        \
+    }                                                                                                       \
+    EPI_B(accB, 4, 1 - (BLK))                                                                               \
+    MIX_B((LD) ? 2 : 0)                                                                                     \
     MVGX_GROUP16(accB, 4, A, CV)                                                                            \
-    CN = *reinterpret_cast<const v4i*>(wc + (NEXT_COFF));                                                   \
-    MVGX_EPI16(accA, 0, BLK)                                                                                \
-    MVGX_MIX16(1)                                                                                           \
+    if (LD) CN = *reinterpret_cast<const v4i*>(wc + (NEXT_COFF));                                           \
+    EPI_A(accA, 0, BLK)                                                                                     \
+    MVGX_MIX16((LD) ? 1 : 0)                                                                                \
   }
+    // a tile whose epilogues all fold (every tile of a window but its first, and the first group of its second)
+#define MVGX_TILE16(T)                                                                                                                       \
+  MVGX_BLOCK16(a0, c0, a1, c1, 0, true, (T) * kTileBytes + 256, (T) * (kTileRows * 4) + 64, MVGX_EPI16, MVGX_MIX16, MVGX_EPI16)              \
+  MVGX_BLOCK16(a1, c1, a0, c0, 1, true, ((T) + 1) * kTileBytes, ((T) + 1) * (kTileRows * 4), MVGX_EPI16, MVGX_MIX16, MVGX_EPI16)                \
+  MVGX_TILE16_END
+    // every tile is a scheduling region of its own, as the loop body was: over one region of 256 MFMAs the group barriers of MVGX_MIX16 pair
+    // an MFMA with the v_max3 of its OWN group, which then waits for the result
+#define MVGX_TILE16_END __builtin_amdgcn_sched_barrier(0);
     v4i a0[2], a1[2], c0, c1;
     a0[0] = *reinterpret_cast<const v4i*>(wb);
     a0[1] = *reinterpret_cast<const v4i*>(wb + 2048);
     c0 = *reinterpret_cast<const v4i*>(wc);
-    // (the first epilogue of a window folds accB = neutral into block class 1 of blocks 4..7: a no-op)
     // (round 6) the wave is given issue priority over its SIMD-mate for the tile loop and hands it back for the window's fold: the mate in
     // its MFMA stream then goes first while this wave is at a fold, a barrier, its start or its merge - 11.80 against 11.89 ms per launch at
     // 2 000 descriptors, 3.53 against 3.57 at 1 000 (calls r6_58 / r6_59; priority over the whole run of windows: half the gain; priority
     // in the OTHER phases instead: a little slower than none)
     __builtin_amdgcn_s_setprio(3);
-    for (int t = 0; t < nt; ++t) {
-      const int tn = min(t + 1, nt - 1);   // the fetch past the window's last tile re-reads it (no branch around the loads)
-      MVGX_BLOCK16(a0, c0, a1, c1, 0, t * kTileBytes + 256, t * (kTileRows * 4) + 64)
-      MVGX_BLOCK16(a1, c1, a0, c0, 1, tn * kTileBytes, tn * (kTileRows * 4))
+    // The order of a window's epilogues is (accA, block 0), (accB, block 0), (accA, block 1) in its first tile and (accB, block 1) beside the
+    // group after it: these four are the first touch of the 32 TW and WRITE them. A window has at least one tile (nwin = ceil(ntI / 8)).
+    if (nt == kWinTiles) {
+      // a full window, unrolled: every LDS address is the window's pointer plus an immediate (at most 7 * 4096 + 2048 + 256 and
+      // 32768 + 7 * 128 + 64 of the 65 535 the field holds); nothing is fetched past the last tile
+      MVGX_BLOCK16(a0, c0, a1, c1, 0, true, 256, 64, MVGX_EPI16_NONE, MVGX_MIX16_NOEPI, MVGX_EPI16_FIRST)
+      MVGX_BLOCK16(a1, c1, a0, c0, 1, true, kTileBytes, kTileRows * 4, MVGX_EPI16_FIRST, MVGX_MIX16, MVGX_EPI16_FIRST)
+      MVGX_TILE16_END
+      MVGX_BLOCK16(a0, c0, a1, c1, 0, true, kTileBytes + 256, kTileRows * 4 + 64, MVGX_EPI16_FIRST, MVGX_MIX16, MVGX_EPI16)
+      MVGX_BLOCK16(a1, c1, a0, c0, 1, true, 2 * kTileBytes, 2 * (kTileRows * 4), MVGX_EPI16, MVGX_MIX16, MVGX_EPI16)
+      MVGX_TILE16_END
+      MVGX_TILE16(2) MVGX_TILE16(3) MVGX_TILE16(4) MVGX_TILE16(5) MVGX_TILE16(6)
+      MVGX_BLOCK16(a0, c0, a1, c1, 0, true, 7 * kTileBytes + 256, 7 * (kTileRows * 4) + 64, MVGX_EPI16, MVGX_MIX16, MVGX_EPI16)
+      MVGX_BLOCK16(a1, c1, a0, c0, 1, false, 0, 0, MVGX_EPI16, MVGX_MIX16, MVGX_EPI16)
+    } else {
+      // the one short window of an image keeps the tile loop. Its first tile is peeled likewise; the fourth first touch would fall into
+      // the loop or the drain, so those eight maxima start at the neutral element instead
+#pragma unroll
+      for (int n = 4; n < kNB16; ++n) { TW[n][2] = kNegInit; TW[n][3] = kNegInit; }
+      const int t1 = min(1, nt - 1);
+      MVGX_BLOCK16(a0, c0, a1, c1, 0, true, 256, 64, MVGX_EPI16_NONE, MVGX_MIX16_NOEPI, MVGX_EPI16_FIRST)
+      MVGX_BLOCK16(a1, c1, a0, c0, 1, true, t1 * kTileBytes, t1 * (kTileRows * 4), MVGX_EPI16_FIRST, MVGX_MIX16, MVGX_EPI16_FIRST)
+      for (int t = 1; t < nt; ++t) {
+        const int tn = min(t + 1, nt - 1);   // the fetch past the window's last tile re-reads it (no branch around the loads)
+        MVGX_BLOCK16(a0, c0, a1, c1, 0, true, t * kTileBytes + 256, t * (kTileRows * 4) + 64, MVGX_EPI16, MVGX_MIX16, MVGX_EPI16)
+        MVGX_BLOCK16(a1, c1, a0, c0, 1, true, tn * kTileBytes, tn * (kTileRows * 4), MVGX_EPI16, MVGX_MIX16, MVGX_EPI16)
+      }
     }
     MVGX_EPI16(accB, 4, 1)   // drain: the second group of the window's last block
     __builtin_amdgcn_s_setprio(0);
+#undef MVGX_TILE16
+#undef MVGX_TILE16_END
 #undef MVGX_BLOCK16
 #pragma unroll
-    for (int n = 0; n < kNB16; ++n) fold_window<4>(TW[n], TP[n], Q1[n], Q2[n], Qg[n], win);
+    for (int n = 0; n < kNB16; ++n) fold_window16(TW[n], TP[n], Q1[n], Q2[n], Qg[n], win);
   }
 
 #pragma unroll
-  for (int n = 0; n < kNB16; ++n) MVGX_FINISH16(n, q < nJ, true)   // a dense slot is a row of J: every one below nJ holds a row
+  for (int n = 0; n < kNB16; ++n) MVGX_FINISH16_MED3(n, q < nJ, true)   // a dense slot is a row of J: every one below nJ holds a row
 }
 
 // ------------------------------------------------------------------------------------------------
