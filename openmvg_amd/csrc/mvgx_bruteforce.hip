@@ -22,19 +22,23 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <deque>
 #include <mutex>
 #include <random>
 #include <thread>
 #include <vector>
 
+#include "mvgx_buffers.h"
 #include "mvgx_common.h"
+#include "mvgx_match_batch.h"
 
 namespace {
 
+using mvgx::DevBuf;
+using mvgx::PinnedBuf;
 using mvgx::set_error;
 
 constexpr int kQBlock = 256;                 // queries per workgroup
-constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 constexpr uint32_t kRowBits = 22;            // rows per image < 2^22 (distance <= 512 fits the upper 10 bits)
 
 struct HamParams {
@@ -43,7 +47,7 @@ struct HamParams {
   const uint32_t* img_n;        // rows of image k
   const uint2* pairs;           // (I, J) per pair of the batch
   const uint2* work;            // (pair in batch, first query)
-  uint32_t* best;               // [pair][query] -> database row or kInvalid
+  uint32_t* best;               // [pair][query] -> database row or kNoMatch
   uint32_t* count;              // matches per pair
   uint32_t qstride;
   float ratio;
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(kQBlock) void hamming_top2_ratio_kernel(HamParams p
     for (int k = 0; k < NW; ++k) qv[k] = src[k];
   }
   const uint32_t* __restrict__ db = p.words + p.img_row_off[ij.x] * NW;   // wave-uniform: scalar loads
-  uint32_t b0 = kInvalid, b1 = kInvalid;
+  uint32_t b0 = kNoMatch, b1 = kNoMatch;
   // rows in groups of four: the scalar loads of a group are issued back to back and their latency is hidden by the VALU work
   // of the other waves on the SIMD (35 VGPRs: the occupancy is bounded by the workgroup size, not by registers)
 #pragma unroll 4
@@ -83,13 +87,13 @@ __global__ __launch_bounds__(kQBlock) void hamming_top2_ratio_kernel(HamParams p
     b1 = umin32(b1, hi);   // = med3(b0, b1, key) for b0 <= b1
     b0 = lo;
   }
-  uint32_t out = kInvalid;
+  uint32_t out = kNoMatch;
   if (active && nI >= 2) {   // matcher_brute_force.hpp:108-113: NN (= 2) > rows -> no result
     const float d0 = (float)(b0 >> kRowBits), d1 = (float)(b1 >> kRowBits);
     if (d0 < __fmul_rn(p.ratio, d1)) out = b0 & ((1u << kRowBits) - 1u);
   }
   if (active) p.best[(size_t)w.x * p.qstride + q] = out;
-  if (out != kInvalid) atomicAdd(&sh_count, 1u);
+  if (out != kNoMatch) atomicAdd(&sh_count, 1u);
   __syncthreads();
   if (threadIdx.x == 0 && sh_count) atomicAdd(&p.count[w.x], sh_count);
 }
@@ -161,13 +165,13 @@ __global__ __launch_bounds__(kQBlock) void l2f_top2_ratio_kernel(L2fParams p) {
     const uint64_t k1 = i + 1 < nI ? (((uint64_t)__float_as_uint(result.y) << 32) | (i + 1)) : ~0ull;   // pad row: never a neighbour
     top2_u64(k1, b0, b1);
   }
-  uint32_t out = kInvalid;
+  uint32_t out = kNoMatch;
   if (active && nI >= 2) {
     const float d0 = __uint_as_float((uint32_t)(b0 >> 32)), d1 = __uint_as_float((uint32_t)(b1 >> 32));
     if (d0 < p.ratio_sq * d1) out = (uint32_t)b0;   // matching_filters.hpp:39-60 on float distances
   }
   if (active) p.best[(size_t)w.x * p.qstride + q] = out;
-  if (out != kInvalid) atomicAdd(&sh_count, 1u);
+  if (out != kNoMatch) atomicAdd(&sh_count, 1u);
   __syncthreads();
   if (threadIdx.x == 0 && sh_count) atomicAdd(&p.count[w.x], sh_count);
 }
@@ -221,13 +225,13 @@ __global__ __launch_bounds__(kQBlock) void l2u8_top2_ratio_kernel(L2uParams p) {
     const uint32_t d = dn[i] + qn - 2u * dot;   // exact: every term < 2^24 for lengths up to 256
     top2_u64(((uint64_t)d << 32) | i, b0, b1);
   }
-  uint32_t out = kInvalid;
+  uint32_t out = kNoMatch;
   if (active && nI >= 2) {
     const float d0 = (float)(uint32_t)(b0 >> 32), d1 = (float)(uint32_t)(b1 >> 32);
     if (d0 < __fmul_rn(p.ratio_sq, d1)) out = (uint32_t)b0;
   }
   if (active) p.best[(size_t)w.x * p.qstride + q] = out;
-  if (out != kInvalid) atomicAdd(&sh_count, 1u);
+  if (out != kNoMatch) atomicAdd(&sh_count, 1u);
   __syncthreads();
   if (threadIdx.x == 0 && sh_count) atomicAdd(&p.count[w.x], sh_count);
 }
@@ -284,7 +288,7 @@ __global__ __launch_bounds__(kQBlock) void cascade_match_kernel(CasParams p) {
   const bool active = q < nJ;
   if (threadIdx.x == 0) sh_count = 0;
   __syncthreads();
-  uint32_t out = kInvalid;
+  uint32_t out = kNoMatch;
   if (active) {
     const uint64_t offI = p.img_row_off[ij.x], rowJ = p.img_row_off[ij.y] + q;
     const uint4 bq = p.bids[rowJ];
@@ -393,77 +397,12 @@ __global__ __launch_bounds__(kQBlock) void cascade_match_kernel(CasParams p) {
     }
     p.best[(size_t)w.x * p.qstride + q] = out;
   }
-  if (out != kInvalid) atomicAdd(&sh_count, 1u);
+  if (out != kNoMatch) atomicAdd(&sh_count, 1u);
   __syncthreads();
   if (threadIdx.x == 0 && sh_count) atomicAdd(&p.count[w.x], sh_count);
 }
 
-// exclusive scan of the per-pair counts (one workgroup)
-__global__ __launch_bounds__(1024) void hamming_scan_kernel(const uint32_t* __restrict__ count, uint32_t n, uint32_t* __restrict__ offsets) {
-  __shared__ uint32_t part[1024];
-  const uint32_t per = (n + 1023) / 1024;
-  const uint32_t lo = umin32(threadIdx.x * per, n), hi = umin32(lo + per, n);
-  uint32_t s = 0;
-  for (uint32_t k = lo; k < hi; ++k) s += count[k];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const uint32_t v = threadIdx.x >= (uint32_t)off ? part[threadIdx.x - off] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[threadIdx.x] - s;
-  for (uint32_t k = lo; k < hi; ++k) { offsets[k] = run; run += count[k]; }
-  if (threadIdx.x == 1023) offsets[n] = part[1023];
-}
-
-// ordered gather: matches of a pair in ascending query index (regions_matcher.hpp:198-205 emits them in that order)
-__global__ __launch_bounds__(256) void hamming_compact_kernel(const uint32_t* __restrict__ best, const uint32_t* __restrict__ offsets,
-                                                              const uint2* __restrict__ pairs, const uint32_t* __restrict__ img_n,
-                                                              uint32_t qstride, uint2* __restrict__ out) {
-  __shared__ uint32_t sh[256];
-  const uint32_t k = blockIdx.x;
-  const uint32_t nJ = img_n[pairs[k].y];
-  uint32_t base = offsets[k];
-  if (offsets[k + 1] == base) return;
-  for (uint32_t q0 = 0; q0 < nJ; q0 += 256) {
-    const uint32_t q = q0 + threadIdx.x;
-    const uint32_t b = q < nJ ? best[(size_t)k * qstride + q] : kInvalid;
-    const uint32_t f = b != kInvalid ? 1u : 0u;
-    sh[threadIdx.x] = f;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-      const uint32_t v = threadIdx.x >= (uint32_t)off ? sh[threadIdx.x - off] : 0;
-      __syncthreads();
-      sh[threadIdx.x] += v;
-      __syncthreads();
-    }
-    if (f) out[base + sh[threadIdx.x] - 1] = make_uint2(b, q);
-    base += sh[255];
-    __syncthreads();
-  }
-}
-
-template <typename T>
-struct Buf {
-  T* p = nullptr;
-  size_t cap = 0;
-  bool pinned = false;
-  int ensure(size_t n) {
-    if (n <= cap) return MVGX_OK;
-    release();
-    const size_t want = std::max<size_t>(n + n / 4, 16);
-    if (pinned) MVGX_HIP(hipHostMalloc(reinterpret_cast<void**>(&p), want * sizeof(T), 0));
-    else MVGX_HIP(mvgx::device_malloc(reinterpret_cast<void**>(&p), want * sizeof(T)));
-    cap = want;
-    return MVGX_OK;
-  }
-  void release() {
-    if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); }
-    p = nullptr; cap = 0;
-  }
-};
+// (per-pair counts -> exclusive scan -> ordered compaction: scan_counts_kernel and compact_matches_kernel of mvgx_match_batch.h)
 
 }  // namespace
 
@@ -614,19 +553,28 @@ struct BfCtx {
   int64_t batch_pairs = 1 << 15;
   uint32_t n_images = 0, nw = 0, desc_bytes = 0, max_n = 0, qstride = 0;
   std::vector<uint32_t> h_n;
-  Buf<uint32_t> d_words, d_n, d_best, d_count, d_offsets, d_norms;
+  DevBuf<uint32_t> d_words, d_n, d_best, d_count, d_offsets, d_norms;
   // kind 3 (cascade hashing): hash codes, bucket ids, per-image bucket lists
-  Buf<uint4> d_hash, d_bids;
-  Buf<uint32_t> d_bstart, d_items;
+  DevBuf<uint4> d_hash, d_bids;
+  DevBuf<uint32_t> d_bstart, d_items;
   uint32_t cas_groups = 0, cas_buckets = 0;
   bool cas_float = false;             // cascade hashing on float rows (AKAZE_Float_Regions): L2<float> on the candidates
-  Buf<uint64_t> d_row_off;
-  Buf<uint2> d_pairs, d_work, d_ij;
-  Buf<uint2> hp_pairs, hp_work;
-  Buf<uint32_t> hp_offsets;
+  DevBuf<uint64_t> d_row_off;
+  DevBuf<uint2> d_pairs, d_work, d_ij;
+  PinnedBuf<uint2> hp_pairs, hp_work;
+  PinnedBuf<uint32_t> hp_offsets;
   std::vector<uint64_t> res_offsets;
   std::vector<uint32_t> res_ij;
-  BfCtx() { hp_pairs.pinned = hp_work.pinned = hp_offsets.pinned = true; }
+  BfCtx() {   // every buffer regrows with 25 % headroom: the lists of a batch vary in length
+    auto pad = [](auto&... b) { ((b.headroom_quarter = true), ...); };
+    pad(d_words, d_n, d_best, d_count, d_offsets, d_norms, d_hash, d_bids, d_bstart, d_items, d_row_off, d_pairs, d_work, d_ij, hp_pairs, hp_work, hp_offsets);
+  }
+  ~BfCtx() {   // the stream drained, then events and stream; the buffers free themselves after this body (also after a failed create)
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (hipEvent_t e : {ev0, ev1, evk0, evk1}) if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 struct mvgx_hamming_ctx : BfCtx {};
 struct mvgx_l2f_ctx : BfCtx {};
@@ -644,17 +592,6 @@ int bf_create(int kind, int device, BfCtx* c) {
   MVGX_HIP(hipEventCreate(&c->ev0)); MVGX_HIP(hipEventCreate(&c->ev1));
   MVGX_HIP(hipEventCreate(&c->evk0)); MVGX_HIP(hipEventCreate(&c->evk1));
   return MVGX_OK;
-}
-
-void bf_release(BfCtx* c) {
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  c->d_hash.release(); c->d_bids.release(); c->d_bstart.release(); c->d_items.release();
-  c->d_words.release(); c->d_norms.release(); c->d_n.release(); c->d_best.release(); c->d_count.release(); c->d_offsets.release();
-  c->d_row_off.release(); c->d_pairs.release(); c->d_work.release(); c->d_ij.release();
-  c->hp_pairs.release(); c->hp_work.release(); c->hp_offsets.release();
-  for (hipEvent_t e : {c->ev0, c->ev1, c->evk0, c->evk1}) if (e) (void)hipEventDestroy(e);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
 }
 
 int bf_set_option(BfCtx* c, const char* key, int64_t value) {
@@ -725,25 +662,19 @@ int bf_set_regions(BfCtx* c, const uint8_t* const* desc_rows, const uint32_t* n_
 int bf_run(BfCtx* c, const uint32_t* pairs_IJ, uint64_t n_pairs, float ratio, mvgx_match_stats* stats) {
   MVGX_REQUIRE(c && (pairs_IJ || n_pairs == 0), MVGX_ERR_ARG, "run: NULL argument");
   MVGX_REQUIRE(c->nw != 0 || c->n_images == 0, MVGX_ERR_STATE, "run before set_regions");
+  int rc;
   // (cascade hashing orders its ten candidates by (distance, id): no ambiguous tie, any ratio is reproduced)
-  MVGX_REQUIRE(c->kind == 3 || (ratio <= 1.0f && ratio >= 0.0f), MVGX_ERR_UNSUPPORTED,
-               "ratio = %g: the device path reproduces the reference only for 0 <= ratio <= 1 "
-               "(ties are libstdc++ partial_sort order beyond that)", (double)ratio);
+  if (c->kind != 3 && (rc = check_ratio(ratio, "ratio"))) return rc;
   MVGX_HIP(hipSetDevice(c->device));
-  for (uint64_t k = 0; k < n_pairs; ++k)
-    MVGX_REQUIRE(pairs_IJ[2 * k] < c->n_images && pairs_IJ[2 * k + 1] < c->n_images, MVGX_ERR_ARG,
-                 "pair %llu references image out of range", (unsigned long long)k);
+  if ((rc = check_pairs_in_range(pairs_IJ, n_pairs, c->n_images, "run"))) return rc;
   c->res_offsets.assign(n_pairs + 1, 0);
   c->res_ij.clear();
   mvgx_match_stats st;
   memset(&st, 0, sizeof(st));
   st.variant = (c->kind == 0 ? 100 : c->kind == 1 ? 200 : c->kind == 2 ? 300 : 400) + c->nw;
-  int rc;
   float kernel_ms = 0.f;
   MVGX_HIP(hipEventRecord(c->ev0, c->stream));
-  // pairs per batch: the option, capped so that the scratch (4 B per pair and query slot) stays near 2 GB when the images carry
-  // tens of thousands of descriptors (the same rule as mvgx_match_run); match totals of a batch are 32-bit on the device
-  const uint64_t B = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->batch_pairs, std::max<uint64_t>(16, (1ull << 29) / std::max<uint32_t>(c->qstride, 1))));
+  const uint64_t B = batch_size(c->batch_pairs, c->qstride);   // match totals of a batch are 32-bit on the device
   MVGX_REQUIRE(B * std::max<uint32_t>(c->qstride, 1) < (1ull << 32), MVGX_ERR_UNSUPPORTED,
                "images of %u descriptor slots: a 16-pair batch overflows the 32-bit match offsets of the device path", c->qstride);
   for (uint64_t p0 = 0; p0 < n_pairs; p0 += B) {
@@ -802,7 +733,7 @@ int bf_run(BfCtx* c, const uint32_t* pairs_IJ, uint64_t n_pairs, float ratio, mv
       MVGX_HIP(hipEventRecord(c->evk1, c->stream));
       st.n_kernel_launches += 1;
     }
-    hipLaunchKernelGGL(hamming_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_count.p, nb, c->d_offsets.p);
+    hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_count.p, nb, c->d_offsets.p);
     MVGX_HIP(hipGetLastError());
     MVGX_HIP(hipMemcpyAsync(c->hp_offsets.p, c->d_offsets.p, ((size_t)nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     MVGX_HIP(hipStreamSynchronize(c->stream));
@@ -817,8 +748,9 @@ int bf_run(BfCtx* c, const uint32_t* pairs_IJ, uint64_t n_pairs, float ratio, mv
     st.n_matches += total;
     if (total) {
       if ((rc = c->d_ij.ensure(total))) return rc;
-      hipLaunchKernelGGL(hamming_compact_kernel, dim3(nb), dim3(256), 0, c->stream, c->d_best.p, c->d_offsets.p, c->d_pairs.p,
-                         c->d_n.p, c->qstride, c->d_ij.p);
+      // best[] is indexed by the query row itself: no row -> slot table
+      hipLaunchKernelGGL(compact_matches_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, c->d_best.p, c->d_offsets.p, c->d_pairs.p,
+                         c->d_n.p, c->d_row_off.p, (const uint32_t*)nullptr, nb, c->qstride, c->d_ij.p);
       MVGX_HIP(hipGetLastError());
       const size_t old = c->res_ij.size();
       c->res_ij.resize(old + (size_t)total * 2);
@@ -842,7 +774,7 @@ int bf_create_as(int kind, int device, Ctx** out) {
   *out = nullptr;
   Ctx* c = new Ctx();
   const int rc = bf_create(kind, device, c);
-  if (rc) { bf_release(c); delete c; return rc; }
+  if (rc) { delete c; return rc; }
   *out = c;
   return MVGX_OK;
 }
@@ -852,7 +784,7 @@ int bf_create_as(int kind, int device, Ctx** out) {
 extern "C" {
 
 int mvgx_hamming_create(int device, mvgx_hamming_ctx** out) { return bf_create_as(0, device, out); }
-int mvgx_hamming_destroy(mvgx_hamming_ctx* c) { if (c) { bf_release(c); delete c; } return MVGX_OK; }
+int mvgx_hamming_destroy(mvgx_hamming_ctx* c) { delete c; return MVGX_OK; }
 int mvgx_hamming_set_option(mvgx_hamming_ctx* c, const char* key, int64_t value) { return bf_set_option(c, key, value); }
 
 int mvgx_hamming_set_regions(mvgx_hamming_ctx* c, const uint8_t* const* desc_rows, const uint32_t* n_desc, uint32_t n_images,
@@ -875,7 +807,7 @@ int mvgx_hamming_results(mvgx_hamming_ctx* c, const uint64_t** offsets, const ui
 }
 
 int mvgx_l2f_create(int device, mvgx_l2f_ctx** out) { return bf_create_as(1, device, out); }
-int mvgx_l2f_destroy(mvgx_l2f_ctx* c) { if (c) { bf_release(c); delete c; } return MVGX_OK; }
+int mvgx_l2f_destroy(mvgx_l2f_ctx* c) { delete c; return MVGX_OK; }
 int mvgx_l2f_set_option(mvgx_l2f_ctx* c, const char* key, int64_t value) { return bf_set_option(c, key, value); }
 
 int mvgx_l2f_set_regions(mvgx_l2f_ctx* c, const float* const* desc_rows, const uint32_t* n_desc, uint32_t n_images, uint32_t dim) {
@@ -897,7 +829,7 @@ int mvgx_l2f_results(mvgx_l2f_ctx* c, const uint64_t** offsets, const uint32_t**
 }
 
 int mvgx_l2u8_create(int device, mvgx_l2u8_ctx** out) { return bf_create_as(2, device, out); }
-int mvgx_l2u8_destroy(mvgx_l2u8_ctx* c) { if (c) { bf_release(c); delete c; } return MVGX_OK; }
+int mvgx_l2u8_destroy(mvgx_l2u8_ctx* c) { delete c; return MVGX_OK; }
 int mvgx_l2u8_set_option(mvgx_l2u8_ctx* c, const char* key, int64_t value) { return bf_set_option(c, key, value); }
 
 int mvgx_l2u8_set_regions(mvgx_l2u8_ctx* c, const uint8_t* const* desc_rows, const uint32_t* n_desc, uint32_t n_images, uint32_t dim) {
@@ -920,7 +852,7 @@ int mvgx_l2u8_results(mvgx_l2u8_ctx* c, const uint64_t** offsets, const uint32_t
 }
 
 int mvgx_cascade_create(int device, mvgx_cascade_ctx** out) { return bf_create_as(3, device, out); }
-int mvgx_cascade_destroy(mvgx_cascade_ctx* c) { if (c) { bf_release(c); delete c; } return MVGX_OK; }
+int mvgx_cascade_destroy(mvgx_cascade_ctx* c) { delete c; return MVGX_OK; }
 int mvgx_cascade_set_option(mvgx_cascade_ctx* c, const char* key, int64_t value) { return bf_set_option(c, key, value); }
 
 }  // extern "C"
@@ -990,16 +922,16 @@ int cas_build_buckets(BfCtx* c, const uint4* bids, const uint32_t* n_desc, uint3
 const std::vector<float>& cas_projections(uint32_t dim, uint32_t groups, uint32_t bits, uint32_t seed) {
   struct Entry { uint32_t dim, groups, bits, seed; std::vector<float> P; };
   static std::mutex mu;
-  static std::vector<Entry*> cache;   // never freed: a handful of parameter sets per process
+  static std::deque<Entry> cache;   // a handful of parameter sets per process; a deque: the references handed out stay valid
   std::lock_guard<std::mutex> lk(mu);
-  for (Entry* e : cache) if (e->dim == dim && e->groups == groups && e->bits == bits && e->seed == seed) return e->P;
-  Entry* e = new Entry{dim, groups, bits, seed, {}};
-  e->P.resize(((size_t)dim + (size_t)groups * bits) * dim);
+  for (Entry& e : cache) if (e.dim == dim && e.groups == groups && e.bits == bits && e.seed == seed) return e.P;
+  cache.push_back(Entry{dim, groups, bits, seed, {}});
+  Entry& e = cache.back();
+  e.P.resize(((size_t)dim + (size_t)groups * bits) * dim);
   std::mt19937 gen(seed);
   std::normal_distribution<> nd(0, 1);
-  for (float& v : e->P) v = (float)nd(gen);
-  cache.push_back(e);
-  return e->P;
+  for (float& v : e.P) v = (float)nd(gen);
+  return e.P;
 }
 }  // namespace
 
@@ -1052,11 +984,12 @@ int mvgx_debug_rounded_ops_f32(const float* abc, float* out) {
   MVGX_REQUIRE(abc && out, MVGX_ERR_ARG, "mvgx_debug_rounded_ops_f32: NULL argument");
   int rc = mvgx::select_device(-1);
   if (rc) return rc;
-  Buf<float> din, dout;
-  struct Release { Buf<float>&a, &b; ~Release() { a.release(); b.release(); } } release{din, dout};
+  DevBuf<float> din, dout;
   if ((rc = din.ensure(3)) || (rc = dout.ensure(2))) return rc;
   MVGX_HIP(hipMemcpy(din.p, abc, 3 * sizeof(float), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(cas_rounded_ops_debug_kernel, dim3(1), dim3(1), 0, nullptr, (const float*)din.p, dout.p);
+  const float* pin = din.p;   // (a launch is handed raw pointers: the test-suite's emulation captures launch arguments by value)
+  float* pout = dout.p;
+  hipLaunchKernelGGL(cas_rounded_ops_debug_kernel, dim3(1), dim3(1), 0, nullptr, pin, pout);
   MVGX_HIP(hipGetLastError());
   MVGX_HIP(hipStreamSynchronize(nullptr));
   MVGX_HIP(hipMemcpy(out, dout.p, 2 * sizeof(float), hipMemcpyDeviceToHost));
@@ -1078,11 +1011,11 @@ int mvgx_cascade_hash_regions_typed(mvgx_cascade_ctx* c, int scalar_type, const 
   for (uint32_t k = 0; k < n_images; ++k) rows += n_desc[k];
   const uint32_t HW = (dim + 31) / 32, HS = HW <= 2 ? 2 : HW <= 4 ? 4 : 8;   // code dwords, slot dwords (cascade_match_kernel)
   const std::vector<float>& P = cas_projections(dim, n_groups, bits_per_bucket, random_seed);
-  Buf<float> d_P, d_zm;
+  DevBuf<float> d_P, d_zm;
+  d_P.headroom_quarter = d_zm.headroom_quarter = true;
   const size_t hash_u4 = ((size_t)std::max<uint64_t>(rows, 1) * HS + 4 + 3) / 4;
   if ((rc = d_P.ensure(P.size())) || (rc = d_zm.ensure(dim)) || (rc = c->d_hash.ensure(hash_u4)) || (rc = c->d_bids.ensure((size_t)std::max<uint64_t>(rows, 1))))
     return rc;
-  struct Release { Buf<float>&a, &b; ~Release() { a.release(); b.release(); } } release{d_P, d_zm};
   MVGX_HIP(hipMemcpyAsync(d_P.p, P.data(), P.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   MVGX_HIP(hipMemcpyAsync(d_zm.p, zero_mean, dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
   std::vector<uint4> bids((size_t)std::max<uint64_t>(rows, 1));
@@ -1090,13 +1023,14 @@ int mvgx_cascade_hash_regions_typed(mvgx_cascade_ctx* c, int scalar_type, const 
   if (rows) {
     const dim3 grid((unsigned)((rows + 255) / 256));
     uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->d_hash.p);
+    const float *pP = d_P.p, *pzm = d_zm.p;   // (raw pointers: the test-suite's emulation captures launch arguments by value)
     if (!is_float && dim == 128)
-      hipLaunchKernelGGL(cascade_hash_kernel, grid, dim3(256), 0, c->stream, c->d_words.p, rows, d_zm.p, d_P.p, (int)n_groups, (int)bits_per_bucket, c->d_hash.p, c->d_bids.p);
+      hipLaunchKernelGGL(cascade_hash_kernel, grid, dim3(256), 0, c->stream, c->d_words.p, rows, pzm, pP, (int)n_groups, (int)bits_per_bucket, c->d_hash.p, c->d_bids.p);
     else if (!is_float)   // 144
-      hipLaunchKernelGGL((cascade_hash_typed_kernel<144, 16, false>), grid, dim3(256), 0, c->stream, c->d_words.p, rows, d_zm.p, d_P.p, (int)n_groups,
+      hipLaunchKernelGGL((cascade_hash_typed_kernel<144, 16, false>), grid, dim3(256), 0, c->stream, c->d_words.p, rows, pzm, pP, (int)n_groups,
                          (int)bits_per_bucket, h32, c->d_bids.p);
     else                  // 64 floats
-      hipLaunchKernelGGL((cascade_hash_typed_kernel<64, 64, true>), grid, dim3(256), 0, c->stream, c->d_words.p, rows, d_zm.p, d_P.p, (int)n_groups,
+      hipLaunchKernelGGL((cascade_hash_typed_kernel<64, 64, true>), grid, dim3(256), 0, c->stream, c->d_words.p, rows, pzm, pP, (int)n_groups,
                          (int)bits_per_bucket, h32, c->d_bids.p);
     MVGX_HIP(hipGetLastError());
     MVGX_HIP(hipMemcpyAsync(bids.data(), c->d_bids.p, rows * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));

@@ -1,4 +1,6 @@
-// Shared host-side helpers for libmvgx_hip.so (error plumbing, HIP call checking).
+// Shared host-side helpers for libmvgx_hip.so: error plumbing and HIP call checking, device selection, the stream cache with the guards
+// that hand a stream / a pair of events back on scope exit, and the slab arenas (device and page-locked host) behind the contexts.
+// Growable buffers that own their memory: mvgx_buffers.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -42,6 +44,10 @@ hipError_t device_malloc(void** p, size_t bytes);
 // SfM engine creates a context per Adjust call); release_stream takes back a stream that has been synchronised.
 int acquire_stream(hipStream_t* out);
 void release_stream(int device, hipStream_t s);
+// On scope exit: drains the stream, then hands it back. Declare it AFTER the Arena whose memory the stream's kernels use - destroyed
+// before it, so the slabs return to the process-wide cache only once nothing enqueued here can still write them.
+struct StreamGuard { int device; hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); release_stream(device, s); } };
+struct EventGuard { hipEvent_t a, b; ~EventGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } };
 
 // MVGX_DEVICES: "all" or a comma-separated list of device ordinals (an ordinal may repeat: several contexts on one device,
 // used by the single-GPU tests of the multi-device paths). Unset / empty -> `out` stays empty (the current device).

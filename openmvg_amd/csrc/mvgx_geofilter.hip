@@ -37,6 +37,7 @@
 #include <thread>
 #include <vector>
 
+#include "mvgx_buffers.h"
 #include "mvgx_common.h"
 
 namespace {
@@ -1070,11 +1071,9 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { MVGX_HIP(mvgx::device_malloc(&p, std::max<size_t>(bytes, 16))); return MVGX_OK; }
-};
+using ByteBuf = mvgx::DevBuf<unsigned char>;   // sized in bytes
+// every buffer of a call exists, an empty one too: 16 bytes at the least, as ever
+int alloc(ByteBuf& b, size_t bytes) { return b.ensure(std::max<size_t>(bytes, 1)); }
 
 template <int WAVES, int MODEL>
 int launch_class(const GeoPair* d_pairs, const uint32_t* d_order, uint32_t n_work, uint32_t n_cap, const double2* x1, const double2* x2,
@@ -1151,12 +1150,12 @@ inline void inverse3(const double* m, double* inv) {
 // slower per iteration than it does in the global form, call r5_61.)
 template <int MODEL>
 int launch_classes(const GeoPair* d_pairs, const uint32_t* ord, const std::vector<uint32_t>& order, uint32_t c_global, uint32_t cap0, uint64_t n_total, uint64_t n_pairs,
-                   const double2* px1, const double2* px2, const float* l10, const uint32_t* mt, uint32_t max_it, GeoResult* res, uint8_t* mask, DevBuf& d_tables,
+                   const double2* px1, const double2* px2, const float* l10, const uint32_t* mt, uint32_t max_it, GeoResult* res, uint8_t* mask, ByteBuf& d_tables,
                    hipStream_t stream, const double* b1 = nullptr, const double* b2 = nullptr, uint32_t ahead = 1) {
   int rc;
   if (c_global) {
-    if ((rc = d_tables.alloc(3 * ((size_t)n_total + 4 * (size_t)n_pairs + 4) * sizeof(uint32_t)))) return rc;
-    if ((rc = launch_class_global<MODEL>(d_pairs, ord, c_global, 0, px1, px2, l10, mt, max_it, res, mask, static_cast<uint32_t*>(d_tables.p), stream, b1, b2, ahead))) return rc;
+    if ((rc = alloc(d_tables, 3 * ((size_t)n_total + 4 * (size_t)n_pairs + 4) * sizeof(uint32_t)))) return rc;
+    if ((rc = launch_class_global<MODEL>(d_pairs, ord, c_global, 0, px1, px2, l10, mt, max_it, res, mask, reinterpret_cast<uint32_t*>(d_tables.p), stream, b1, b2, ahead))) return rc;
   }
   return launch_class<4, MODEL>(d_pairs, ord + c_global, (uint32_t)order.size() - c_global, cap0, px1, px2, l10, mt, max_it, res, mask, stream, b1, b2, ahead);
 }
@@ -1313,30 +1312,30 @@ int geofilter_run(int device, int model, const GeoSource& src, const uint64_t* m
   if ((rc = mvgx::acquire_stream(&stream))) return rc;
   int stream_device = 0;
   MVGX_HIP(hipGetDevice(&stream_device));
-  struct StreamGuard { int dev; hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); mvgx::release_stream(dev, s); } } sg{stream_device, stream};
-  DevBuf d_pairs, d_order, d_x1, d_x2, d_l10, d_mt, d_res, d_mask, d_raw1, d_raw2, d_norm, d_feat, d_fstart, d_pimg, d_b1, d_b2, d_fbear;
+  mvgx::StreamGuard sg{stream_device, stream};
+  ByteBuf d_pairs, d_order, d_x1, d_x2, d_l10, d_mt, d_res, d_mask, d_raw1, d_raw2, d_norm, d_feat, d_fstart, d_pimg, d_b1, d_b2, d_fbear;
   const uint64_t n_feat = src.indexed && src.n_images ? src.feat_start[src.n_images] : 0;
   const uint64_t n_xy = angular ? 0 : n_total;   // (the angular models never touch pixel positions)
-  if ((rc = d_pairs.alloc(n_pairs * sizeof(GeoPair))) || (rc = d_order.alloc(order.size() * sizeof(uint32_t))) || (rc = d_x1.alloc(n_xy * sizeof(double2))) ||
-      (rc = d_x2.alloc(n_xy * sizeof(double2))) || (rc = d_l10.alloc(l10.size() * sizeof(float))) || (rc = d_mt.alloc(sizeof(mt_init))) ||
-      (rc = d_res.alloc(n_pairs * sizeof(GeoResult))) || (rc = d_mask.alloc(n_total)) || (rc = d_norm.alloc(norm_size * sizeof(double))))
+  if ((rc = alloc(d_pairs, n_pairs * sizeof(GeoPair))) || (rc = alloc(d_order, order.size() * sizeof(uint32_t))) || (rc = alloc(d_x1, n_xy * sizeof(double2))) ||
+      (rc = alloc(d_x2, n_xy * sizeof(double2))) || (rc = alloc(d_l10, l10.size() * sizeof(float))) || (rc = alloc(d_mt, sizeof(mt_init))) ||
+      (rc = alloc(d_res, n_pairs * sizeof(GeoResult))) || (rc = alloc(d_mask, n_total)) || (rc = alloc(d_norm, norm_size * sizeof(double))))
     return rc;
   if (src.indexed) {   // d_raw1: the index pairs
-    if ((rc = d_raw1.alloc(n_total * sizeof(uint2))) || (rc = d_feat.alloc((angular ? 0 : n_feat) * sizeof(double2))) ||
-        (rc = d_fstart.alloc(((size_t)src.n_images + 1) * sizeof(uint64_t))) || (rc = d_pimg.alloc(n_pairs * sizeof(uint2))))
+    if ((rc = alloc(d_raw1, n_total * sizeof(uint2))) || (rc = alloc(d_feat, (angular ? 0 : n_feat) * sizeof(double2))) ||
+        (rc = alloc(d_fstart, ((size_t)src.n_images + 1) * sizeof(uint64_t))) || (rc = alloc(d_pimg, n_pairs * sizeof(uint2))))
       return rc;
-  } else if ((rc = d_raw1.alloc(n_xy * sizeof(double2))) || (rc = d_raw2.alloc(n_xy * sizeof(double2)))) {
+  } else if ((rc = alloc(d_raw1, n_xy * sizeof(double2))) || (rc = alloc(d_raw2, n_xy * sizeof(double2)))) {
     return rc;
   }
   if (bearings) {
-    if ((rc = d_b1.alloc(n_total * 3 * sizeof(double))) || (rc = d_b2.alloc(n_total * 3 * sizeof(double)))) return rc;
-    if (src.indexed && (rc = d_fbear.alloc(n_feat * 3 * sizeof(double)))) return rc;
+    if ((rc = alloc(d_b1, n_total * 3 * sizeof(double))) || (rc = alloc(d_b2, n_total * 3 * sizeof(double)))) return rc;
+    if (src.indexed && (rc = alloc(d_fbear, n_feat * 3 * sizeof(double)))) return rc;
   }
   mark(0);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   MVGX_HIP(hipEventCreate(&e0));
   MVGX_HIP(hipEventCreate(&e1));
-  struct EventGuard { hipEvent_t a, b; ~EventGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } eg{e0, e1};
+  mvgx::EventGuard eg{e0, e1};
   if (n_pairs) MVGX_HIP(hipMemcpyAsync(d_pairs.p, hp, n_pairs * sizeof(GeoPair), hipMemcpyHostToDevice, stream));
   if (!order.empty()) MVGX_HIP(hipMemcpyAsync(d_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   if (n_total) {
@@ -1365,22 +1364,22 @@ int geofilter_run(int device, int model, const GeoSource& src, const uint64_t* m
   if (n_pairs) MVGX_HIP(hipMemsetAsync(d_res.p, 0, n_pairs * sizeof(GeoResult), stream));
   MVGX_HIP(hipEventRecord(e0, stream));
   mark(1);
-  const uint32_t* ord = static_cast<const uint32_t*>(d_order.p);
-  const auto* px1 = static_cast<const double2*>(d_x1.p);
-  const auto* px2 = static_cast<const double2*>(d_x2.p);
+  const uint32_t* ord = reinterpret_cast<const uint32_t*>(d_order.p);
+  const auto* px1 = reinterpret_cast<const double2*>(d_x1.p);
+  const auto* px2 = reinterpret_cast<const double2*>(d_x2.p);
   if (n_total) {   // (plain pointers in the launch: the buffers own their memory and must not be captured by value)
-    const auto* pp = static_cast<const GeoPair*>(d_pairs.p);
-    const auto* pn = static_cast<const double*>(d_norm.p);
-    const auto *r1 = static_cast<const double2*>(d_raw1.p), *r2 = static_cast<const double2*>(d_raw2.p);
-    auto *o1 = static_cast<double2*>(d_x1.p), *o2 = static_cast<double2*>(d_x2.p);
+    const auto* pp = reinterpret_cast<const GeoPair*>(d_pairs.p);
+    const auto* pn = reinterpret_cast<const double*>(d_norm.p);
+    const auto *r1 = reinterpret_cast<const double2*>(d_raw1.p), *r2 = reinterpret_cast<const double2*>(d_raw2.p);
+    auto *o1 = reinterpret_cast<double2*>(d_x1.p), *o2 = reinterpret_cast<double2*>(d_x2.p);
     if (src.indexed) {
-      const auto* ft = static_cast<const double2*>(d_feat.p);
-      const auto* fs = static_cast<const uint64_t*>(d_fstart.p);
-      const auto *pim = static_cast<const uint2*>(d_pimg.p), *mij = static_cast<const uint2*>(d_raw1.p);
+      const auto* ft = reinterpret_cast<const double2*>(d_feat.p);
+      const auto* fs = reinterpret_cast<const uint64_t*>(d_fstart.p);
+      const auto *pim = reinterpret_cast<const uint2*>(d_pimg.p), *mij = reinterpret_cast<const uint2*>(d_raw1.p);
       if (!angular) hipLaunchKernelGGL(geofilter_normalize_indexed_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, pp, pn, (uint32_t)n_pairs, ft, fs, pim, mij, o1, o2);
       if (bearings) {
-        const double* fb = static_cast<const double*>(d_fbear.p);
-        double *ob1 = static_cast<double*>(d_b1.p), *ob2 = static_cast<double*>(d_b2.p);
+        const double* fb = reinterpret_cast<const double*>(d_fbear.p);
+        double *ob1 = reinterpret_cast<double*>(d_b1.p), *ob2 = reinterpret_cast<double*>(d_b2.p);
         hipLaunchKernelGGL(geofilter_gather_bearings_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, pp, (uint32_t)n_pairs, fb, fs, pim, mij, ob1, ob2);
       }
     } else if (!angular) {
@@ -1388,25 +1387,25 @@ int geofilter_run(int device, int model, const GeoSource& src, const uint64_t* m
     }
     MVGX_HIP(hipGetLastError());
   }
-  DevBuf d_tables;
+  ByteBuf d_tables;
   {
     // fundamental / homography / essential models: samples drawn and solved ahead of their iterations, four side by side (1: one minimal solve per
     // iteration, the form of rounds 3-4; results equal)
     uint32_t e_ahead = kAhead;
     if (const char* env = getenv("MVGX_GEO_AHEAD")) e_ahead = (uint32_t)std::min(kAhead, std::max(1, atoi(env)));
     else if (const char* env2 = getenv("MVGX_GEO_E_AHEAD")) e_ahead = (uint32_t)std::min(kAhead, std::max(1, atoi(env2)));
-    auto* dp = static_cast<const GeoPair*>(d_pairs.p);
-    auto* dl = static_cast<const float*>(d_l10.p);
-    auto* dm = static_cast<const uint32_t*>(d_mt.p);
-    auto* dr = static_cast<GeoResult*>(d_res.p);
-    auto* dk = static_cast<uint8_t*>(d_mask.p);
-    const double *pb1 = static_cast<const double*>(d_b1.p), *pb2 = static_cast<const double*>(d_b2.p);
+    auto* dp = reinterpret_cast<const GeoPair*>(d_pairs.p);
+    auto* dl = reinterpret_cast<const float*>(d_l10.p);
+    auto* dm = reinterpret_cast<const uint32_t*>(d_mt.p);
+    auto* dr = reinterpret_cast<GeoResult*>(d_res.p);
+    auto* dk = reinterpret_cast<uint8_t*>(d_mask.p);
+    const double *pb1 = reinterpret_cast<const double*>(d_b1.p), *pb2 = reinterpret_cast<const double*>(d_b2.p);
     rc = model == kModelH ? launch_classes<kModelH>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, nullptr, nullptr, e_ahead)
          : model == kModelEO ? launch_classes<kModelEO>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream)
          : model == kModelEA8 ? launch_classes<kModelEA8>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, pb1, pb2)
          : model == kModelEU3 ? launch_classes<kModelEU3>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, pb1, pb2)
          : model == kModelE ? launch_classes<kModelE>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream,
-                                                      static_cast<const double*>(d_b1.p), static_cast<const double*>(d_b2.p), e_ahead)
+                                                      reinterpret_cast<const double*>(d_b1.p), reinterpret_cast<const double*>(d_b2.p), e_ahead)
                             : launch_classes<kModelF>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, nullptr, nullptr, e_ahead);
     if (rc) return rc;
   }
@@ -1579,12 +1578,12 @@ int mvgx_debug_rounded_ops(const double* abc, double* out) {
   MVGX_REQUIRE(abc && out, MVGX_ERR_ARG, "mvgx_debug_rounded_ops: NULL argument");
   int rc = mvgx::select_device(-1);
   if (rc) return rc;
-  DevBuf din, dout;
-  if ((rc = din.alloc(3 * sizeof(double))) || (rc = dout.alloc(2 * sizeof(double)))) return rc;
+  ByteBuf din, dout;
+  if ((rc = alloc(din, 3 * sizeof(double))) || (rc = alloc(dout, 2 * sizeof(double)))) return rc;
   MVGX_HIP(hipMemcpy(din.p, abc, 3 * sizeof(double), hipMemcpyHostToDevice));
   {
-    const double* pi = static_cast<const double*>(din.p);
-    double* po = static_cast<double*>(dout.p);
+    const double* pi = reinterpret_cast<const double*>(din.p);
+    double* po = reinterpret_cast<double*>(dout.p);
     hipLaunchKernelGGL(rounded_ops_debug_kernel, dim3(1), dim3(1), 0, nullptr, pi, po);
   }
   MVGX_HIP(hipGetLastError());
@@ -1633,15 +1632,15 @@ int mvgx_debug_five_point(const double* b1, const double* b2, double* Es_out, in
   MVGX_REQUIRE(b1 && b2 && Es_out && n_out, MVGX_ERR_ARG, "mvgx_debug_five_point: NULL argument");
   int rc = mvgx::select_device(-1);
   if (rc) return rc;
-  DevBuf d1, d2, dE, dn;
-  if ((rc = d1.alloc(15 * sizeof(double))) || (rc = d2.alloc(15 * sizeof(double))) || (rc = dE.alloc(90 * sizeof(double))) || (rc = dn.alloc(sizeof(int)))) return rc;
+  ByteBuf d1, d2, dE, dn;
+  if ((rc = alloc(d1, 15 * sizeof(double))) || (rc = alloc(d2, 15 * sizeof(double))) || (rc = alloc(dE, 90 * sizeof(double))) || (rc = alloc(dn, sizeof(int)))) return rc;
   MVGX_HIP(hipMemcpy(d1.p, b1, 15 * sizeof(double), hipMemcpyHostToDevice));
   MVGX_HIP(hipMemcpy(d2.p, b2, 15 * sizeof(double), hipMemcpyHostToDevice));
   MVGX_HIP(hipMemset(dE.p, 0, 90 * sizeof(double)));
   {   // (plain pointers in the launch: the buffers own their memory and must not be captured by value)
-    const double *p1 = static_cast<const double*>(d1.p), *p2 = static_cast<const double*>(d2.p);
-    double* pE = static_cast<double*>(dE.p);
-    int* pn = static_cast<int*>(dn.p);
+    const double *p1 = reinterpret_cast<const double*>(d1.p), *p2 = reinterpret_cast<const double*>(d2.p);
+    double* pE = reinterpret_cast<double*>(dE.p);
+    int* pn = reinterpret_cast<int*>(dn.p);
     hipLaunchKernelGGL(five_point_debug_kernel, dim3(1), dim3(64), 0, nullptr, p1, p2, pE, pn);
   }
   MVGX_HIP(hipGetLastError());
@@ -1656,15 +1655,15 @@ int mvgx_debug_five_point4(const double* b1, const double* b2, double* Es_out, i
   MVGX_REQUIRE(b1 && b2 && Es_out && n_out, MVGX_ERR_ARG, "mvgx_debug_five_point4: NULL argument");
   int rc = mvgx::select_device(-1);
   if (rc) return rc;
-  DevBuf d1, d2, dE, dn;
-  if ((rc = d1.alloc(60 * sizeof(double))) || (rc = d2.alloc(60 * sizeof(double))) || (rc = dE.alloc(360 * sizeof(double))) || (rc = dn.alloc(4 * sizeof(int)))) return rc;
+  ByteBuf d1, d2, dE, dn;
+  if ((rc = alloc(d1, 60 * sizeof(double))) || (rc = alloc(d2, 60 * sizeof(double))) || (rc = alloc(dE, 360 * sizeof(double))) || (rc = alloc(dn, 4 * sizeof(int)))) return rc;
   MVGX_HIP(hipMemcpy(d1.p, b1, 60 * sizeof(double), hipMemcpyHostToDevice));
   MVGX_HIP(hipMemcpy(d2.p, b2, 60 * sizeof(double), hipMemcpyHostToDevice));
   MVGX_HIP(hipMemset(dE.p, 0, 360 * sizeof(double)));
   {
-    const double *p1 = static_cast<const double*>(d1.p), *p2 = static_cast<const double*>(d2.p);
-    double* pE = static_cast<double*>(dE.p);
-    int* pn = static_cast<int*>(dn.p);
+    const double *p1 = reinterpret_cast<const double*>(d1.p), *p2 = reinterpret_cast<const double*>(d2.p);
+    double* pE = reinterpret_cast<double*>(dE.p);
+    int* pn = reinterpret_cast<int*>(dn.p);
     hipLaunchKernelGGL(five_point4_debug_kernel, dim3(1), dim3(64), 0, nullptr, p1, p2, pE, pn);
   }
   MVGX_HIP(hipGetLastError());

@@ -322,7 +322,7 @@ int mvgx_guided_match(int device, const double* feat_xy, const void* desc, int d
   if ((rc = mvgx::acquire_stream(&stream))) return rc;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  struct StreamGuard { int d; hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); mvgx::release_stream(d, s); } } guard{dev, stream};
+  mvgx::StreamGuard guard{dev, stream};
 
   const int DW = (int)desc_bytes / 4;
   DevArray<double2> d_xy; DevArray<uint32_t> d_desc; DevArray<int> d_norm; DevArray<uint64_t> d_fs, d_ls, d_ms; DevArray<uint32_t> d_pairs, d_best, d_count, d_ij;
@@ -347,7 +347,7 @@ int mvgx_guided_match(int device, const double* feat_xy, const void* desc, int d
   hipEvent_t e0 = nullptr, e1 = nullptr;
   MVGX_HIP(hipEventCreate(&e0));
   MVGX_HIP(hipEventCreate(&e1));
-  struct EventGuard { hipEvent_t a, b; ~EventGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } eguard{e0, e1};
+  mvgx::EventGuard eguard{e0, e1};
   MVGX_HIP(hipEventRecord(e0, stream));
   if (n_feat && desc_type == MVGX_DESC_U8) {
     const unsigned nb = (unsigned)((n_feat + 255) / 256);

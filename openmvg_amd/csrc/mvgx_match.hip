@@ -57,10 +57,14 @@
 #include <thread>
 #include <vector>
 
+#include "mvgx_buffers.h"
 #include "mvgx_common.h"
+#include "mvgx_match_batch.h"
 
 namespace {
 
+using mvgx::DevBuf;
+using mvgx::PinnedBuf;
 using mvgx::set_error;
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -79,7 +83,6 @@ constexpr int kStageBytes = kWinTiles * kTileBytes + kWinTiles * kTileRows * 4; 
 constexpr int kRPad = INT_MIN + 512;
 constexpr int kCPad = -(1 << 27);             // accumulator init of pad slots (real values are > -2^22)
 constexpr int kNegInit = -(1 << 28);          // "no value yet" for running maxima; 2 * kNegInit - 1 fits int32
-constexpr uint32_t kNoMatch = 0xFFFFFFFFu;
 constexpr int kTailTiles = 16;                // slack tiles after the last image (query over-read)
 
 struct MatchParams {
@@ -1438,112 +1441,7 @@ __global__ __launch_bounds__(256) void l2_top2_ratio_naive_kernel(MatchParams p)
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// compaction: exclusive scan of per-pair counts, then ordered (ascending j) gather of the accepted queries
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void scan_counts_kernel(const uint32_t* __restrict__ count, uint32_t n,
-                                                           uint32_t* __restrict__ offsets /* n+1 */) {
-  __shared__ uint32_t s_part[1024];
-  const uint32_t per = (n + 1023) / 1024;
-  const uint32_t lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
-  uint32_t sum = 0;
-  for (uint32_t i = lo; i < hi; ++i) sum += count[i];
-  s_part[threadIdx.x] = sum;
-  __syncthreads();
-  // Hillis-Steele inclusive scan over 1024 partials
-  for (uint32_t d = 1; d < 1024; d <<= 1) {
-    const uint32_t v = (threadIdx.x >= d) ? s_part[threadIdx.x - d] : 0;
-    __syncthreads();
-    s_part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint32_t run = s_part[threadIdx.x] - sum;
-  for (uint32_t i = lo; i < hi; ++i) { offsets[i] = run; run += count[i]; }
-  if (threadIdx.x == 1023) offsets[n] = s_part[1023];
-}
-
-__global__ __launch_bounds__(256) void compact_matches_kernel(const uint32_t* __restrict__ best,
-                                                              const uint32_t* __restrict__ offsets,
-                                                              const uint2* __restrict__ pairs,
-                                                              const uint32_t* __restrict__ img_n,
-                                                              const uint64_t* __restrict__ img_row_off,
-                                                              const uint32_t* __restrict__ rowpos,
-                                                              uint32_t n_pairs, uint32_t qstride,
-                                                              uint2* __restrict__ out_ij) {
-  const uint32_t pidx = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per image pair
-  if (pidx >= n_pairs) return;
-  const int lane = threadIdx.x & 63;
-  const uint32_t off = offsets[pidx];
-  if (offsets[pidx + 1] == off) return;
-  const uint32_t J = pairs[pidx].y;
-  const uint32_t nJ = img_n[J];
-  // original query row -> slot (best[] is slot-indexed); no table: the dense query slots of l2_filter16_kernel, slot = row
-  const uint32_t* pos = rowpos ? rowpos + img_row_off[J] : nullptr;
-  uint32_t run = off;
-  for (uint32_t q0 = 0; q0 < nJ; q0 += 64) {
-    const uint32_t q = q0 + lane;
-    const uint32_t v = (q < nJ) ? best[(size_t)pidx * qstride + (pos ? pos[q] : q)] : kNoMatch;
-    const bool ok = v != kNoMatch;
-    const unsigned long long m = __ballot(ok);
-    if (ok) {
-      const uint32_t pre = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      out_ij[run + pre] = make_uint2(v, q);
-    }
-    run += (uint32_t)__popcll(m);
-  }
-}
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;  // elements
-  int ensure(size_t n) {
-    if (n <= cap) return MVGX_OK;
-    if (p) { MVGX_HIP(hipFree(p)); p = nullptr; cap = 0; }
-    const size_t want = std::max<size_t>(n, 16);
-    MVGX_HIP(mvgx::device_malloc(reinterpret_cast<void**>(&p), want * sizeof(T)));
-    cap = want;
-    return MVGX_OK;
-  }
-  void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
-};
-
-template <typename T>
-struct PinnedBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t n) {
-    if (n <= cap) return MVGX_OK;
-    if (p) { MVGX_HIP(hipHostFree(p)); p = nullptr; cap = 0; }
-    const size_t want = std::max<size_t>(n, 16);
-    MVGX_HIP(hipHostMalloc(reinterpret_cast<void**>(&p), want * sizeof(T), hipHostMallocDefault));
-    cap = want;
-    return MVGX_OK;
-  }
-  bool pageable = false;   // true: plain malloc'd memory (cheap to obtain; D2H copies are staged by the runtime)
-  // grow to at least n elements, keeping the first `used` (geometric growth: the caller appends batch after batch)
-  int grow_keep(size_t n, size_t used) {
-    if (n <= cap) return MVGX_OK;
-    const size_t want = std::max<size_t>(std::max<size_t>(n, cap + cap / 2), 16);
-    if (pageable) {
-      T* q = static_cast<T*>(realloc(p, want * sizeof(T)));
-      MVGX_REQUIRE(q != nullptr, MVGX_ERR_HIP, "out of host memory (%zu bytes)", want * sizeof(T));
-      p = q;
-      cap = want;
-      return MVGX_OK;
-    }
-    T* q = nullptr;
-    MVGX_HIP(hipHostMalloc(reinterpret_cast<void**>(&q), want * sizeof(T), hipHostMallocDefault));
-    if (p) {
-      if (used) memcpy(q, p, used * sizeof(T));
-      (void)hipHostFree(p);
-    }
-    p = q;
-    cap = want;
-    return MVGX_OK;
-  }
-  void release() { if (p) { if (pageable) free(p); else (void)hipHostFree(p); p = nullptr; cap = 0; } }
-};
+// (the compaction that follows - scan_counts_kernel, compact_matches_kernel - is shared with the other matchers: mvgx_match_batch.h)
 
 }  // namespace
 
@@ -1918,22 +1816,13 @@ int mvgx_match_destroy(mvgx_match_ctx* c) {
   if (!c) return MVGX_OK;
   if (!c->children.empty()) {
     for (mvgx_match_ctx* child : c->children) mvgx_match_destroy(child);
-    for (auto& r : c->results) r.ij.release();
-    delete c;
+    delete c;   // (a parent owns no device state: its result lists are host memory)
     return MVGX_OK;
   }
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  c->d_rows.release(); c->d_tiles.release(); c->d_rconst.release(); c->d_qnorm.release();
-  c->d_rows_slot.release(); c->d_cinit.release(); c->d_rownorm.release(); c->d_ntiles.release(); c->d_perm.release(); c->d_rowpos.release();
-  c->d_neven.release(); c->d_err.release(); c->d_qtiles.release(); c->d_qtnorm.release(); c->d_qtile_off.release();
-  c->d_row_off.release(); c->d_tile_off.release(); c->d_n.release();
-  for (auto& r : c->results) r.ij.release();
-  for (auto& sl : c->slot) {
-    sl.d_work8.release(); sl.hp_work8.release(); sl.d_work8h.release(); sl.hp_work8h.release();
-    sl.d_pairs.release(); sl.d_work.release(); sl.d_ij.release(); sl.d_cd.release();
-    sl.d_best.release(); sl.d_count.release(); sl.d_offsets.release();
-    sl.hp_pairs.release(); sl.hp_work.release(); sl.hp_offsets.release(); sl.hp_ij[0].release(); sl.hp_ij[1].release();
+  for (auto& sl : c->slot) {   // (synchronised before its events and stream go; the buffers free themselves with the context)
+    if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     if (sl.ev_copy) (void)hipEventDestroy(sl.ev_copy);
     if (sl.ev_scan) (void)hipEventDestroy(sl.ev_scan);
     if (sl.ev_filter) (void)hipEventDestroy(sl.ev_filter);
@@ -2178,7 +2067,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
             hipLaunchKernelGGL(count_candidates_units_kernel, dim3(n_verify), dim3(256), 0, stream, mp, c->d_err.p + 1);
           else
             hipLaunchKernelGGL(count_candidates_kernel, dim3((unsigned)((nslots + 16383) / 16384)), dim3(256), 0, stream,
-                               sl.d_best.p, nslots, c->d_err.p + 1);
+                               mp.best, nslots, c->d_err.p + 1);
         }
         // the verify stage walks what the filter just wrote, nothing else of best[]
         hipLaunchKernelGGL(form.verify, dim3(n_verify), dim3(256), 0, stream, mp);
@@ -2187,7 +2076,9 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
       if (c->verify_alone) MVGX_HIP(hipEventRecord(sl.ev_filter, stream));
     }
     if (!n_filter) MVGX_HIP(hipEventRecord(sl.ev_filter, stream));
-    hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, stream, sl.d_count.p, nb, sl.d_offsets.p);
+    // (a launch is handed raw pointers, never a Slot or a buffer: the test-suite's emulation captures launch arguments by value)
+    uint32_t* const d_offsets = sl.d_offsets.p;
+    hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, stream, mp.count, nb, d_offsets);
     MVGX_HIP(hipGetLastError());
     MVGX_HIP(hipMemcpyAsync(sl.hp_offsets.p, sl.d_offsets.p, ((size_t)nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     MVGX_HIP(hipEventRecord(sl.ev_scan, stream));
@@ -2212,9 +2103,12 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     st.n_matches += total;
     if (total) {
       if ((rc = sl.d_ij.ensure(total))) return rc;
-      hipLaunchKernelGGL(compact_matches_kernel, dim3((nb + 3) / 4), dim3(256), 0, sl.stream, sl.d_best.p,
-                         sl.d_offsets.p, sl.d_pairs.p, c->d_n.p, c->d_row_off.p, form.dense_slots ? nullptr : c->d_rowpos.p, nb, c->qstride,
-                         sl.d_ij.p);
+      hipStream_t stream = sl.stream;
+      const uint32_t *d_best = sl.d_best.p, *d_offsets = sl.d_offsets.p;
+      const uint2* d_pairs = sl.d_pairs.p;
+      uint2* d_ij = sl.d_ij.p;
+      hipLaunchKernelGGL(compact_matches_kernel, dim3((nb + 3) / 4), dim3(256), 0, stream, d_best, d_offsets, d_pairs, c->d_n.p,
+                         c->d_row_off.p, form.dense_slots ? nullptr : c->d_rowpos.p, nb, c->qstride, d_ij);
       MVGX_HIP(hipGetLastError());
       if (sink) {
         PinnedBuf<uint32_t>& hb = sl.hp_ij[sl.out_set];
@@ -2371,20 +2265,13 @@ int check_run_args(mvgx_match_ctx* c, const uint32_t* pairs_IJ, uint64_t n_pairs
   MVGX_REQUIRE(c && (pairs_IJ || n_pairs == 0), MVGX_ERR_ARG, "%s: NULL argument", who);
   const mvgx_match_ctx* r = c->children.empty() ? c : c->children[0];
   MVGX_REQUIRE(r->d_rows_view != nullptr || r->n_images == 0, MVGX_ERR_STATE, "%s before set_regions", who);
-  MVGX_REQUIRE(ratio_sq <= 1.0f && ratio_sq >= 0.0f, MVGX_ERR_UNSUPPORTED,
-               "ratio_sq = %g: the device path reproduces the reference only for 0 <= ratio^2 <= 1 "
-               "(ties are libstdc++ partial_sort order beyond that)", (double)ratio_sq);
-  for (uint64_t k = 0; k < n_pairs; ++k)
-    MVGX_REQUIRE(pairs_IJ[2 * k] < r->n_images && pairs_IJ[2 * k + 1] < r->n_images, MVGX_ERR_ARG,
-                 "pair %llu references image out of range", (unsigned long long)k);
-  return MVGX_OK;
+  const int rc = check_ratio(ratio_sq, "ratio_sq");
+  return rc ? rc : check_pairs_in_range(pairs_IJ, n_pairs, r->n_images, who);
 }
 
-// pairs per batch: the option, capped so that the per-slot scratch (12 B per pair and query slot) stays near 6 GB when the
-// images carry tens of thousands of descriptors
+// pairs per batch (mvgx_match_batch.h) from the option and the query stride of the device contexts
 uint64_t batch_size(const mvgx_match_ctx* c) {
-  const mvgx_match_ctx* r = c->children.empty() ? c : c->children[0];
-  return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->batch_pairs, std::max<uint64_t>(16, (1ull << 29) / std::max<uint32_t>(r->qstride, 1))));
+  return batch_size(c->batch_pairs, (c->children.empty() ? c : c->children[0])->qstride);
 }
 
 }  // namespace

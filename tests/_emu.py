@@ -135,7 +135,8 @@ def build_match(force=False):
     gen = generate_match_source()
     deps = [gen, os.path.join(_SRC, "hipemu.cpp"), os.path.join(_SRC, "hipemu_match.cpp"), os.path.join(_SRC, "hip", "hip_runtime.h"),
             os.path.join(_ROOT, "include", "mvgx.h"), os.path.join(_ROOT, "openmvg_amd", "csrc", "mvgx_common.hip"),
-            os.path.join(_ROOT, "openmvg_amd", "csrc", "mvgx_common.h")]
+            os.path.join(_ROOT, "openmvg_amd", "csrc", "mvgx_common.h"), os.path.join(_ROOT, "openmvg_amd", "csrc", "mvgx_buffers.h"),
+            os.path.join(_ROOT, "openmvg_amd", "csrc", "mvgx_match_batch.h")]
     if not force and os.path.exists(_OUT_MATCH) and all(os.path.getmtime(d) <= os.path.getmtime(_OUT_MATCH) for d in deps):
         return _OUT_MATCH
     cxx = _CLANG if os.path.exists(_CLANG) else "clang++"

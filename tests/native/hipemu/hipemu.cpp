@@ -4,6 +4,7 @@
 #include <ucontext.h>
 
 #include <cstdio>
+#include <memory>
 #include <vector>
 
 namespace hipemu {
@@ -13,10 +14,11 @@ thread_local dim3 g_threadIdx, g_blockIdx, g_blockDim, g_gridDim;   // one emula
 namespace {
 enum State { RUNNABLE, WAIT_WAVE, WAIT_BLOCK, DONE };
 constexpr size_t kStack = 512 * 1024;
+struct FreeStack { void operator()(char* p) const { free(p); } };
 struct Fiber {
   ucontext_t ctx;
   State st = DONE;
-  char* stack = nullptr;
+  std::unique_ptr<char, FreeStack> stack;   // (goes with its thread: a leak checker sees none at exit)
 };
 thread_local std::vector<Fiber> g_fibers;
 thread_local ucontext_t g_sched;
@@ -50,13 +52,13 @@ void run_block(unsigned nthreads) {
   if (g_fibers.size() < nthreads) {
     const size_t old = g_fibers.size();
     g_fibers.resize(nthreads);
-    for (size_t i = old; i < nthreads; ++i) g_fibers[i].stack = static_cast<char*>(malloc(kStack));
+    for (size_t i = old; i < nthreads; ++i) g_fibers[i].stack.reset(static_cast<char*>(malloc(kStack)));
   }
   g_n = (int)nthreads;
   for (int i = 0; i < g_n; ++i) {
     Fiber& f = g_fibers[i];
     getcontext(&f.ctx);
-    f.ctx.uc_stack.ss_sp = f.stack;
+    f.ctx.uc_stack.ss_sp = f.stack.get();
     f.ctx.uc_stack.ss_size = kStack;
     f.ctx.uc_link = &g_sched;
     makecontext(&f.ctx, trampoline, 0);
