@@ -3474,6 +3474,28 @@ int dev_upload_n(mvgx::Arena& pool, T** p, const T* v, size_t n, hipStream_t s) 
 template <typename T>
 int dev_upload(mvgx::Arena& pool, T** p, const std::vector<T>& v, hipStream_t s) { return dev_upload_n(pool, p, v.data(), v.size(), s); }
 
+// Which kernels an LM iteration launches: everything about that which is constant during a solve, resolved once by resolve_step_form
+// (the table of forms is there) when start() has the solver in place. The functions of a step read this and no setting.
+struct StepForm {
+  // Jacobian evaluation and assembly: what runs on the record path (Jacobian records per observation, sums per point) beside the point groups
+  enum Records { kRecordsNone, kRecordsAll, kRecordsUngrouped } records = kRecordsNone;   // observations linearized into records, with ba_obs_z_kernel
+  bool record_points = false;           // some point is in no group: ba_point_norms_kernel, ba_point_solve_kernel
+  bool finish_folds_diag = false;       // after iteration zero ba_gram_finish_kernel also forms the LM diagonal and max |gradient|: no ba_lm_diag_kernel
+  bool assemble_finishes = false;       // ba_schur_assemble_all_kernel applies the LM diagonal (Dev::asm_inv_radius): no ba_finish_system_kernel
+  // reduced solve
+  bool sparse = false;                  // block-sparse tile Cholesky, else the dense one
+  enum Schedule { kLevelByLevel, kLookahead } schedule = kLevelByLevel;
+  int chain_fuse_max_tasks = 0;         // kLevelByLevel: single-column levels with at most this many update tasks run panel + update as one launch
+  enum Sweep { kSweepOneLaunch, kSweepChainThenLevels, kSweepLevels } sweep = kSweepLevels;
+  int sweep_chain_levels = 0;           // kSweepChainThenLevels: the top levels sp_backsolve_chain_kernel walks
+  bool gather_with_cam_sums = false;    // after the sweep: ba_step_scalars_cam_kernel (solution + the camera half of the step's sums), else sp_gather_solution_kernel
+  // back-substitution, candidate and cost
+  enum Candidate { kCandFolded, kCandJacobianModel, kCandStepScalars } candidate = kCandStepScalars;
+  bool backsub_launch = true;           // ba_backsub_kernel runs
+  bool cam_sums_launch = false;         // kCandFolded: ba_step_scalars_cam_kernel has a launch of its own (dense solve)
+  bool speculate = false;               // the next Jacobian evaluation may be launched ahead of the host's decision
+};
+
 }  // namespace
 
 struct mvgx_ba_ctx {
@@ -3486,11 +3508,8 @@ struct mvgx_ba_ctx {
   double* h_scalars = nullptr;         // pinned: kSCount scalars | fail word | sequence number of the last publication
   double* h_scalars_dev = nullptr;     // the same block as the device addresses it
   unsigned long long publish_seq = 0;
-  bool poll_scalars = true;
   int* h_fail = nullptr;               // the slot after h_scalars
   int* d_accept = nullptr;             // device word: the accept decision of the step just computed (ba_publish_scalars_kernel)
-  bool speculate = true;               // MVGX_BA_SPECULATE=0: the next Jacobian evaluation is launched after the host's decision, as before round 6
-  bool spec_done = false;              // this step's Jacobian evaluation at x + delta is already enqueued, gated by d_accept
   uint64_t spec_stats[3] = {0, 0, 0};  // since creation: evaluations launched ahead, consumed as the next Jacobian, gate stayed shut (mvgx_debug_ba_speculation)
   mvgx_allreduce_f64 allreduce = nullptr;
   void* allreduce_user = nullptr;
@@ -3498,73 +3517,91 @@ struct mvgx_ba_ctx {
   double n_obs_rmse_local = 0;         // observations of this rank that count in the RMSE (not control points)
   double n_obs_global = 0;             // ... over all ranks
   bool update_incomplete = false;      // a mvgx_ba_update{,_subset} failed half way: no solve until one succeeds
+  // Every MVGX_BA_* environment setting of a context (read_settings, at mvgx_ba_create); solver_mode also by mvgx_ba_set_linear_solver
+  struct Settings {
+    bool poll_scalars = true;            // MVGX_BA_POLL_SCALARS=0 (or no device address for h_scalars): the scalars of a step come by copy + synchronise (read_scalars)
+    bool speculate = true;               // MVGX_BA_SPECULATE=0: the next Jacobian evaluation is launched after the host's decision, as before round 6
+    bool model_cost_from_jacobian = false;   // MVGX_BA_MODEL_COST=jacobian: ba_model_cost_kernel instead of the normal-equation form
+    bool fold_candidate = true;          // MVGX_BA_SEPARATE_COST=1 clears it: the candidate and its cost from passes of their own, not from the point groups' back-substitution
+    // block-sparse solve, MVGX_BA_LOOKAHEAD=1: one launch per level, the next level's factorisation beside the tasks of this one. Built and measured
+    // in round 5 (calls r5_06 .. r5_10), bit-identical, and 7 % SLOWER than the level-by-level schedule (C5 0.445 against 0.416 ms, C3 0.266 against
+    // 0.249): taking a contribution inside the factor workgroup costs the 6 us the separate task launch did, and the U tasks that rebuild their
+    // strips of L do six times the MFMA work at a quarter of the occupancy. Off by default; kept as the cross-check of the schedule (tests).
+    bool lookahead = false;
+    // reverse sweep of the block-sparse solve in ONE launch (sp_backsolve_all_kernel: the consumers poll the solution's values). On by default;
+    // MVGX_BA_BACKSOLVE_FLAGS=0 runs a launch per level. Round 5's form of it handed the columns over through device-scope flags and was
+    // bit-identical but SLOWER (call r5_16: C5 solve 0.474 against 0.409 ms, C3 0.246 against 0.245): a device-scope release on this eight-XCD
+    // part writes the producer's whole L2 back, a hand-over cost ~15 us where a launch boundary costs 10.
+    bool bs_one_launch = true;
+    bool backsolve_chain = true;         // MVGX_BA_BACKSOLVE_CHAIN=0: the launch-per-level sweep without the chain kernel over the top levels
+    int chain_fuse_max_tasks = 4096;     // single-column levels with at most this many update tasks run panel + update as one launch (MVGX_BA_CHAIN_FUSE=0: never)
+    int solver_mode = 0;                 // MVGX_BA_SOLVER / mvgx_ba_set_linear_solver: 0 auto, 1 dense, 2 sparse, 3 sparse when its plan exists
+    bool solver_from_env = false;        // MVGX_BA_SOLVER names the solver: mvgx_ba_set_linear_solver leaves it alone
+    mvgx_sparse::PlanParams plan_params; // MVGX_BA_ND_LEAF_COLS, MVGX_BA_ND_SEP_SLACK, MVGX_BA_LOOKAHEAD_MAX_PRE (tests: the schedule's fall-back forms)
+    bool plan_debug = false;             // MVGX_BA_PLAN_DEBUG: the plan's levels on stderr
+    int update128_min_tiles = 128;       // tuning (MVGX_BA_UPDATE128_MIN_TILES): deferred updates with at least this many 128 x 128 tiles use them
+    int two_level_min_n = 2048;          // tuning (MVGX_BA_TWO_LEVEL_MIN_N): reduced systems at least this wide factor with 256-column outer panels
+    // the structure build
+    bool groups_on = true;               // MVGX_BA_GROUPS=0: no point groups
+    int sg_max_groups = 0;               // groups per supergroup at most (MVGX_BA_SG_GROUPS)
+    bool sg_index_order = false;         // MVGX_BA_SG_INDEX_ORDER: supergroups launched in the order of construction (A/B runs), not largest first
+    bool generic_models = false;         // MVGX_BA_GENERIC_MODELS=1: the point-group kernels keep the spherical / fisheye branches whatever the models
+    bool phase_timing = false;           // MVGX_BA_PHASE_TIMING=1: HIP events around the five phases of an iteration (Timing)
+  } set;
+  StepForm form;                         // the launches of an LM iteration (resolve_step_form, by every start())
   // LM state (persists across mvgx_ba_lm_iteration calls)
-  bool started = false;
-  double x_cost = 0, radius = 0, decrease_factor = 2.0, gradient_max_norm = 0;
-  double dmin = 1e-6, dmax = 1e32;     // LM diagonal clamp of the options the current Jacobian evaluation ran with
-  bool gmax_pending = false;           // max |gradient| of the last Jacobian evaluation is still on the device
-  bool gmax_resolved = false;          // ... and arrived with this iteration's step
-  bool reuse_diagonal = false, x_norm_valid = false, last_successful = true;
-  int iteration = 0, invalid = 0, successful = 0, termination = 1;
-  bool finished = false;
-  double initial_cost = 0, initial_rmse = 0;
-  int grid_obs = 0, grid_vec = 0;
+  struct LmState {
+    bool started = false;
+    double x_cost = 0, radius = 0, decrease_factor = 2.0, gradient_max_norm = 0;
+    double x_sqerr = 0;                  // sum of squared residuals at x (the RMSE's numerator), kept with x_cost
+    double dmin = 1e-6, dmax = 1e32;     // LM diagonal clamp of the options the current Jacobian evaluation ran with
+    bool gmax_pending = false;           // max |gradient| of the last Jacobian evaluation is still on the device
+    bool gmax_resolved = false;          // ... and arrived with this iteration's step
+    bool fail_clear = false;             // the device's fail word was cleared by the last Jacobian evaluation and nothing has run since that can set it
+    bool spec_done = false;              // this step's Jacobian evaluation at x + delta is already enqueued, gated by d_accept
+    bool reuse_diagonal = false, x_norm_valid = false, last_successful = true;
+    int iteration = 0, invalid = 0, successful = 0, termination = 1;
+    bool finished = false;
+    double initial_cost = 0, initial_rmse = 0;
+  } lm;
   // reduced-system solver: block-sparse (tile) Cholesky with a nested-dissection order, or the dense one (auto: by fill)
-  std::vector<std::pair<uint32_t, uint32_t>> h_blocks;   // non-zero camera blocks of this rank's S (row block, col block)
+  struct SolverState {
+    std::vector<std::pair<uint32_t, uint32_t>> h_blocks;   // non-zero camera blocks of this rank's S (row block, col block)
+    bool plan_ready = false, plan_sparse = false;   // symbolic phase of the reduced solve done (mvgx_ba_create; again at the first iteration when a communicator was attached since)
+    bool plan_tried = false, plan_ok = false;       // the last plan_solver attempted the sparse plan / it exists
+    mvgx_sparse::Plan plan;              // host copy of the schedule (launch geometry per level)
+    bool ready = false;                  // the device arrays of the solver in place exist (setup_solver)
+    int bs_chain_levels = 0;             // the top levels of the elimination tree with one tile column each (sp_backsolve_chain_kernel), 0: none
+    unsigned bs_epoch = 0;               // number of the solve whose solution the flags of that launch announce
+  } solver;
+  // functions of the structure (mvgx_ba_create)
+  int grid_obs = 0, grid_vec = 0;
   uint32_t n_grouped_points = 0;
-  bool model_cost_from_jacobian = false;   // MVGX_BA_MODEL_COST=jacobian: ba_model_cost_kernel instead of the normal-equation form
-  bool solver_ready = false;
-  bool pinhole_family = false;       // every intrinsic is pinhole / radial K1 / radial K3 / Brown T2: the point-group kernels run without the spherical / fisheye branches
+  bool all_points_grouped = false;     // every point is in a group: the per-point kernels of the record path have nothing to do
+  bool pinhole_family = false;         // every intrinsic is pinhole / radial K1 / radial K3 / Brown T2: the point-group kernels run without the spherical / fisheye branches
   bool diag_blocks_complete = false;   // every pose / intrinsic block has a diagonal destination block in the assemble lists
-  uint32_t n_sg_wide = 0;             // supergroups of the wide form: the tail of sg_order, a launch of their own
-  std::vector<uint32_t> h_sg_order;   // (a member: the asynchronous upload may read it after mvgx_ba_create's locals are gone)
+  uint32_t n_sg_wide = 0;              // supergroups of the wide form: the tail of sg_order, a launch of their own
+  std::vector<uint32_t> h_sg_order;    // (a member: the asynchronous upload may read it after mvgx_ba_create's locals are gone)
+  double* filter_scratch = nullptr;    // 3 n_obs doubles: residual norms / observation rays (mvgx_ba_residuals, mvgx_ba_track_angles)
   // what mvgx_ba_update needs to re-bind the context to new values of the same structure
-  mvgx::BaFingerprint fingerprint;            // of the problem the context was created from
-  std::vector<uint8_t> h_pose_used, h_intr_used;   // blocks that carry a residual (the camera masks are applied on top of these)
-  std::vector<uint32_t> h_perm;               // caller's observation index of point-order position k; empty: the caller's list was in point order
-  uint64_t n_gentries = 0;                    // entries of the point groups (their copy of the image points is re-gathered)
-  std::vector<uint8_t> h_pt_free;             // which points are free parameter blocks with residuals (structure)
-  double n_obs_rmse_all = 0;                  // n_obs_rmse_local of the whole structure (a subset counts its own)
-  uint8_t* odisabled_buf = nullptr;           // device array behind Dev::odisabled (allocated by the first mvgx_ba_update_subset)
-  double* filter_scratch = nullptr;           // 3 n_obs doubles: residual norms / observation rays (mvgx_ba_residuals, mvgx_ba_track_angles)
-  // block-sparse solve, MVGX_BA_LOOKAHEAD=1: one launch per level, the next level's factorisation beside the tasks of this one. Built and measured
-  // in round 5 (calls r5_06 .. r5_10), bit-identical, and 7 % SLOWER than the level-by-level schedule (C5 0.445 against 0.416 ms, C3 0.266 against
-  // 0.249): taking a contribution inside the factor workgroup costs the 6 us the separate task launch did, and the U tasks that rebuild their
-  // strips of L do six times the MFMA work at a quarter of the occupancy. Off by default; kept as the cross-check of the schedule (tests).
-  bool lookahead = false;
-  // reverse sweep of the block-sparse solve in ONE launch (sp_backsolve_all_kernel: the consumers poll the solution's values). On by default;
-  // MVGX_BA_BACKSOLVE_FLAGS=0 runs a launch per level. Round 5's form of it handed the columns over through device-scope flags and was
-  // bit-identical but SLOWER (call r5_16: C5 solve 0.474 against 0.409 ms, C3 0.246 against 0.245): a device-scope release on this eight-XCD
-  // part writes the producer's whole L2 back, a hand-over cost ~15 us where a launch boundary costs 10.
-  bool bs_one_launch = true;
-  unsigned bs_epoch = 0;       // number of the solve whose solution the flags of that launch announce
-  int chain_fuse_max_tasks = 4096;   // single-column levels with at most this many update tasks run panel + update as one launch (MVGX_BA_CHAIN_FUSE=0: never)
-  bool fold_cand_now = false;   // this step: set by compute_step before the solve
-  bool fold_candidate = true, candidate_cost_done = false;   // the candidate and its cost from the back-substitution pass of the point groups (compute_step)
-  bool all_points_grouped = false;   // every point is in a group: the per-point kernels of the record path have nothing to do
-  bool fail_clear = false;           // the device's fail word was cleared by the last Jacobian evaluation and nothing has run since that can set it
-  int bs_chain_levels = 0;   // the top levels of the elimination tree with one tile column each (sp_backsolve_chain_kernel), 0: none
-  bool plan_ready = false, plan_sparse = false;   // symbolic phase of the reduced solve done (mvgx_ba_create; again at the first iteration when a communicator was attached since)
-  double x_sqerr = 0;   // sum of squared residuals at x (the RMSE's numerator), kept with x_cost
-  int solver_mode = 0;             // MVGX_BA_SOLVER / mvgx_ba_set_linear_solver: 0 auto, 1 dense, 2 sparse, 3 sparse when its plan exists
-  bool solver_from_env = false;    // MVGX_BA_SOLVER names the solver: mvgx_ba_set_linear_solver leaves it alone
-  bool plan_tried = false, plan_ok = false;   // the last plan_solver attempted the sparse plan / it exists
-  mvgx_sparse::Plan plan;          // host copy of the schedule (launch geometry per level)
-  int update128_min_tiles = 128;   // tuning (MVGX_BA_UPDATE128_MIN_TILES): deferred updates with at least this many 128 x 128 tiles use them
-  int two_level_min_n = 2048;   // tuning (MVGX_BA_TWO_LEVEL_MIN_N): reduced systems at least this wide factor with 256-column outer panels
-  // settings of the structure build (read_settings)
-  bool groups_on = true;        // MVGX_BA_GROUPS=0: no point groups
-  int sg_max_groups = 0;        // groups per supergroup at most (MVGX_BA_SG_GROUPS)
-  bool sg_index_order = false;  // MVGX_BA_SG_INDEX_ORDER: supergroups launched in the order of construction (A/B runs), not largest first
-  bool generic_models = false;  // MVGX_BA_GENERIC_MODELS=1: the point-group kernels keep the spherical / fisheye branches whatever the models
-  // phase timing (MVGX_BA_PHASE_TIMING=1 at create): HIP events around the five phases of an iteration, summed into phase_ms
-  bool phase_timing = false;
-  struct Mark { int id; hipEvent_t a, b; };
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
-  std::vector<Mark> marks;
-  hipEvent_t ph_a = nullptr;
-  double phase_ms[5] = {0, 0, 0, 0, 0};   // jacobian, schur, solve, backsub, cost
+  struct Rebind {
+    mvgx::BaFingerprint fingerprint;            // of the problem the context was created from
+    std::vector<uint8_t> h_pose_used, h_intr_used;   // blocks that carry a residual (the camera masks are applied on top of these)
+    std::vector<uint32_t> h_perm;               // caller's observation index of point-order position k; empty: the caller's list was in point order
+    uint64_t n_gentries = 0;                    // entries of the point groups (their copy of the image points is re-gathered)
+    std::vector<uint8_t> h_pt_free;             // which points are free parameter blocks with residuals (structure)
+    double n_obs_rmse_all = 0;                  // n_obs_rmse_local of the whole structure (a subset counts its own)
+    uint8_t* odisabled_buf = nullptr;           // device array behind Dev::odisabled (allocated by the first mvgx_ba_update_subset)
+  } rebind;
+  // phase timing (Settings::phase_timing): HIP events around the five phases of an iteration, summed into phase_ms
+  struct Timing {
+    struct Mark { int id; hipEvent_t a, b; };
+    std::vector<hipEvent_t> ev_pool;
+    size_t ev_used = 0;
+    std::vector<Mark> marks;
+    hipEvent_t ph_a = nullptr;
+    double phase_ms[5] = {0, 0, 0, 0, 0};   // jacobian, schur, solve, backsub, cost
+  } timing;
 };
 
 namespace {
@@ -3605,14 +3642,14 @@ __global__ __launch_bounds__(64) void ba_publish_scalars_kernel(const double* __
   if (t == 0) *reinterpret_cast<volatile unsigned long long*>(host + kSCount + 1) = seq;
 }
 int read_scalars(mvgx_ba_ctx* c, int decide = 0, const mvgx_ba_options* opt = nullptr, int (*between)(mvgx_ba_ctx*, void*) = nullptr, void* between_arg = nullptr) {
-  if (!c->poll_scalars) {
+  if (!c->set.poll_scalars) {
     MVGX_HIP(hipMemcpyAsync(c->h_scalars, c->d.scalars, (kSCount + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     MVGX_HIP(hipStreamSynchronize(c->stream));
     return MVGX_OK;
   }
   const unsigned long long seq = ++c->publish_seq;
-  hipLaunchKernelGGL(ba_publish_scalars_kernel, dim3(1), dim3(64), 0, c->stream, c->d.scalars, c->h_scalars_dev, seq, c->d_accept, c->x_cost, opt ? opt->min_relative_decrease : 0.0, decide,
-                     opt ? opt->parameter_tolerance : 0.0, opt ? opt->function_tolerance : 0.0, c->x_norm_valid ? 1 : 0);
+  hipLaunchKernelGGL(ba_publish_scalars_kernel, dim3(1), dim3(64), 0, c->stream, c->d.scalars, c->h_scalars_dev, seq, c->d_accept, c->lm.x_cost, opt ? opt->min_relative_decrease : 0.0, decide,
+                     opt ? opt->parameter_tolerance : 0.0, opt ? opt->function_tolerance : 0.0, c->lm.x_norm_valid ? 1 : 0);
   BA_LAUNCH_CHECK();
   if (between) { const int rc_b = between(c, between_arg); if (rc_b) return rc_b; }   // (work enqueued behind the publish kernel while the device still runs the step)
   volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(c->h_scalars + kSCount + 1);
@@ -3633,29 +3670,29 @@ bool multi_rank(const mvgx_ba_ctx* c) { return c->rccl != nullptr || c->allreduc
 
 enum { kPhJacobian = 0, kPhSchur, kPhSolve, kPhBacksub, kPhCost };
 hipEvent_t phase_event(mvgx_ba_ctx* c) {
-  if (c->ev_used == c->ev_pool.size()) {
+  if (c->timing.ev_used == c->timing.ev_pool.size()) {
     hipEvent_t e = nullptr;
     if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    c->ev_pool.push_back(e);
+    c->timing.ev_pool.push_back(e);
   }
-  hipEvent_t e = c->ev_pool[c->ev_used++];
+  hipEvent_t e = c->timing.ev_pool[c->timing.ev_used++];
   (void)hipEventRecord(e, c->stream);
   return e;
 }
-void phase_begin(mvgx_ba_ctx* c) { if (c->phase_timing) c->ph_a = phase_event(c); }
+void phase_begin(mvgx_ba_ctx* c) { if (c->set.phase_timing) c->timing.ph_a = phase_event(c); }
 void phase_end(mvgx_ba_ctx* c, int id) {
-  if (!c->phase_timing || !c->ph_a) return;
+  if (!c->set.phase_timing || !c->timing.ph_a) return;
   hipEvent_t b = phase_event(c);
-  if (b) c->marks.push_back({id, c->ph_a, b});
-  c->ph_a = nullptr;
+  if (b) c->timing.marks.push_back({id, c->timing.ph_a, b});
+  c->timing.ph_a = nullptr;
 }
 void phase_collect(mvgx_ba_ctx* c) {   // after a stream synchronisation
-  for (const auto& m : c->marks) {
+  for (const auto& m : c->timing.marks) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, m.a, m.b) == hipSuccess) c->phase_ms[m.id] += ms;
+    if (hipEventElapsedTime(&ms, m.a, m.b) == hipSuccess) c->timing.phase_ms[m.id] += ms;
   }
-  c->marks.clear();
-  c->ev_used = 0;
+  c->timing.marks.clear();
+  c->timing.ev_used = 0;
 }
 
 int all_reduce(mvgx_ba_ctx* c, double* buf, uint64_t count, int op = MVGX_REDUCE_SUM) {
@@ -3698,40 +3735,105 @@ void launch_point_groups(mvgx_ba_ctx* c, double inv_radius, double dmin, double 
   }
 }
 
-// TrustRegionMinimizer::EvaluateGradientAndJacobian at the current x (its cost is known: c->x_cost - the cost pass of the
+// ------------------------------------------------------------------------------------------------
+// The launches of an LM iteration. Settings (mvgx_ba_ctx::Settings), structure and the solver in place are resolved ONCE per solve into a
+// StepForm, by start() after setup_solver; nothing that runs in a step looks at them again. What is left to the call: iteration zero,
+// the iteration count against max_num_iterations, and the dynamic lm.fail_clear / gmax_pending / spec_done. Each phase has its own rows,
+// tried from the top; "one rank": neither a communicator nor an all-reduce callback (the shards of a multi-device context have one).
+//
+//   Jacobian evaluation and assembly             | linearize                  | per-point kernels (norms, solve) | ba_obs_z_kernel, ba_slot_z_kernel | the system is zeroed by
+//   ---------------------------------------------+----------------------------+----------------------------------+-----------------------------------+------------------------
+//   no point groups (MVGX_BA_GROUPS=0,           | ba_linearize_kernel<true>  | yes                              | every observation, every slot     | hipMemsetAsync
+//     MVGX_BA_MODEL_COST=jacobian, or no group)  |                            |                                  |                                   |
+//   groups, some observations ungrouped          | ba_linearize_list_kernel   | yes                              | the ungrouped list, every slot    | the groups' forward pass
+//   groups, every observation grouped            | none                       | only if a point is in no group   | none                              | the groups' forward pass
+//                                                |                            | (one without observations)       |                                   |
+//
+//   LM diagonal                                                    | formed by
+//   ---------------------------------------------------------------+-----------------------------------------------------------------------------
+//   iteration zero, several ranks, a point in no group, no chunks  | ba_lm_diag_kernel + reduce_partials_kernel
+//   else (one rank, every point grouped, camera chunks exist)      | ba_gram_finish_kernel (finish_folds_diag)
+//   one rank, every camera block has its diagonal destination      | added to the system by ba_schur_assemble_all_kernel (assemble_finishes)
+//   else (several ranks: after the exchange; a block without one)  | ... by ba_finish_system_kernel
+//
+//   reduced solve (MVGX_BA_SOLVER=dense / sparse, else by fill)    | launches
+//   ---------------------------------------------------------------+-----------------------------------------------------------------------------
+//   dense                                                          | dense_factor_and_solve (MVGX_BA_TWO_LEVEL_MIN_N, MVGX_BA_UPDATE128_MIN_TILES)
+//   sparse, MVGX_BA_LOOKAHEAD=1                                    | sp_level_kernel per level (MVGX_BA_LOOKAHEAD_MAX_PRE: the plan's fall-back levels)
+//   sparse                                                         | per level sp_factor_kernel, then sp_chain_level_kernel (one column, at most
+//                                                                  | MVGX_BA_CHAIN_FUSE update tasks; 0: never) or sp_gemm_kernel<false> / <true>
+//   sparse: reverse sweep, MVGX_BA_BACKSOLVE_FLAGS unset or 1      | sp_backsolve_all_kernel
+//   ... =0, two or more chain levels at the top                    | sp_backsolve_chain_kernel over them, then sp_backsolve_kernel per level
+//   ... =0, MVGX_BA_BACKSOLVE_CHAIN=0 or a shorter chain           | sp_backsolve_kernel per level
+//   sparse: then, candidate folded / not                           | ba_step_scalars_cam_kernel(gather) / sp_gather_solution_kernel
+//
+//   candidate and cost                                             | back-substitution                      | model cost, candidate, its cost
+//   ---------------------------------------------------------------+----------------------------------------+------------------------------------------
+//   MVGX_BA_MODEL_COST=jacobian (no point groups)                  | ba_backsub_kernel                      | ba_model_cost_kernel, ba_candidate_kernel,
+//                                                                  |                                        | ba_linearize_kernel<false>
+//   MVGX_BA_SEPARATE_COST=1, or a point in no group                | ba_backsub_kernel (*), groups' pass    | ba_step_scalars_kernel (model + candidate),
+//                                                                  |                                        | ba_linearize_kernel<false>
+//   else (every point grouped): folded                             | (*), ba_step_scalars_cam_kernel of its | the groups' pass + ba_step_reduce_kernel
+//                                                                  | own if dense, the groups' pass         |
+//   (*) not with the sparse solve and every point grouped: the gather has written the camera steps, no point is left
+//
+//   speculation: MVGX_BA_SPECULATE unset or 1, MVGX_BA_POLL_SCALARS unset or 1, candidate folded, one rank, no priors, camera chunks exist
+//   (and, at the call, an iteration left): the next Jacobian evaluation is enqueued behind ba_publish_scalars_kernel, gated by its verdict.
+// ------------------------------------------------------------------------------------------------
+StepForm resolve_step_form(const mvgx_ba_ctx* c) {
+  const Dev& d = c->d;
+  const mvgx_ba_ctx::Settings& set = c->set;
+  const bool groups = d.grp.n_sg != 0, one_rank = !multi_rank(c);
+  const bool folded = set.fold_candidate && c->all_points_grouped && groups && !set.model_cost_from_jacobian;
+  StepForm f;
+  f.records = !d.n_obs ? StepForm::kRecordsNone : !groups ? StepForm::kRecordsAll : d.grp.n_ungrouped ? StepForm::kRecordsUngrouped : StepForm::kRecordsNone;
+  f.record_points = d.n_pts && !c->all_points_grouped;
+  f.finish_folds_diag = one_rank && c->all_points_grouped && d.n_pichunks != 0;
+  f.assemble_finishes = c->diag_blocks_complete && one_rank;
+  f.sparse = d.sp.enabled != 0;
+  f.schedule = set.lookahead ? StepForm::kLookahead : StepForm::kLevelByLevel;
+  f.chain_fuse_max_tasks = set.chain_fuse_max_tasks;
+  f.sweep = set.bs_one_launch && c->solver.plan.nT > 0 ? StepForm::kSweepOneLaunch : c->solver.bs_chain_levels >= 2 ? StepForm::kSweepChainThenLevels : StepForm::kSweepLevels;
+  f.sweep_chain_levels = c->solver.bs_chain_levels;
+  f.gather_with_cam_sums = folded;
+  f.candidate = folded ? StepForm::kCandFolded : set.model_cost_from_jacobian ? StepForm::kCandJacobianModel : StepForm::kCandStepScalars;
+  f.backsub_launch = !(f.sparse && c->all_points_grouped);
+  f.cam_sums_launch = folded && !f.sparse;
+  f.speculate = set.speculate && set.poll_scalars && folded && one_rank && !d.n_priors && d.n_pichunks;
+  return f;
+}
+
+// TrustRegionMinimizer::EvaluateGradientAndJacobian at the current x (its cost is known: c->lm.x_cost - the cost pass of the
 // candidate that became x, or of the start). What depends on the Jacobian alone is formed here: the Gram blocks of the camera
 // columns with their column norms and gradient (ba_cam_gram_kernel evaluates the observations itself), the Jacobian records,
 // column norms and gradients of the points OUTSIDE the point groups, the Jacobi scaling at iteration 0, the LM diagonal. The
 // points of the groups have no stored Jacobian: their norms come from the kGroupNorms pass at iteration 0 (the scaling needs
 // them first) and from the forward pass of the next compute_step afterwards, which also reports their max |gradient|
-// (scalars[kSGmaxGrp]): c->gmax_pending tells lm_iteration to complete gradient_max_norm with it.
+// (scalars[kSGmaxGrp]): c->lm.gmax_pending tells lm_iteration to complete gradient_max_norm with it.
 int evaluate_gradient_and_jacobian(mvgx_ba_ctx* c, const mvgx_ba_options* opt, bool iteration_zero) {
   Dev& d = c->d;
+  const StepForm& f = c->form;
   phase_begin(c);
   int rc;
-  if (d.n_obs) {
-    if (!d.grp.n_sg) {
-      hipLaunchKernelGGL(ba_linearize_kernel<true>, dim3(c->grid_obs), dim3(256), 0, c->stream, d, d.poses, d.intr, d.pts, d.part);
-    } else if (d.grp.n_ungrouped) {
-      hipLaunchKernelGGL(ba_linearize_list_kernel, dim3((d.grp.n_ungrouped + 255) / 256), dim3(256), 0, c->stream, d, d.grp.ungrouped, d.grp.n_ungrouped);
-    }
-  }
+  if (f.records == StepForm::kRecordsAll)
+    hipLaunchKernelGGL(ba_linearize_kernel<true>, dim3(c->grid_obs), dim3(256), 0, c->stream, d, d.poses, d.intr, d.pts, d.part);
+  else if (f.records == StepForm::kRecordsUngrouped)
+    hipLaunchKernelGGL(ba_linearize_list_kernel, dim3((d.grp.n_ungrouped + 255) / 256), dim3(256), 0, c->stream, d, d.grp.ungrouped, d.grp.n_ungrouped);
   if (d.n_priors) hipLaunchKernelGGL(ba_prior_kernel<true>, dim3(1), dim3(256), 0, c->stream, d, d.poses, 0);
   BA_LAUNCH_CHECK();
   // (always: a point without observations is on neither path's lists, and its norms / factor / step must still be defined)
-  if (d.n_pts && !c->all_points_grouped) hipLaunchKernelGGL(ba_point_norms_kernel, dim3((d.n_pts + 255) / 256), dim3(256), 0, c->stream, d);
+  if (f.record_points) hipLaunchKernelGGL(ba_point_norms_kernel, dim3((d.n_pts + 255) / 256), dim3(256), 0, c->stream, d);
   if (d.n_pichunks) {   // (also clears the fail word)
     if (c->pinhole_family) hipLaunchKernelGGL(ba_cam_gram_kernel<true>, dim3(d.n_pichunks), dim3(256), 0, c->stream, d);
     else hipLaunchKernelGGL(ba_cam_gram_kernel<false>, dim3(d.n_pichunks), dim3(256), 0, c->stream, d);
   }
-  c->fail_clear = d.n_pichunks != 0;
-  c->dmin = opt->min_lm_diagonal; c->dmax = opt->max_lm_diagonal;
-  // (one rank, not iteration zero, every point grouped: the finish launch also forms the LM diagonal and the gradient maximum of
-  // the camera columns - there is nothing else for ba_lm_diag_kernel to do)
-  const bool fold_diag = !iteration_zero && !multi_rank(c) && c->all_points_grouped && d.n_pichunks != 0;
+  c->lm.fail_clear = d.n_pichunks != 0;
+  c->lm.dmin = opt->min_lm_diagonal; c->lm.dmax = opt->max_lm_diagonal;
+  // (the finish launch also forms the LM diagonal and the gradient maximum of the camera columns: nothing left for ba_lm_diag_kernel)
+  const bool fold_diag = !iteration_zero && f.finish_folds_diag;
   {
     const uint32_t wg_pi = ((uint32_t)d.n_pi + 7) / 8, wg_pose = (d.n_poses + 31) / 32, wg_all = wg_pi + wg_pose + d.n_intr * kIntrSlices;
-    if (wg_all) hipLaunchKernelGGL(ba_gram_finish_kernel, dim3(wg_all), dim3(1024), 0, c->stream, d, wg_pi, wg_pose, fold_diag ? 1 : 0, c->dmin, c->dmax);
+    if (wg_all) hipLaunchKernelGGL(ba_gram_finish_kernel, dim3(wg_all), dim3(1024), 0, c->stream, d, wg_pi, wg_pose, fold_diag ? 1 : 0, c->lm.dmin, c->lm.dmax);
   }
   BA_LAUNCH_CHECK();
   if ((rc = all_reduce(c, d.cn_cam, d.N))) return rc;
@@ -3749,10 +3851,10 @@ int evaluate_gradient_and_jacobian(mvgx_ba_ctx* c, const mvgx_ba_options* opt, b
   }
   if ((rc = all_reduce(c, d.scalars + kSGmax, 1, MVGX_REDUCE_MAX))) return rc;   // point gradients are rank-local
   phase_end(c, kPhJacobian);
-  c->gmax_pending = !iteration_zero;
+  c->lm.gmax_pending = !iteration_zero;
   if (iteration_zero) {   // the first gradient_max_norm is tested before any step is computed
     if ((rc = read_scalars(c))) return rc;
-    c->gradient_max_norm = c->h_scalars[kSGmax];
+    c->lm.gradient_max_norm = c->h_scalars[kSGmax];
   }
   return MVGX_OK;
 }
@@ -3760,24 +3862,22 @@ int evaluate_gradient_and_jacobian(mvgx_ba_ctx* c, const mvgx_ba_options* opt, b
 // Partial reduced camera system of this rank at the current radius (raw sums: LM diagonal not yet added)
 int assemble_system(mvgx_ba_ctx* c, double inv_radius) {
   Dev& d = c->d;
-  if (!c->fail_clear) MVGX_HIP(hipMemsetAsync(d.fail, 0, sizeof(int), c->stream));   // (a step that follows a rejected one: no Jacobian evaluation in between)
-  c->fail_clear = false;
-  const bool flat = !d.grp.n_sg || d.grp.n_ungrouped;   // some points are on the record-based path
-  if (d.n_pts && !c->all_points_grouped) hipLaunchKernelGGL(ba_point_solve_kernel, dim3((d.n_pts + 255) / 256), dim3(256), 0, c->stream, d, inv_radius);
-  if (d.grp.n_sg) {
-    if (d.grp.n_ungrouped)
-      hipLaunchKernelGGL(ba_obs_z_kernel, dim3((d.grp.n_ungrouped + 255) / 256), dim3(256), 0, c->stream, d, d.grp.ungrouped, (uint64_t)d.grp.n_ungrouped);
-  } else if (d.n_obs) {
+  if (!c->lm.fail_clear) MVGX_HIP(hipMemsetAsync(d.fail, 0, sizeof(int), c->stream));   // (a step that follows a rejected one: no Jacobian evaluation in between)
+  c->lm.fail_clear = false;
+  const StepForm& f = c->form;
+  if (f.record_points) hipLaunchKernelGGL(ba_point_solve_kernel, dim3((d.n_pts + 255) / 256), dim3(256), 0, c->stream, d, inv_radius);
+  if (f.records == StepForm::kRecordsUngrouped)
+    hipLaunchKernelGGL(ba_obs_z_kernel, dim3((d.grp.n_ungrouped + 255) / 256), dim3(256), 0, c->stream, d, d.grp.ungrouped, (uint64_t)d.grp.n_ungrouped);
+  else if (f.records == StepForm::kRecordsAll)
     hipLaunchKernelGGL(ba_obs_z_kernel, dim3(c->grid_obs), dim3(256), 0, c->stream, d, (const uint32_t*)nullptr, (uint64_t)d.n_obs);
-  }
-  if (d.n_islots && flat) hipLaunchKernelGGL(ba_slot_z_kernel, dim3((8 * d.n_islots + 255) / 256), dim3(256), 0, c->stream, d);
+  if (d.n_islots && f.records != StepForm::kRecordsNone) hipLaunchKernelGGL(ba_slot_z_kernel, dim3((8 * d.n_islots + 255) / 256), dim3(256), 0, c->stream, d);
   BA_LAUNCH_CHECK();
   if (!d.grp.n_sg) {   // (with point groups their forward pass zeroes the system, a slice per workgroup)
-    if (d.sp.enabled) MVGX_HIP(hipMemsetAsync(d.sp.A, 0, (size_t)d.sp.n_slots * 4096 * sizeof(double), c->stream));
+    if (f.sparse) MVGX_HIP(hipMemsetAsync(d.sp.A, 0, (size_t)d.sp.n_slots * 4096 * sizeof(double), c->stream));
     else MVGX_HIP(hipMemsetAsync(d.S, 0, (size_t)d.N * d.LD * sizeof(double), c->stream));
   }
   if (d.grp.n_sg) {
-    launch_point_groups<kGroupForward>(c, inv_radius, c->dmin, c->dmax);   // (max |gradient| of its supergroups: reduced by the assemble launch below)
+    launch_point_groups<kGroupForward>(c, inv_radius, c->lm.dmin, c->lm.dmax);   // (max |gradient| of its supergroups: reduced by the assemble launch below)
   }
   if (d.tpp.n_chunks)
     hipLaunchKernelGGL((ba_schur_products_kernel<6, 6>), dim3(8 * ((d.tpp.n_chunks + 7) / 8)), dim3(64), 0, c->stream, d.tpp, d.Zpose, d.Zpose, d.hp, d.opt);
@@ -3787,7 +3887,7 @@ int assemble_system(mvgx_ba_ctx* c, double inv_radius) {
     hipLaunchKernelGGL((ba_schur_products_kernel<8, 8>), dim3(8 * ((d.tii.n_chunks + 7) / 8)), dim3(64), 0, c->stream, d.tii, d.Zint, d.Zint, d.hp, d.slot_point);
   BA_LAUNCH_CHECK();
   {
-    d.asm_inv_radius = c->diag_blocks_complete && !multi_rank(c) ? inv_radius : 0.0;
+    d.asm_inv_radius = f.assemble_finishes ? inv_radius : 0.0;
     const uint32_t wg_pp = (d.tpp.n_blocks + 7) / 8, wg_pi = (d.tpi.n_blocks + 7) / 8, wg_ii = d.tii.n_blocks;
     const uint32_t wg_all = wg_pp + wg_pi + wg_ii + (d.grp.n_sg ? 1u : 0u);
     if (wg_all) hipLaunchKernelGGL(ba_schur_assemble_all_kernel, dim3(wg_all), dim3(1024), 0, c->stream, d, wg_pp, wg_pi, wg_ii);
@@ -3810,8 +3910,9 @@ int assemble_system(mvgx_ba_ctx* c, double inv_radius) {
 // took 235 us in the fused launch against ~140 us as 16 launches, 6 levels of C5 262 us against ~216 us.
 int factor_and_solve_sparse(mvgx_ba_ctx* c) {
   Dev& d = c->d;
-  const mvgx_sparse::Plan& pl = c->plan;
-  if (c->lookahead) {
+  const StepForm& f = c->form;
+  const mvgx_sparse::Plan& pl = c->solver.plan;
+  if (f.schedule == StepForm::kLookahead) {
     // One launch per level (sp_level_kernel): the factorisation of level l beside the T / U tasks of level l - 1. A level whose diagonal
     // tiles collect more contributions of the level before than a factor workgroup takes (ba_sparse_plan.h: kMaxPre) waits for them:
     // its tasks get a launch of their own in front of its factorisation.
@@ -3830,35 +3931,36 @@ int factor_and_solve_sparse(mvgx_ba_ctx* c) {
       if (l == 0 || pre || l == pl.n_levels) level(f0, nf, pre ? 1 : 0, u0, nu, t0, nt);
       else { level(0, 0, 0, u0, nu, t0, nt); level(f0, nf, 0, 0, 0, 0, 0); }
     }
-  } else
-  for (int l = 0; l < pl.n_levels; ++l) {
-    const int nf = pl.f_start[l + 1] - pl.f_start[l], nt = pl.t_start[l + 1] - pl.t_start[l], nu = pl.u_start[l + 1] - pl.u_start[l];
-    hipLaunchKernelGGL(sp_factor_kernel, dim3(nf), dim3(256), kDiagLds, c->stream, d.sp, pl.f_start[l], d.fail);
-    if (nf == 1 && nu && nu <= c->chain_fuse_max_tasks) {   // a chain level: panel and update tasks in one launch (sp_chain_level_kernel)
-      hipLaunchKernelGGL(sp_chain_level_kernel, dim3((nt + nu + 3) / 4), dim3(256), 0, c->stream, d.sp, pl.t_start[l], nt, pl.u_start[l], nu,
-                         pl.f_cols[pl.f_start[l]]);
-      continue;
+  } else {
+    for (int l = 0; l < pl.n_levels; ++l) {
+      const int nf = pl.f_start[l + 1] - pl.f_start[l], nt = pl.t_start[l + 1] - pl.t_start[l], nu = pl.u_start[l + 1] - pl.u_start[l];
+      hipLaunchKernelGGL(sp_factor_kernel, dim3(nf), dim3(256), kDiagLds, c->stream, d.sp, pl.f_start[l], d.fail);
+      if (nf == 1 && nu && nu <= f.chain_fuse_max_tasks) {   // a chain level: panel and update tasks in one launch (sp_chain_level_kernel)
+        hipLaunchKernelGGL(sp_chain_level_kernel, dim3((nt + nu + 3) / 4), dim3(256), 0, c->stream, d.sp, pl.t_start[l], nt, pl.u_start[l], nu,
+                           pl.f_cols[pl.f_start[l]]);
+        continue;
+      }
+      if (nt) hipLaunchKernelGGL(sp_gemm_kernel<false>, dim3((nt + 3) / 4), dim3(256), 0, c->stream, d.sp, pl.t_start[l], nt);
+      if (nu) hipLaunchKernelGGL(sp_gemm_kernel<true>, dim3((nu + 3) / 4), dim3(256), 0, c->stream, d.sp, pl.u_start[l], nu);
     }
-    if (nt) hipLaunchKernelGGL(sp_gemm_kernel<false>, dim3((nt + 3) / 4), dim3(256), 0, c->stream, d.sp, pl.t_start[l], nt);
-    if (nu) hipLaunchKernelGGL(sp_gemm_kernel<true>, dim3((nu + 3) / 4), dim3(256), 0, c->stream, d.sp, pl.u_start[l], nu);
   }
   BA_LAUNCH_CHECK();
-  if (c->bs_one_launch && pl.nT > 0) {   // the whole reverse sweep as one launch, columns handed over through flags (sp_backsolve_all_kernel)
-    c->bs_epoch += 1;
-    if (c->bs_epoch == 0) c->bs_epoch = 1;   // (0 is the value the flags start from)
-    hipLaunchKernelGGL(sp_backsolve_all_kernel, dim3(pl.nT), dim3(256), 0, c->stream, d.sp, c->bs_epoch, d.fail);
+  if (f.sweep == StepForm::kSweepOneLaunch) {   // the whole reverse sweep as one launch, columns handed over through flags (sp_backsolve_all_kernel)
+    c->solver.bs_epoch += 1;
+    if (c->solver.bs_epoch == 0) c->solver.bs_epoch = 1;   // (0 is the value the flags start from)
+    hipLaunchKernelGGL(sp_backsolve_all_kernel, dim3(pl.nT), dim3(256), 0, c->stream, d.sp, c->solver.bs_epoch, d.fail);
   } else {
-  int l_top = pl.n_levels - 1;
-  if (c->bs_chain_levels >= 2) {   // the chain at the top of the tree: one workgroup, one launch
-    const int l0 = pl.n_levels - c->bs_chain_levels;
-    hipLaunchKernelGGL(sp_backsolve_chain_kernel, dim3(1), dim3(256), 0, c->stream, d.sp, pl.f_start[l0], c->bs_chain_levels, l0);
-    l_top = l0 - 1;
+    int l_top = pl.n_levels - 1;
+    if (f.sweep == StepForm::kSweepChainThenLevels) {   // the chain at the top of the tree: one workgroup, one launch
+      const int l0 = pl.n_levels - f.sweep_chain_levels;
+      hipLaunchKernelGGL(sp_backsolve_chain_kernel, dim3(1), dim3(256), 0, c->stream, d.sp, pl.f_start[l0], f.sweep_chain_levels, l0);
+      l_top = l0 - 1;
+    }
+    for (int l = l_top; l >= 0; --l)
+      hipLaunchKernelGGL(sp_backsolve_kernel, dim3(pl.f_start[l + 1] - pl.f_start[l]), dim3(256), 0, c->stream, d.sp, pl.f_start[l]);
   }
-  for (int l = l_top; l >= 0; --l)
-    hipLaunchKernelGGL(sp_backsolve_kernel, dim3(pl.f_start[l + 1] - pl.f_start[l]), dim3(256), 0, c->stream, d.sp, pl.f_start[l]);
-  }
-  if (c->fold_cand_now)   // (compute_step: this step's back-substitution forms the candidate - the gather and the camera half of the step's sums are one launch)
-    hipLaunchKernelGGL(ba_step_scalars_cam_kernel, dim3((d.N + 255) / 256), dim3(256), 0, c->stream, d, 1.0 / c->radius, d.part, 1);
+  if (f.gather_with_cam_sums)   // (the point groups' back-substitution forms the candidate - the gather and the camera half of the step's sums are one launch)
+    hipLaunchKernelGGL(ba_step_scalars_cam_kernel, dim3((d.N + 255) / 256), dim3(256), 0, c->stream, d, 1.0 / c->lm.radius, d.part, 1);
   else
     hipLaunchKernelGGL(sp_gather_solution_kernel, dim3((d.N + 255) / 256), dim3(256), 0, c->stream, d);
   BA_LAUNCH_CHECK();
@@ -3910,8 +4012,8 @@ int dense_factor_and_solve(double* S, int N, int LD, double* linv_all, double* z
 int factor_and_solve(mvgx_ba_ctx* c) {
   Dev& d = c->d;
   if (!d.N) return MVGX_OK;
-  if (d.sp.enabled) return factor_and_solve_sparse(c);
-  return dense_factor_and_solve(d.S, d.N, d.LD, d.linv, d.zsol, d.fail, c->stream, c->two_level_min_n, c->update128_min_tiles);
+  if (c->form.sparse) return factor_and_solve_sparse(c);
+  return dense_factor_and_solve(d.S, d.N, d.LD, d.linv, d.zsol, d.fail, c->stream, c->set.two_level_min_n, c->set.update128_min_tiles);
 }
 
 // One-time agreement across ranks, before the first iteration:
@@ -3929,7 +4031,7 @@ __global__ void ba_masks_f64_kernel(Dev d, double* __restrict__ buf, int dir) {
 
 int setup_block_exchange(mvgx_ba_ctx* c, std::vector<std::pair<uint32_t, uint32_t>>& blocks) {
   Dev& d = c->d;
-  blocks = c->h_blocks;
+  blocks = c->solver.h_blocks;
   if (!multi_rank(c) || d.ublk_off) return MVGX_OK;
   int rc;
   if (d.N) {
@@ -3991,27 +4093,23 @@ int setup_block_exchange(mvgx_ba_ctx* c, std::vector<std::pair<uint32_t, uint32_
 // afterwards plans again at its first iteration, on the union of the ranks' blocks.
 int plan_solver(mvgx_ba_ctx* c, const std::vector<std::pair<uint32_t, uint32_t>>& blocks) {
   Dev& d = c->d;
-  if (c->plan_ready) return MVGX_OK;
+  if (c->solver.plan_ready) return MVGX_OK;
   bool sparse = false;
   const uint32_t np = d.n_poses;
-  if (d.N > 0 && c->solver_mode != 1) {
-    mvgx_sparse::PlanParams prm;
-    if (const char* env = getenv("MVGX_BA_ND_LEAF_COLS")) prm.leaf_cols = std::max(64, atoi(env));
-    if (const char* env = getenv("MVGX_BA_ND_SEP_SLACK")) prm.sep_weight_slack = std::max(1.0, atof(env));   // (1: only level sets as light as the lightest compete on balance)
-    if (const char* env = getenv("MVGX_BA_LOOKAHEAD_MAX_PRE")) prm.max_pre = std::max(0, atoi(env));   // (tests: the schedule's fall-back forms)
+  if (d.N > 0 && c->set.solver_mode != 1) {
     const bool ok = mvgx_sparse::build_plan(
         (int)(np + d.n_intr), d.N, blocks, [&](int cb) { return cb < (int)np ? 6 : 8; },
-        [&](int cb) { return cb < (int)np ? 6 * cb : 6 * (int)np + 8 * (cb - (int)np); }, prm, (uint64_t)1 << 25, c->plan);
+        [&](int cb) { return cb < (int)np ? 6 * cb : 6 * (int)np + 8 * (cb - (int)np); }, c->set.plan_params, (uint64_t)1 << 25, c->solver.plan);
     const uint64_t nd = (uint64_t)((d.N + 63) / 64);
-    c->plan_tried = true; c->plan_ok = ok;
+    c->solver.plan_tried = true; c->solver.plan_ok = ok;
     // (round 6: "<=" - a camera graph without structure gives a plan of nd single-column levels, a dense factorisation run by the tile
     // kernels: a level is then two launches where the dense solver's block step is three, and the reverse sweep one launch where it
     // is nd - 0.59 against 0.93 ms at N = 1 203 on a scene with long tracks, call r6_14)
-    sparse = ok && (c->solver_mode >= 2 || ((uint64_t)c->plan.n_levels <= nd && c->plan.n_fill_tiles <= nd * (nd + 1) / 2));
-    MVGX_REQUIRE(ok || c->solver_mode != 2, MVGX_ERR_UNSUPPORTED, "MVGX_BA_SOLVER=sparse: the reduced system fills too much for the task lists");
+    sparse = ok && (c->set.solver_mode >= 2 || ((uint64_t)c->solver.plan.n_levels <= nd && c->solver.plan.n_fill_tiles <= nd * (nd + 1) / 2));
+    MVGX_REQUIRE(ok || c->set.solver_mode != 2, MVGX_ERR_UNSUPPORTED, "MVGX_BA_SOLVER=sparse: the reduced system fills too much for the task lists");
   }
-  if (sparse && getenv("MVGX_BA_PLAN_DEBUG")) {
-    const mvgx_sparse::Plan& pl = c->plan;
+  if (sparse && c->set.plan_debug) {
+    const mvgx_sparse::Plan& pl = c->solver.plan;
     for (int l = 0; l < pl.n_levels; ++l) {
       int longest = 0; long total = 0;
       for (int t = pl.u_start[l]; t < pl.u_start[l + 1]; ++t) { const int n = pl.u_tasks[t].c1 - pl.u_tasks[t].c0; longest = std::max(longest, n); total += n; }
@@ -4020,19 +4118,19 @@ int plan_solver(mvgx_ba_ctx* c, const std::vector<std::pair<uint32_t, uint32_t>>
               pl.f_start[l + 1] - pl.f_start[l], pl.t_start[l + 1] - pl.t_start[l], pl.u_start[l + 1] - pl.u_start[l], total, longest);
     }
   }
-  c->plan_sparse = sparse;
-  c->plan_ready = true;
+  c->solver.plan_sparse = sparse;
+  c->solver.plan_ready = true;
   return MVGX_OK;
 }
 
 int setup_solver(mvgx_ba_ctx* c, const std::vector<std::pair<uint32_t, uint32_t>>& blocks) {
   Dev& d = c->d;
-  if (c->solver_ready) return MVGX_OK;
+  if (c->solver.ready) return MVGX_OK;
   int rc = plan_solver(c, blocks);
   if (rc) return rc;
-  const bool sparse = c->plan_sparse;
+  const bool sparse = c->solver.plan_sparse;
   if (sparse) {
-    const mvgx_sparse::Plan& pl = c->plan;
+    const mvgx_sparse::Plan& pl = c->solver.plan;
     SpSys& s = d.sp;
     s.nT = pl.nT; s.n_slots = pl.n_slots; s.n_levels = pl.n_levels;
     int32_t *pcol = nullptr, *tmap = nullptr, *tile_kb = nullptr, *f_cols = nullptr, *bs_start = nullptr, *bs_slot = nullptr, *bs_row = nullptr;
@@ -4063,20 +4161,19 @@ int setup_solver(mvgx_ba_ctx* c, const std::vector<std::pair<uint32_t, uint32_t>
       s.bs_rec = bs_rec;
       if ((rc = dev_alloc(c->pool, &s.z_flag, (size_t)std::max(pl.nT, 1)))) return rc;
       MVGX_HIP(hipMemsetAsync(s.z_flag, 0, (size_t)std::max(pl.nT, 1) * sizeof(unsigned), c->stream));
-      c->bs_epoch = 0;
+      c->solver.bs_epoch = 0;
     }
     {   // the chain at the top: as many single-column levels as the kernel's LDS tables hold (MVGX_BA_BACKSOLVE_CHAIN=0: none)
-      const char* env = getenv("MVGX_BA_BACKSOLVE_CHAIN");
       int n = 0; size_t entries = 0;
-      if (!(env && atoi(env) == 0))
+      if (c->set.backsolve_chain)
         for (int l = pl.n_levels - 1; l >= 0 && pl.f_start[l + 1] - pl.f_start[l] == 1 && n < kChainMax; --l) {
           const int k = pl.f_cols[pl.f_start[l]];
           const size_t e = (size_t)(pl.bs_start[k + 1] - pl.bs_start[k]);
           if (entries + e > (size_t)kChainEntriesMax) break;
           entries += e; ++n;
         }
-      c->bs_chain_levels = n;
-      if (getenv("MVGX_BA_PLAN_DEBUG")) fprintf(stderr, "[mvgx ba plan] tile columns %d, levels %d, chain at the top %d levels (%zu tiles below its columns)\n", pl.nT, pl.n_levels, n, entries);
+      c->solver.bs_chain_levels = n;
+      if (c->set.plan_debug) fprintf(stderr, "[mvgx ba plan] tile columns %d, levels %d, chain at the top %d levels (%zu tiles below its columns)\n", pl.nT, pl.n_levels, n, entries);
     }
     if ((rc = dev_upload(c->pool, &tt, pl.t_tasks, c->stream))) return rc;
     if ((rc = dev_upload(c->pool, &ut, pl.u_tasks, c->stream))) return rc;
@@ -4107,7 +4204,7 @@ int setup_solver(mvgx_ba_ctx* c, const std::vector<std::pair<uint32_t, uint32_t>
     if ((rc = dev_alloc(c->pool, &d.S, (size_t)d.N * d.LD))) return rc;
     if ((rc = dev_alloc(c->pool, &d.linv, (size_t)((d.N + 63) / 64) * 8192))) return rc;
   }
-  c->solver_ready = true;
+  c->solver.ready = true;
   return MVGX_OK;
 }
 
@@ -4127,12 +4224,12 @@ int exchange_system(mvgx_ba_ctx* c) {
 // x + delta and its cost, enqueued behind the step that produced delta WITHOUT waiting for the step's verdict: an invalid step
 // (failed factorisation, non-positive model cost change) is rare and only wastes these launches - the candidate arrays and
 // scalars they write are not read in that case - while every valid step saves one host round trip per iteration.
-int enqueue_candidate_and_cost(mvgx_ba_ctx* c, bool candidate_done) {
+int enqueue_candidate_and_cost(mvgx_ba_ctx* c) {
   Dev& d = c->d;
-  if (c->candidate_cost_done) return all_reduce(c, d.scalars + kSCost, 2);   // (the back-substitution pass has formed both)
+  if (c->form.candidate == StepForm::kCandFolded) return all_reduce(c, d.scalars + kSCost, 2);   // (the back-substitution pass has formed both)
   phase_begin(c);
   int rc;
-  if (!candidate_done) {   // (else ba_step_scalars_kernel has formed the candidate with the model cost)
+  if (c->form.candidate == StepForm::kCandJacobianModel) {   // (else ba_step_scalars_kernel has formed the candidate with the model cost)
     // the kernel writes EVERY entry of the three candidate arrays (x + 0 for constant parameters): no copy of x beforehand
     hipLaunchKernelGGL(ba_candidate_kernel, dim3(c->grid_vec), dim3(256), 0, c->stream, d, d.part);
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, c->stream, d.part, c->grid_vec, 4, 4, d.scalars, kSCamStepSq, 0);
@@ -4144,93 +4241,92 @@ int enqueue_candidate_and_cost(mvgx_ba_ctx* c, bool candidate_done) {
   return MVGX_OK;
 }
 
-// LevenbergMarquardtStrategy::ComputeStep + SchurComplementSolver::SolveImpl. ok=false <=> LINEAR_SOLVER_FAILURE.
-int evaluate_gradient_and_jacobian(mvgx_ba_ctx* c, const mvgx_ba_options* opt, bool iteration_zero);
 // The Jacobian evaluation of the NEXT iteration at x + delta, enqueued behind the publish kernel and gated by the device's accept word
 // (ba_publish_scalars_kernel): the pointers of x and the candidate are exchanged for the launches and exchanged back - the host accepts,
 // or does not, when it has read the scalars. Host-side flags the evaluation sets are restored: they become true only with the acceptance.
 int speculative_evaluation(mvgx_ba_ctx* c, void* arg) {
   const mvgx_ba_options* opt = static_cast<const mvgx_ba_options*>(arg);
   Dev& d = c->d;
-  const bool fail_clear = c->fail_clear, gmax_pending = c->gmax_pending;
-  const double dmin = c->dmin, dmax = c->dmax;
+  const bool fail_clear = c->lm.fail_clear, gmax_pending = c->lm.gmax_pending;
+  const double dmin = c->lm.dmin, dmax = c->lm.dmax;
   std::swap(d.poses, d.cposes); std::swap(d.intr, d.cintr); std::swap(d.pts, d.cpts);
   d.gate = c->d_accept;
   const int rc = evaluate_gradient_and_jacobian(c, opt, false);
   d.gate = nullptr;
   std::swap(d.poses, d.cposes); std::swap(d.intr, d.cintr); std::swap(d.pts, d.cpts);
-  c->fail_clear = fail_clear; c->gmax_pending = gmax_pending; c->dmin = dmin; c->dmax = dmax;
-  c->spec_done = rc == MVGX_OK;
-  if (c->spec_done) ++c->spec_stats[0];
+  c->lm.fail_clear = fail_clear; c->lm.gmax_pending = gmax_pending; c->lm.dmin = dmin; c->lm.dmax = dmax;
+  c->lm.spec_done = rc == MVGX_OK;
+  if (c->lm.spec_done) ++c->spec_stats[0];
   return rc;
 }
 
+// LevenbergMarquardtStrategy::ComputeStep + SchurComplementSolver::SolveImpl. ok=false <=> LINEAR_SOLVER_FAILURE.
 int compute_step(mvgx_ba_ctx* c, bool* ok, double* model_cost_change, const mvgx_ba_options* opt) {
   Dev& d = c->d;
-  const double inv_radius = 1.0 / c->radius;
+  const StepForm& f = c->form;
+  const double inv_radius = 1.0 / c->lm.radius;
   phase_begin(c);
   int rc = assemble_system(c, inv_radius);
   if (rc) return rc;
   if ((rc = exchange_system(c))) return rc;
-  if (d.N && d.asm_inv_radius == 0.0) hipLaunchKernelGGL(ba_finish_system_kernel, dim3((d.N + 255) / 256), dim3(256), 0, c->stream, d, inv_radius);   // (else: done by the assemble launch)
+  if (d.N && !(f.assemble_finishes && inv_radius != 0.0))   // (else: done by the assemble launch - it reads asm_inv_radius 0, an infinite radius, as "not here")
+    hipLaunchKernelGGL(ba_finish_system_kernel, dim3((d.N + 255) / 256), dim3(256), 0, c->stream, d, inv_radius);
   BA_LAUNCH_CHECK();
   phase_end(c, kPhSchur);
   phase_begin(c);
-  // every point grouped: the back-substitution pass forms the candidate x + delta and its cost on the way (one pass over the
-  // observations less per iteration); the camera half of the step's sums runs in front of it (MVGX_BA_SEPARATE_COST=1: the passes of old)
-  const bool fold_cand = c->fold_candidate && c->all_points_grouped && d.grp.n_sg && !c->model_cost_from_jacobian;
-  c->fold_cand_now = fold_cand;
   if ((rc = factor_and_solve(c))) return rc;
   phase_end(c, kPhSolve);
   phase_begin(c);
-  if (!(d.sp.enabled && c->all_points_grouped))   // (sparse solve + every point grouped: the gather kernel has written the camera steps, no point is left for this kernel)
-    hipLaunchKernelGGL(ba_backsub_kernel, dim3(c->grid_vec), dim3(256), 0, c->stream, d);   // camera steps; points of the record-based path
-  c->candidate_cost_done = fold_cand;
-  if (fold_cand) {
-    const int n_cam_wg = (d.N + 255) / 256;
-    if (!d.sp.enabled) hipLaunchKernelGGL(ba_step_scalars_cam_kernel, dim3(n_cam_wg), dim3(256), 0, c->stream, d, inv_radius, d.part, 0);   // (else: with the gather)
-    launch_point_groups<kGroupBacksub>(c, inv_radius, c->dmin, c->dmax, d.grp_part);
-    hipLaunchKernelGGL(ba_step_reduce_kernel, dim3(8), dim3(1024), 0, c->stream, d.part, n_cam_wg, d.grp_part, (int)d.grp.n_sg, d.scalars);
-    if (d.n_priors) hipLaunchKernelGGL(ba_prior_kernel<false>, dim3(1), dim3(256), 0, c->stream, d, d.cposes, 1);
-    BA_LAUNCH_CHECK();
-    if ((rc = all_reduce(c, d.scalars + kSStepSq, 3))) return rc;   // (the cost's all-reduce: where the separate cost pass has it - ranks may differ in fold_cand)
-  } else if (d.grp.n_sg) launch_point_groups<kGroupBacksub>(c, inv_radius, c->dmin, c->dmax);
-  if (fold_cand) {
-  } else if (c->model_cost_from_jacobian) {   // Ceres' own form (trust_region_minimizer.cc:402-405): one more pass over the Jacobian records
-    if (d.n_obs) hipLaunchKernelGGL(ba_model_cost_kernel, dim3(c->grid_obs), dim3(256), 0, c->stream, d, d.part);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, c->stream, d.part, d.n_obs ? c->grid_obs : 0, 1, 1, d.scalars,
-                       kSModel, 0);
-    if (d.n_priors) hipLaunchKernelGGL(ba_prior_model_kernel, dim3(1), dim3(256), 0, c->stream, d);
-    BA_LAUNCH_CHECK();
-    if ((rc = all_reduce(c, d.scalars + kSModel, 1))) return rc;
-  } else {
-    hipLaunchKernelGGL(ba_step_scalars_kernel, dim3(c->grid_vec), dim3(256), 0, c->stream, d, inv_radius, d.part);   // model cost + candidate
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, c->stream, d.part, c->grid_vec, 6, 6, d.scalars, kSCamStepSq, 0);
-    BA_LAUNCH_CHECK();
-    if ((rc = all_reduce(c, d.scalars + kSStepSq, 3))) return rc;   // the rank-local point parts; the camera parts are the same on every rank
+  if (f.backsub_launch) hipLaunchKernelGGL(ba_backsub_kernel, dim3(c->grid_vec), dim3(256), 0, c->stream, d);   // camera steps; points of the record-based path
+  switch (f.candidate) {
+    case StepForm::kCandFolded: {
+      // the groups' pass forms the candidate x + delta and its cost on the way (one pass over the observations less per iteration)
+      const int n_cam_wg = (d.N + 255) / 256;
+      if (f.cam_sums_launch) hipLaunchKernelGGL(ba_step_scalars_cam_kernel, dim3(n_cam_wg), dim3(256), 0, c->stream, d, inv_radius, d.part, 0);
+      launch_point_groups<kGroupBacksub>(c, inv_radius, c->lm.dmin, c->lm.dmax, d.grp_part);
+      hipLaunchKernelGGL(ba_step_reduce_kernel, dim3(8), dim3(1024), 0, c->stream, d.part, n_cam_wg, d.grp_part, (int)d.grp.n_sg, d.scalars);
+      if (d.n_priors) hipLaunchKernelGGL(ba_prior_kernel<false>, dim3(1), dim3(256), 0, c->stream, d, d.cposes, 1);
+      BA_LAUNCH_CHECK();
+      if ((rc = all_reduce(c, d.scalars + kSStepSq, 3))) return rc;   // (the cost's all-reduce: where the separate cost pass has it - ranks may differ in this form)
+      break;
+    }
+    case StepForm::kCandJacobianModel:   // Ceres' own form (trust_region_minimizer.cc:402-405): one more pass over the Jacobian records (of every observation: no point groups)
+      if (d.n_obs) hipLaunchKernelGGL(ba_model_cost_kernel, dim3(c->grid_obs), dim3(256), 0, c->stream, d, d.part);
+      hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, c->stream, d.part, d.n_obs ? c->grid_obs : 0, 1, 1, d.scalars,
+                         kSModel, 0);
+      if (d.n_priors) hipLaunchKernelGGL(ba_prior_model_kernel, dim3(1), dim3(256), 0, c->stream, d);
+      BA_LAUNCH_CHECK();
+      if ((rc = all_reduce(c, d.scalars + kSModel, 1))) return rc;
+      break;
+    case StepForm::kCandStepScalars:
+      if (d.grp.n_sg) launch_point_groups<kGroupBacksub>(c, inv_radius, c->lm.dmin, c->lm.dmax);
+      hipLaunchKernelGGL(ba_step_scalars_kernel, dim3(c->grid_vec), dim3(256), 0, c->stream, d, inv_radius, d.part);   // model cost + candidate
+      hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, c->stream, d.part, c->grid_vec, 6, 6, d.scalars, kSCamStepSq, 0);
+      BA_LAUNCH_CHECK();
+      if ((rc = all_reduce(c, d.scalars + kSStepSq, 3))) return rc;   // the rank-local point parts; the camera parts are the same on every rank
+      break;
   }
   if (multi_rank(c)) {   // a point block that failed to invert on one rank fails the step everywhere
     hipLaunchKernelGGL(ba_pack_fail_kernel, dim3(1), dim3(1), 0, c->stream, d);
     BA_LAUNCH_CHECK();
     if ((rc = all_reduce(c, d.scalars + kSFail, 1, MVGX_REDUCE_MAX))) return rc;
   }
-  if (c->gmax_pending && multi_rank(c)) {   // max |gradient| of the grouped points (rank-local), from this step's forward pass
+  if (c->lm.gmax_pending && multi_rank(c)) {   // max |gradient| of the grouped points (rank-local), from this step's forward pass
     if ((rc = all_reduce(c, d.scalars + kSGmaxGrp, 1, MVGX_REDUCE_MAX))) return rc;
   }
   phase_end(c, kPhBacksub);
-  if ((rc = enqueue_candidate_and_cost(c, !c->model_cost_from_jacobian))) return rc;
+  if ((rc = enqueue_candidate_and_cost(c))) return rc;
   // the usual case - one rank, every point grouped, no priors, the candidate's cost from the back-substitution pass - launches the next
   // iteration's Jacobian evaluation ahead of the decision (two gated kernels: Gram + finish)
-  c->spec_done = false;
-  const bool spec = c->speculate && c->poll_scalars && fold_cand && !multi_rank(c) && !d.n_priors && d.n_pichunks && !c->model_cost_from_jacobian &&
-                    c->iteration < opt->max_num_iterations;
+  c->lm.spec_done = false;
+  const bool spec = f.speculate && c->lm.iteration < opt->max_num_iterations;
   if ((rc = read_scalars(c, spec ? 1 : 0, opt, spec ? &speculative_evaluation : nullptr, const_cast<mvgx_ba_options*>(opt)))) return rc;
-  if (c->gmax_pending) {   // the Jacobian evaluation before this step left its max |gradient| on the device (see there)
-    c->gradient_max_norm = std::max(c->h_scalars[kSGmax], c->h_scalars[kSGmaxGrp]);
-    c->gmax_pending = false;
-    c->gmax_resolved = true;
+  if (c->lm.gmax_pending) {   // the Jacobian evaluation before this step left its max |gradient| on the device (see there)
+    c->lm.gradient_max_norm = std::max(c->h_scalars[kSGmax], c->h_scalars[kSGmaxGrp]);
+    c->lm.gmax_pending = false;
+    c->lm.gmax_resolved = true;
   }
-  *model_cost_change = c->model_cost_from_jacobian ? c->h_scalars[kSModel] : c->h_scalars[kSModelPt] + c->h_scalars[kSModelCam];
+  *model_cost_change = f.candidate == StepForm::kCandJacobianModel ? c->h_scalars[kSModel] : c->h_scalars[kSModelPt] + c->h_scalars[kSModelCam];
   const bool failed = multi_rank(c) ? (c->h_scalars[kSFail] != 0.0) : (*c->h_fail != 0);
   *ok = !failed && std::isfinite(*model_cost_change);
   return MVGX_OK;
@@ -4263,7 +4359,7 @@ int global_obs_count(mvgx_ba_ctx* c) {
 }
 
 double rmse_from(const mvgx_ba_ctx* c) {   // of the current x
-  return c->n_obs_global > 0 ? std::sqrt(c->x_sqerr / (2.0 * c->n_obs_global)) : 0.0;
+  return c->n_obs_global > 0 ? std::sqrt(c->lm.x_sqerr / (2.0 * c->n_obs_global)) : 0.0;
 }
 
 int start(mvgx_ba_ctx* c, const mvgx_ba_options* opt) {
@@ -4274,80 +4370,81 @@ int start(mvgx_ba_ctx* c, const mvgx_ba_options* opt) {
     if ((rc = setup_block_exchange(c, blocks))) return rc;
     if ((rc = setup_solver(c, blocks))) return rc;
   }
+  c->form = resolve_step_form(c);
   if ((rc = eval<false>(c, c->d.poses, c->d.intr, c->d.pts))) return rc;
   if ((rc = read_scalars(c))) return rc;
-  c->x_cost = c->h_scalars[kSCost];
-  c->x_sqerr = c->h_scalars[kSSqErr];
-  c->initial_rmse = rmse_from(c);
-  c->radius = opt->initial_radius;
-  c->decrease_factor = 2.0;
-  c->reuse_diagonal = false; c->x_norm_valid = false; c->last_successful = true;
-  c->iteration = 0; c->invalid = 0; c->successful = 0; c->termination = 1; c->finished = false;
+  c->lm.x_cost = c->h_scalars[kSCost];
+  c->lm.x_sqerr = c->h_scalars[kSSqErr];
+  c->lm.initial_rmse = rmse_from(c);
+  c->lm.radius = opt->initial_radius;
+  c->lm.decrease_factor = 2.0;
+  c->lm.reuse_diagonal = false; c->lm.x_norm_valid = false; c->lm.last_successful = true;
+  c->lm.iteration = 0; c->lm.invalid = 0; c->lm.successful = 0; c->lm.termination = 1; c->lm.finished = false;
   if ((rc = evaluate_gradient_and_jacobian(c, opt, true))) return rc;  // IterationZero
-  c->initial_cost = c->x_cost;
-  c->started = true;
+  c->lm.initial_cost = c->lm.x_cost;
+  c->lm.started = true;
   return MVGX_OK;
 }
 
-// One pass of the while-loop of TrustRegionMinimizer::Minimize. Sets c->finished when a termination test fires.
+// One pass of the while-loop of TrustRegionMinimizer::Minimize. Sets c->lm.finished when a termination test fires.
 int lm_iteration(mvgx_ba_ctx* c, const mvgx_ba_options* opt) {
   // FinalizeIterationAndCheckIfMinimizerCanContinue
-  if (c->last_successful) ++c->successful;
-  if (c->iteration >= opt->max_num_iterations) { c->termination = 1; c->finished = true; return MVGX_OK; }
-  if (c->last_successful && !c->gmax_pending && c->gradient_max_norm <= opt->gradient_tolerance) { c->termination = 0; c->finished = true; return MVGX_OK; }
-  if (c->radius <= opt->min_radius) { c->termination = 0; c->finished = true; return MVGX_OK; }
-  ++c->iteration;
+  if (c->lm.last_successful) ++c->lm.successful;
+  if (c->lm.iteration >= opt->max_num_iterations) { c->lm.termination = 1; c->lm.finished = true; return MVGX_OK; }
+  if (c->lm.last_successful && !c->lm.gmax_pending && c->lm.gradient_max_norm <= opt->gradient_tolerance) { c->lm.termination = 0; c->lm.finished = true; return MVGX_OK; }
+  if (c->lm.radius <= opt->min_radius) { c->lm.termination = 0; c->lm.finished = true; return MVGX_OK; }
+  ++c->lm.iteration;
   bool ok = false;
   double model_cost_change = 0;
-  c->gmax_resolved = false;
+  c->lm.gmax_resolved = false;
   int rc = compute_step(c, &ok, &model_cost_change, opt);
   if (rc) return rc;
-  if (c->spec_done && !((int)c->h_scalars[kSCount + 2] & 2)) ++c->spec_stats[2];   // (a rejected step, or one the tolerance tests end on)
+  if (c->lm.spec_done && !((int)c->h_scalars[kSCount + 2] & 2)) ++c->spec_stats[2];   // (a rejected step, or one the tolerance tests end on)
   // The gradient test of this iteration's start, made now that the max |gradient| of the last Jacobian evaluation has come back
   // with the step's scalars (one host round trip per iteration instead of two): the step just computed is dropped, as if the
   // test had fired before it.
-  if (c->gmax_resolved && c->last_successful && c->gradient_max_norm <= opt->gradient_tolerance) {
-    --c->iteration; c->termination = 0; c->finished = true; return MVGX_OK;
+  if (c->lm.gmax_resolved && c->lm.last_successful && c->lm.gradient_max_norm <= opt->gradient_tolerance) {
+    --c->lm.iteration; c->lm.termination = 0; c->lm.finished = true; return MVGX_OK;
   }
-  c->reuse_diagonal = true;
+  c->lm.reuse_diagonal = true;
   if (!(ok && model_cost_change > 0.0)) {  // HandleInvalidStep + StepIsInvalid (= StepRejected(0))
-    if (++c->invalid >= opt->max_consecutive_invalid_steps) { c->termination = 2; c->finished = true; return MVGX_OK; }
-    c->radius = c->radius / c->decrease_factor; c->decrease_factor *= 2.0;
-    c->last_successful = false;
+    if (++c->lm.invalid >= opt->max_consecutive_invalid_steps) { c->lm.termination = 2; c->lm.finished = true; return MVGX_OK; }
+    c->lm.radius = c->lm.radius / c->lm.decrease_factor; c->lm.decrease_factor *= 2.0;
+    c->lm.last_successful = false;
     return MVGX_OK;
   }
-  c->invalid = 0;
+  c->lm.invalid = 0;
   double step_norm, x_norm, cand;
   candidate_results(c, &step_norm, &x_norm, &cand);
-  if (!c->x_norm_valid) x_norm = -1.0;  // Init() leaves x_norm_ = -1 until the first accepted step
+  if (!c->lm.x_norm_valid) x_norm = -1.0;  // Init() leaves x_norm_ = -1 until the first accepted step
   if (opt->verbose)
-    fprintf(stderr, "[mvgx ba] it %d cost %.9e cand %.9e model %.6e radius %.3e |step| %.3e\n", c->iteration, c->x_cost, cand,
-            model_cost_change, c->radius, step_norm);
-  if (step_norm <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance)) { c->termination = 0; c->finished = true; return MVGX_OK; }
-  if (std::fabs(c->x_cost - cand) <= opt->function_tolerance * c->x_cost) { c->termination = 0; c->finished = true; return MVGX_OK; }
-  const double relative_decrease = (c->x_cost - cand) / model_cost_change;
+    fprintf(stderr, "[mvgx ba] it %d cost %.9e cand %.9e model %.6e radius %.3e |step| %.3e\n", c->lm.iteration, c->lm.x_cost, cand,
+            model_cost_change, c->lm.radius, step_norm);
+  if (step_norm <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance)) { c->lm.termination = 0; c->lm.finished = true; return MVGX_OK; }
+  if (std::fabs(c->lm.x_cost - cand) <= opt->function_tolerance * c->lm.x_cost) { c->lm.termination = 0; c->lm.finished = true; return MVGX_OK; }
+  const double relative_decrease = (c->lm.x_cost - cand) / model_cost_change;
   const bool accept = relative_decrease > opt->min_relative_decrease;
   // (a Jacobian evaluation launched ahead runs on the device's own decision: the two are the same test on the same doubles)
-  const int dev_word = c->spec_done ? (int)c->h_scalars[kSCount + 2] : 0;   // accept + 2 gate
-  MVGX_REQUIRE(!c->spec_done || accept == ((dev_word & 1) != 0), MVGX_ERR_NUMERIC, "internal error: the device's accept decision differs from the host's");
-  if (c->spec_done && !(dev_word & 2)) c->spec_done = false;   // (the gate stayed shut - the device saw the solve end here: the evaluation is launched below, as without the look-ahead)
+  const int dev_word = c->lm.spec_done ? (int)c->h_scalars[kSCount + 2] : 0;   // accept + 2 gate
+  MVGX_REQUIRE(!c->lm.spec_done || accept == ((dev_word & 1) != 0), MVGX_ERR_NUMERIC, "internal error: the device's accept decision differs from the host's");
+  if (c->lm.spec_done && !(dev_word & 2)) c->lm.spec_done = false;   // (the gate stayed shut - the device saw the solve end here: the evaluation is launched below, as without the look-ahead)
   if (accept) {
     if ((rc = accept_candidate(c))) return rc;
-    c->x_cost = cand;   // the cost pass of the candidate IS the cost at the new x
-    c->x_sqerr = c->h_scalars[kSSqErr];
-    if (c->spec_done) {   // the evaluation at the new x is on its way: what it leaves on the host side
+    c->lm.x_cost = cand;   // the cost pass of the candidate IS the cost at the new x
+    c->lm.x_sqerr = c->h_scalars[kSSqErr];
+    if (c->lm.spec_done) {   // the evaluation at the new x is on its way: what it leaves on the host side
       ++c->spec_stats[1];
-      c->fail_clear = c->d.n_pichunks != 0;
-      c->dmin = opt->min_lm_diagonal; c->dmax = opt->max_lm_diagonal;
-      c->gmax_pending = true;
+      c->lm.fail_clear = c->d.n_pichunks != 0;
+      c->lm.dmin = opt->min_lm_diagonal; c->lm.dmax = opt->max_lm_diagonal;
+      c->lm.gmax_pending = true;
     } else if ((rc = evaluate_gradient_and_jacobian(c, opt, false))) return rc;
-    c->radius = c->radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
-    c->radius = std::min(opt->max_radius, c->radius);
-    c->decrease_factor = 2.0; c->reuse_diagonal = false;
-    c->last_successful = true; c->x_norm_valid = true;
+    c->lm.radius = c->lm.radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
+    c->lm.radius = std::min(opt->max_radius, c->lm.radius);
+    c->lm.decrease_factor = 2.0; c->lm.reuse_diagonal = false;
+    c->lm.last_successful = true; c->lm.x_norm_valid = true;
   } else {
-    c->radius = c->radius / c->decrease_factor; c->decrease_factor *= 2.0;
-    c->last_successful = false;
+    c->lm.radius = c->lm.radius / c->lm.decrease_factor; c->lm.decrease_factor *= 2.0;
+    c->lm.last_successful = false;
   }
   return MVGX_OK;
 }
@@ -4356,16 +4453,16 @@ int fill_summary(mvgx_ba_ctx* c, mvgx_ba_summary* s) {
   if (!s) return MVGX_OK;
   // (cost and squared error at the final x were computed when that x was evaluated as a candidate: no pass of their own)
   MVGX_HIP(hipStreamSynchronize(c->stream));
-  s->num_iterations = c->iteration;
-  s->num_successful_steps = c->successful;
-  s->termination = c->termination;
-  s->initial_cost = c->initial_cost;
-  s->final_cost = c->x_cost;
-  s->initial_rmse = c->initial_rmse;
+  s->num_iterations = c->lm.iteration;
+  s->num_successful_steps = c->lm.successful;
+  s->termination = c->lm.termination;
+  s->initial_cost = c->lm.initial_cost;
+  s->final_cost = c->lm.x_cost;
+  s->initial_rmse = c->lm.initial_rmse;
   s->final_rmse = rmse_from(c);
   phase_collect(c);   // (the stream is idle)
-  s->jacobian_ms = c->phase_ms[kPhJacobian]; s->schur_ms = c->phase_ms[kPhSchur]; s->solve_ms = c->phase_ms[kPhSolve];
-  s->backsub_ms = c->phase_ms[kPhBacksub]; s->cost_ms = c->phase_ms[kPhCost];
+  s->jacobian_ms = c->timing.phase_ms[kPhJacobian]; s->schur_ms = c->timing.phase_ms[kPhSchur]; s->solve_ms = c->timing.phase_ms[kPhSolve];
+  s->backsub_ms = c->timing.phase_ms[kPhBacksub]; s->cost_ms = c->timing.phase_ms[kPhCost];
   return MVGX_OK;
 }
 
@@ -4503,15 +4600,21 @@ struct CreateTimer {
   void total() { t_prev = t_enter; (*this)("total (before the locals are released)"); }
 };
 
-// Every environment setting of a context, read once by mvgx_ba_create (after the counts of Dev are set).
+// Every MVGX_BA_* setting a context uses, read once by mvgx_ba_create into mvgx_ba_ctx::Settings (after the counts of Dev are set); the
+// debug switches of the kernels go to their device symbols.
 void read_settings(mvgx_ba_ctx* c) {
-  if (const char* env = getenv("MVGX_BA_SPECULATE")) c->speculate = atoi(env) != 0;
-  if (const char* env = getenv("MVGX_BA_POLL_SCALARS")) c->poll_scalars = c->poll_scalars && atoi(env) != 0;
-  if (const char* env = getenv("MVGX_BA_SEPARATE_COST")) c->fold_candidate = atoi(env) == 0;
-  if (const char* env = getenv("MVGX_BA_CHAIN_FUSE")) c->chain_fuse_max_tasks = atoi(env);
-  if (const char* env = getenv("MVGX_BA_LOOKAHEAD")) c->lookahead = atoi(env) != 0;
-  if (const char* env = getenv("MVGX_BA_BACKSOLVE_FLAGS")) c->bs_one_launch = atoi(env) != 0;
-  c->phase_timing = getenv("MVGX_BA_PHASE_TIMING") != nullptr;
+  if (const char* env = getenv("MVGX_BA_SPECULATE")) c->set.speculate = atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_POLL_SCALARS")) c->set.poll_scalars = c->set.poll_scalars && atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_SEPARATE_COST")) c->set.fold_candidate = atoi(env) == 0;
+  if (const char* env = getenv("MVGX_BA_CHAIN_FUSE")) c->set.chain_fuse_max_tasks = atoi(env);
+  if (const char* env = getenv("MVGX_BA_LOOKAHEAD")) c->set.lookahead = atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_BACKSOLVE_FLAGS")) c->set.bs_one_launch = atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_BACKSOLVE_CHAIN")) c->set.backsolve_chain = atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_ND_LEAF_COLS")) c->set.plan_params.leaf_cols = std::max(64, atoi(env));
+  if (const char* env = getenv("MVGX_BA_ND_SEP_SLACK")) c->set.plan_params.sep_weight_slack = std::max(1.0, atof(env));   // (1: only level sets as light as the lightest compete on balance)
+  if (const char* env = getenv("MVGX_BA_LOOKAHEAD_MAX_PRE")) c->set.plan_params.max_pre = std::max(0, atoi(env));   // (tests: the schedule's fall-back forms)
+  c->set.plan_debug = getenv("MVGX_BA_PLAN_DEBUG") != nullptr;
+  c->set.phase_timing = getenv("MVGX_BA_PHASE_TIMING") != nullptr;
   if (getenv("MVGX_BA_FACTOR_DEBUG")) { const int one = 1; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_factor_debug), &one, sizeof(one)); }
   {   // (a synchronous copy: only when the setting changes)
     static std::atomic<int> last_on{0};
@@ -4522,24 +4625,24 @@ void read_settings(mvgx_ba_ctx* c) {
     const int compact_on = env_c ? (atoi(env_c) != 0) : 1;
     if (last_compact.exchange(compact_on) != compact_on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_group_compact), &compact_on, sizeof(compact_on));
   }
-  if (const char* env = getenv("MVGX_BA_MODEL_COST")) c->model_cost_from_jacobian = !strcmp(env, "jacobian");
+  if (const char* env = getenv("MVGX_BA_MODEL_COST")) c->set.model_cost_from_jacobian = !strcmp(env, "jacobian");
   if (const char* env = getenv("MVGX_BA_SOLVER")) {
-    c->solver_mode = !strcmp(env, "dense") ? 1 : !strcmp(env, "sparse") ? 2 : 0;
-    c->solver_from_env = true;   // ("auto" included: the library's rule, whatever the caller's options say)
+    c->set.solver_mode = !strcmp(env, "dense") ? 1 : !strcmp(env, "sparse") ? 2 : 0;
+    c->set.solver_from_env = true;   // ("auto" included: the library's rule, whatever the caller's options say)
   }
-  if (const char* env = getenv("MVGX_BA_TWO_LEVEL_MIN_N")) c->two_level_min_n = std::max(1, atoi(env));
-  if (const char* env = getenv("MVGX_BA_UPDATE128_MIN_TILES")) c->update128_min_tiles = std::max(1, atoi(env));
+  if (const char* env = getenv("MVGX_BA_TWO_LEVEL_MIN_N")) c->set.two_level_min_n = std::max(1, atoi(env));
+  if (const char* env = getenv("MVGX_BA_UPDATE128_MIN_TILES")) c->set.update128_min_tiles = std::max(1, atoi(env));
   // MVGX_BA_GROUPS=0 disables the point groups; so does MVGX_BA_MODEL_COST=jacobian (Ceres' form of the model cost reads the Jacobian
   // records of every observation).
-  if (const char* env = getenv("MVGX_BA_GROUPS")) c->groups_on = atoi(env) != 0;
+  if (const char* env = getenv("MVGX_BA_GROUPS")) c->set.groups_on = atoi(env) != 0;
   // A supergroup covers up to 2048 observations (8 groups); problems of 4 M observations and more - enough supergroups to fill the device
   // several times either way - up to 4096 (16 groups): fewer prologues, MFMA flushes and partial blocks. MVGX_BA_SG_GROUPS=n sets the
   // limit (sweeps of calls 83 / 84 / 86 with the largest-first launch order: C3 0.625 ms at 8, 0.654 at 12, 0.715 at 16, 0.726 at 6;
   // C5 1.747 ms at 8, 1.729 at 12, 1.714 at 16, 1.754 at 24, 1.914 at 6).
-  c->sg_max_groups = c->d.n_obs >= 4000000ull ? 4096 / kGroupThreads : 2048 / kGroupThreads;
-  if (const char* env = getenv("MVGX_BA_SG_GROUPS")) c->sg_max_groups = std::max(1, std::min(64, atoi(env)));
-  c->sg_index_order = getenv("MVGX_BA_SG_INDEX_ORDER") != nullptr;
-  if (const char* env = getenv("MVGX_BA_GENERIC_MODELS")) c->generic_models = atoi(env) != 0;
+  c->set.sg_max_groups = c->d.n_obs >= 4000000ull ? 4096 / kGroupThreads : 2048 / kGroupThreads;
+  if (const char* env = getenv("MVGX_BA_SG_GROUPS")) c->set.sg_max_groups = std::max(1, std::min(64, atoi(env)));
+  c->set.sg_index_order = getenv("MVGX_BA_SG_INDEX_ORDER") != nullptr;
+  if (const char* env = getenv("MVGX_BA_GENERIC_MODELS")) c->set.generic_models = atoi(env) != 0;
 }
 
 constexpr size_t kObsGrain = 16384;   // observations per work item of the structure build's loops
@@ -4946,12 +5049,12 @@ int stitch_groups(std::vector<BucketGroups>& per_bucket, mvgx::HostArena& ha, Ho
 // (lowest pose, highest pose, hash of the pose set); consecutive points join a group while the union of their poses stays within
 // kGroupCams, the union of their intrinsics within kGroupIntr and the group within kGroupPts points. A group that closes because
 // it is full hands its camera set to the next one: groups with the same set form a supergroup (one workgroup, one set of partial
-// blocks), up to c->sg_max_groups of them. Groups of fewer than kGroupMinPts points are dissolved unless they continue a supergroup
+// blocks), up to c->set.sg_max_groups of them. Groups of fewer than kGroupMinPts points are dissolved unless they continue a supergroup
 // (their points stay on the record-based path, as do long tracks and constant points).
 int build_point_groups(const mvgx_ba_problem* p, const mvgx_ba_ctx* c, mvgx::HostArena& ha, HostStructure& S, CreateTimer& tick) {
   const uint32_t n_pts = p->n_points, n_poses = p->n_poses;
   S.in_group.assign(n_pts, 0);
-  if (!c->groups_on || c->model_cost_from_jacobian || !n_poses || !n_pts) return MVGX_OK;
+  if (!c->set.groups_on || c->set.model_cost_from_jacobian || !n_poses || !n_pts) return MVGX_OK;
   const unsigned T = S.T;
   const std::vector<uint32_t>& pt_start = S.pt_start;
   std::vector<uint32_t> lo_pose(n_pts, UINT32_MAX), hi_pose(n_pts, 0);
@@ -4991,7 +5094,7 @@ int build_point_groups(const mvgx_ba_problem* p, const mvgx_ba_ctx* c, mvgx::Hos
       for (uint32_t q = q0; q < q1; ++q) n_e += pt_start[order[q] + 1] - pt_start[order[q]];
       B.eobs.reserve(n_e); B.eq.reserve(n_e); B.pts.reserve(q1 - q0); B.nk0.reserve(q1 - q0);
     }
-    GroupSweep sweep{S, c->sg_max_groups, B};
+    GroupSweep sweep{S, c->set.sg_max_groups, B};
     for (uint32_t q = q0; q < q1; ++q) {
       // (the points of a bucket lie anywhere in the caller's order - a scene flattened from a hash map: their rows are fetched ahead,
       // the CSR entry sixteen points ahead, the rows it names eight points ahead; 1.7 -> ms of this phase at 1 M observations were misses)
@@ -5151,7 +5254,7 @@ int staged_copy(mvgx_ba_ctx* c, mvgx::HostArena& ha, E* dev, const E* src, size_
 }
 
 // The VALUES of a problem on the device (mvgx_ba_create, mvgx_ba_update): the parameters, the prior targets, and the image points and
-// weights in point order - through the permutation c->h_perm when the caller's list is not in it.
+// weights in point order - through the permutation c->rebind.h_perm when the caller's list is not in it.
 int upload_values(mvgx_ba_ctx* c, const mvgx_ba_problem* p, mvgx::HostArena& ha) {
   Dev& d = c->d;
   const uint64_t no = d.n_obs;
@@ -5161,7 +5264,7 @@ int upload_values(mvgx_ba_ctx* c, const mvgx_ba_problem* p, mvgx::HostArena& ha)
       (rc = staged_copy(c, ha, d.prior_center, p->prior_center, (size_t)d.n_priors * 3)) ||
       (rc = staged_copy(c, ha, d.prior_weight, p->prior_weight, (size_t)d.n_priors * 3)))
     return rc;
-  if (c->h_perm.empty()) {
+  if (c->rebind.h_perm.empty()) {
     if ((rc = staged_copy(c, ha, d.oxy, p->obs_xy, (size_t)(2 * no)))) return rc;
     if (p->obs_weight && (rc = staged_copy(c, ha, d.oweight, p->obs_weight, (size_t)no))) return rc;
     return MVGX_OK;
@@ -5170,7 +5273,7 @@ int upload_values(mvgx_ba_ctx* c, const mvgx_ba_problem* p, mvgx::HostArena& ha)
   if ((rc = ha.array(&g_xy, (size_t)(2 * no))) || (p->obs_weight && (rc = ha.array(&g_w, (size_t)no)))) return rc;
   parallel_for_dynamic(obs_grains(no), 1, host_threads(no), [&](size_t g, unsigned) {
     for (uint64_t k = g * kObsGrain, e = std::min<uint64_t>(no, (g + 1) * kObsGrain); k < e; ++k) {
-      const uint64_t s_ = c->h_perm[k];
+      const uint64_t s_ = c->rebind.h_perm[k];
       g_xy[2 * k] = p->obs_xy[2 * s_]; g_xy[2 * k + 1] = p->obs_xy[2 * s_ + 1];
       if (g_w) g_w[k] = p->obs_weight[s_];
     }
@@ -5207,9 +5310,9 @@ int upload_structure(mvgx_ba_ctx* c, HostStructure& S, CreateTimer& tick) {
 #define UPN(field, ptr, n) if ((rc = dev_upload_n(c->pool, &d.field, ptr, (size_t)(n), c->stream))) return rc
 #define AL(field, n) if ((rc = dev_alloc(c->pool, &d.field, (size_t)(n)))) return rc
   d.n_islots = (int)S.slot_intr.size(); d.n_pi = (int)S.pi_intr.size(); d.n_pichunks = (int)S.pichunk_lo.size();
-  c->h_pose_used = S.used.pose; c->h_intr_used = S.used.intr; c->h_pt_free = S.used.pt;
-  c->n_obs_rmse_all = S.used.n_rmse;
-  c->h_blocks = std::move(S.h_blocks);
+  c->rebind.h_pose_used = S.used.pose; c->rebind.h_intr_used = S.used.intr; c->rebind.h_pt_free = S.used.pt;
+  c->rebind.n_obs_rmse_all = S.used.n_rmse;
+  c->solver.h_blocks = std::move(S.h_blocks);
   c->diag_blocks_complete = S.diag_blocks_complete;
   UP(pt_start, S.pt_start); UP(ptk_start, S.ptk_start); UP(slot_intr, S.slot_intr); UP(slot_point, S.slot_point);
   AL(cam_active, d.N); AL(cam_counts, d.N); AL(pt_free, d.n_pts);
@@ -5259,7 +5362,7 @@ int upload_structure(mvgx_ba_ctx* c, HostStructure& S, CreateTimer& tick) {
     d.grp.n_ungrouped = (uint32_t)S.n_ungrouped;
     c->h_sg_order = std::move(S.sg_order);
     c->n_sg_wide = S.n_sg_wide;
-    c->n_gentries = S.n_gentries;
+    c->rebind.n_gentries = S.n_gentries;
     UP(grp.sg_start, S.sg_start); UP(grp.sg_order, c->h_sg_order); UP(grp.obs_start, S.g_obs_start); UP(grp.pt_start, S.g_pt_start);
     UP(grp.pts, S.g_pts); UP(grp.pt_estart, S.g_pt_estart); UP(grp.pt_ksplit, S.g_pt_ksplit);
     UPN(grp.eq, S.g_eq, S.n_gentries); UPN(grp.eobs, S.g_eobs, S.n_gentries);
@@ -5297,7 +5400,7 @@ int set_kernel_attributes(mvgx_ba_ctx* c, const mvgx_ba_problem* p) {
   MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sp_level_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDiagLds));
   MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_panel_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds));
   MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_update128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kUpd128Lds));
-  c->pinhole_family = !c->generic_models;
+  c->pinhole_family = !c->set.generic_models;
   for (uint32_t k = 0; k < p->n_intrinsics; ++k) {
     const int m = p->intr_model[k];
     c->pinhole_family = c->pinhole_family && (m == mvgx_ba::kCamPinhole || m == mvgx_ba::kCamRadial1 || m == mvgx_ba::kCamRadial3 || m == mvgx_ba::kCamBrown);
@@ -5315,17 +5418,17 @@ int bind_values(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_t* obs_ena
   int rc;
   UsedBlocks sub;   // with a subset: the blocks of the observations that are on
   if (obs_enabled) {
-    sub = used_blocks(p, c->h_perm, obs_enabled);
-    for (uint32_t j = 0; j < d.n_pts; ++j) sub.pt[j] = c->h_pt_free[j] && sub.pt[j];
+    sub = used_blocks(p, c->rebind.h_perm, obs_enabled);
+    for (uint32_t j = 0; j < d.n_pts; ++j) sub.pt[j] = c->rebind.h_pt_free[j] && sub.pt[j];
   }
-  const std::vector<uint8_t>& pose_used = obs_enabled ? sub.pose : c->h_pose_used;
-  const std::vector<uint8_t>& intr_used = obs_enabled ? sub.intr : c->h_intr_used;
-  const std::vector<uint8_t>& pt_free = obs_enabled ? sub.pt : c->h_pt_free;
-  const double n_rmse = obs_enabled ? sub.n_rmse : c->n_obs_rmse_all;
+  const std::vector<uint8_t>& pose_used = obs_enabled ? sub.pose : c->rebind.h_pose_used;
+  const std::vector<uint8_t>& intr_used = obs_enabled ? sub.intr : c->rebind.h_intr_used;
+  const std::vector<uint8_t>& pt_free = obs_enabled ? sub.pt : c->rebind.h_pt_free;
+  const double n_rmse = obs_enabled ? sub.n_rmse : c->rebind.n_obs_rmse_all;
   if (sub.any_off) {
-    if (!c->odisabled_buf && (rc = dev_alloc(c->pool, &c->odisabled_buf, (size_t)no))) return rc;
-    MVGX_HIP(hipMemcpyAsync(c->odisabled_buf, sub.off.data(), (size_t)no, hipMemcpyHostToDevice, c->stream));
-    d.odisabled = c->odisabled_buf;
+    if (!c->rebind.odisabled_buf && (rc = dev_alloc(c->pool, &c->rebind.odisabled_buf, (size_t)no))) return rc;
+    MVGX_HIP(hipMemcpyAsync(c->rebind.odisabled_buf, sub.off.data(), (size_t)no, hipMemcpyHostToDevice, c->stream));
+    d.odisabled = c->rebind.odisabled_buf;
   } else {
     d.odisabled = nullptr;
   }
@@ -5341,8 +5444,8 @@ int bind_values(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_t* obs_ena
   d.huber_a = p->huber_a;
   d.prior_huber_a = p->prior_huber_a;
   if (no) hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, c->stream, d.pi_obs, (uint32_t)no, d.opt, d.oxy, d.pi_pt, d.pi_xy);
-  if (c->n_gentries)
-    hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((c->n_gentries + 255) / 256)), dim3(256), 0, c->stream, d.grp.eobs, (uint32_t)c->n_gentries,
+  if (c->rebind.n_gentries)
+    hipLaunchKernelGGL(ba_gather_lists_kernel, dim3((unsigned)((c->rebind.n_gentries + 255) / 256)), dim3(256), 0, c->stream, d.grp.eobs, (uint32_t)c->rebind.n_gentries,
                        d.opt, d.oxy, static_cast<uint32_t*>(nullptr), d.grp.exy);
   BA_LAUNCH_CHECK();
   MVGX_HIP(hipMemsetAsync(d.scalars, 0, (kSCount + 1) * sizeof(double), c->stream));
@@ -5411,7 +5514,7 @@ int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
     mvgx_ba_ctx* c;
     ~Guard() { if (c) mvgx_ba_destroy(c); }
   } guard{c};
-  c->fingerprint = mvgx::ba_fingerprint(p);
+  c->rebind.fingerprint = mvgx::ba_fingerprint(p);
   tick("validation, fingerprint");
   MVGX_HIP(hipGetDevice(&c->device));
   if ((rc = mvgx::acquire_stream(&c->stream))) return rc;
@@ -5421,7 +5524,7 @@ int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
   tick("events");
   MVGX_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_scalars), (kSCount + 3) * sizeof(double), hipHostMallocDefault));
   memset(c->h_scalars, 0, (kSCount + 3) * sizeof(double));
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_scalars_dev), c->h_scalars, 0) != hipSuccess) { (void)hipGetLastError(); c->poll_scalars = false; }
+  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_scalars_dev), c->h_scalars, 0) != hipSuccess) { (void)hipGetLastError(); c->set.poll_scalars = false; }
   c->h_fail = reinterpret_cast<int*>(c->h_scalars + kSCount);
   tick("page-locked scalars");
   Dev& d = c->d;
@@ -5434,7 +5537,7 @@ int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
   HostStructure S;
   S.T = host_threads(no);
   if ((rc = build_point_order(p, ha, S))) return rc;
-  if (!S.sorted) c->h_perm.assign(S.orig, S.orig + no);
+  if (!S.sorted) c->rebind.h_perm.assign(S.orig, S.orig + no);
   // the values go up at once (their DMA overlaps the structure build); mvgx_ba_update copies into the same arrays
   if ((rc = dev_alloc(c->pool, &d.poses, (size_t)d.n_poses * 6)) || (rc = dev_alloc(c->pool, &d.intr, (size_t)d.n_intr * 8)) ||
       (rc = dev_alloc(c->pool, &d.pts, (size_t)d.n_pts * 3)) || (rc = dev_alloc(c->pool, &d.oxy, (size_t)(2 * no))) ||
@@ -5452,7 +5555,7 @@ int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
   tick("slots, pose / intrinsic lists");
   if ((rc = build_point_groups(p, c, ha, S, tick))) return rc;
   tick("  entry starts");
-  build_group_destinations(p, c->sg_index_order, S, tick);
+  build_group_destinations(p, c->set.sg_index_order, S, tick);
   tick("point groups");
   if ((rc = build_product_lists(p, ha, S, tick))) return rc;
   tick("pose-intr / intr-intr products");
@@ -5461,7 +5564,7 @@ int mvgx_ba_create(int device, const mvgx_ba_problem* p, mvgx_ba_ctx** out) {
   tick("product lists upload (enqueue)");
   if ((rc = bind_values(c, p, nullptr))) return rc;
   tick("stream drain");
-  if (!mvgx::ba_create_plan_deferred() && (rc = plan_solver(c, c->h_blocks))) return rc;
+  if (!mvgx::ba_create_plan_deferred() && (rc = plan_solver(c, c->solver.h_blocks))) return rc;
   tick("reduced solve: symbolic phase");
   tick.total();
   guard.c = nullptr;
@@ -5501,7 +5604,7 @@ int mvgx_ba_destroy(mvgx_ba_ctx* c) {
   if (c->h_scalars) (void)hipHostFree(c->h_scalars);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
-  for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->timing.ev_pool) (void)hipEventDestroy(e);
   mvgx::rccl_destroy(c->rccl);
   mvgx::release_stream(c->device, c->stream);   // (synchronised above)
   delete c;
@@ -5535,7 +5638,7 @@ static int ba_update_impl(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_
     MVGX_REQUIRE(!obs_enabled, MVGX_ERR_UNSUPPORTED, "mvgx_ba_update_subset: not available on a multi-device context");
     return mvgx::ba_multi_update(c->multi, p);
   }
-  if (!(mvgx::ba_fingerprint(p) == c->fingerprint)) {
+  if (!(mvgx::ba_fingerprint(p) == c->rebind.fingerprint)) {
     set_error("mvgx_ba_update: the problem's structure is not the one this context was created from");
     return MVGX_ERR_STRUCTURE;
   }
@@ -5549,8 +5652,8 @@ static int ba_update_impl(mvgx_ba_ctx* c, const mvgx_ba_problem* p, const uint8_
   } drain{c};
   int rc;
   if ((rc = upload_values(c, p, ha)) || (rc = bind_values(c, p, obs_enabled))) return rc;
-  c->started = false; c->finished = false;
-  c->gmax_pending = false; c->gmax_resolved = false; c->fail_clear = false; c->fold_cand_now = false; c->candidate_cost_done = false;
+  c->lm.started = false; c->lm.finished = false;
+  c->lm.gmax_pending = false; c->lm.gmax_resolved = false; c->lm.fail_clear = false;
   drain.ok = true;
   return MVGX_OK;
 }
@@ -5629,11 +5732,11 @@ int mvgx_debug_dense_solve(const double* a, const double* b, int n, int two_leve
 int mvgx_ba_comm_init(mvgx_ba_ctx* c, int world, int rank, const void* unique_id128) {
   MVGX_REQUIRE(c && unique_id128, MVGX_ERR_ARG, "mvgx_ba_comm_init: NULL argument");
   MVGX_REQUIRE(!c->multi, MVGX_ERR_STATE, "mvgx_ba_comm_init: a multi-device context has its own exchange");
-  MVGX_REQUIRE(!c->started, MVGX_ERR_STATE, "mvgx_ba_comm_init after the solve has started");
+  MVGX_REQUIRE(!c->lm.started, MVGX_ERR_STATE, "mvgx_ba_comm_init after the solve has started");
   MVGX_HIP(hipSetDevice(c->device));
   mvgx::rccl_destroy(c->rccl);
   c->rccl = nullptr;
-  c->plan_ready = false;   // the plan is made on the union of the ranks' blocks
+  c->solver.plan_ready = false;   // the plan is made on the union of the ranks' blocks
   int rc = mvgx::rccl_init(&c->rccl, world, rank, unique_id128);
   if (rc) return rc;
   if ((rc = mvgx::rccl_self_check(c->rccl, c->stream))) { mvgx::rccl_destroy(c->rccl); c->rccl = nullptr; }
@@ -5645,7 +5748,7 @@ int mvgx_ba_set_allreduce(mvgx_ba_ctx* c, mvgx_allreduce_f64 fn, void* user) {
   MVGX_REQUIRE(!c->multi, MVGX_ERR_STATE, "mvgx_ba_set_allreduce: a multi-device context has its own exchange");
   c->allreduce = fn;
   c->allreduce_user = user;
-  c->plan_ready = false;   // the plan is made on the union of the ranks' blocks
+  c->solver.plan_ready = false;   // the plan is made on the union of the ranks' blocks
   return MVGX_OK;
 }
 
@@ -5656,15 +5759,15 @@ int mvgx_ba_lm_iteration(mvgx_ba_ctx* c, const mvgx_ba_options* opt, mvgx_ba_sum
   MVGX_HIP(hipSetDevice(c->device));
   int rc;
   MVGX_HIP(hipEventRecord(c->ev0, c->stream));
-  if (!c->started && (rc = start(c, opt))) return rc;
-  if (!c->finished && (rc = lm_iteration(c, opt))) return rc;
+  if (!c->lm.started && (rc = start(c, opt))) return rc;
+  if (!c->lm.finished && (rc = lm_iteration(c, opt))) return rc;
   MVGX_HIP(hipEventRecord(c->ev1, c->stream));
   MVGX_HIP(hipEventSynchronize(c->ev1));
   float ms = 0;
   MVGX_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if ((rc = fill_summary(c, summary))) return rc;
   if (summary) { summary->total_ms = ms; summary->iter_ms_mean = ms; }
-  return c->termination == 2 ? MVGX_ERR_NUMERIC : MVGX_OK;
+  return c->lm.termination == 2 ? MVGX_ERR_NUMERIC : MVGX_OK;
 }
 
 int mvgx_ba_solve(mvgx_ba_ctx* c, const mvgx_ba_options* opt, mvgx_ba_summary* summary) {
@@ -5674,17 +5777,17 @@ int mvgx_ba_solve(mvgx_ba_ctx* c, const mvgx_ba_options* opt, mvgx_ba_summary* s
   MVGX_HIP(hipSetDevice(c->device));
   int rc;
   MVGX_HIP(hipEventRecord(c->ev0, c->stream));
-  c->started = false;
+  c->lm.started = false;
   if ((rc = start(c, opt))) return rc;
-  while (!c->finished)
+  while (!c->lm.finished)
     if ((rc = lm_iteration(c, opt))) return rc;
   MVGX_HIP(hipEventRecord(c->ev1, c->stream));
   MVGX_HIP(hipEventSynchronize(c->ev1));
   float ms = 0;
   MVGX_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if ((rc = fill_summary(c, summary))) return rc;
-  if (summary) { summary->total_ms = ms; summary->iter_ms_mean = c->iteration ? ms / c->iteration : ms; }
-  if (c->termination == 2) { set_error("mvgx_ba_solve: %d consecutive invalid steps (linear solve failed or model cost did not decrease)", c->invalid); return MVGX_ERR_NUMERIC; }
+  if (summary) { summary->total_ms = ms; summary->iter_ms_mean = c->lm.iteration ? ms / c->lm.iteration : ms; }
+  if (c->lm.termination == 2) { set_error("mvgx_ba_solve: %d consecutive invalid steps (linear solve failed or model cost did not decrease)", c->lm.invalid); return MVGX_ERR_NUMERIC; }
   return MVGX_OK;
 }
 
@@ -5757,26 +5860,26 @@ int mvgx_ba_set_linear_solver(mvgx_ba_ctx* c, int kind) {
   MVGX_REQUIRE(c, MVGX_ERR_ARG, "mvgx_ba_set_linear_solver: NULL context");
   MVGX_REQUIRE(kind >= MVGX_BA_LINEAR_SOLVER_AUTO && kind <= MVGX_BA_LINEAR_SOLVER_SPARSE_PREFERRED, MVGX_ERR_ARG, "mvgx_ba_set_linear_solver: kind %d", kind);
   if (c->multi) return mvgx::ba_multi_set_linear_solver(c->multi, kind);
-  if (c->solver_from_env || kind == c->solver_mode) return MVGX_OK;
-  if (c->solver_ready) {
+  if (c->set.solver_from_env || kind == c->set.solver_mode) return MVGX_OK;
+  if (c->solver.ready) {
     const bool sparse_now = c->d.sp.enabled != 0;
     const bool same = (kind == MVGX_BA_LINEAR_SOLVER_DENSE && !sparse_now) || (kind >= MVGX_BA_LINEAR_SOLVER_SPARSE && sparse_now) ||
-                      (kind == MVGX_BA_LINEAR_SOLVER_SPARSE_PREFERRED && !sparse_now && c->plan_tried && !c->plan_ok) || c->d.N == 0;
+                      (kind == MVGX_BA_LINEAR_SOLVER_SPARSE_PREFERRED && !sparse_now && c->solver.plan_tried && !c->solver.plan_ok) || c->d.N == 0;
     MVGX_REQUIRE(same, MVGX_ERR_STATE, "mvgx_ba_set_linear_solver(%d) after the first iteration: the %s solver is set up", kind, sparse_now ? "block-sparse" : "dense");
-    c->solver_mode = kind;
+    c->set.solver_mode = kind;
     return MVGX_OK;
   }
-  c->solver_mode = kind;
-  c->plan_ready = false;
+  c->set.solver_mode = kind;
+  c->solver.plan_ready = false;
   if (multi_rank(c) || mvgx::ba_create_plan_deferred()) return MVGX_OK;   // (planned at the first iteration, on the union of the ranks' blocks)
   MVGX_HIP(hipSetDevice(c->device));
-  return plan_solver(c, c->h_blocks);
+  return plan_solver(c, c->solver.h_blocks);
 }
 
 int mvgx_ba_get_solver_info(mvgx_ba_ctx* c, mvgx_ba_solver_info* out) {
   MVGX_REQUIRE(c && out, MVGX_ERR_ARG, "mvgx_ba_get_solver_info: NULL argument");
   if (c->multi) return mvgx::ba_multi_solver_info(c->multi, out);
-  MVGX_REQUIRE(c->solver_ready, MVGX_ERR_STATE, "mvgx_ba_get_solver_info before the first iteration");
+  MVGX_REQUIRE(c->solver.ready, MVGX_ERR_STATE, "mvgx_ba_get_solver_info before the first iteration");
   memset(out, 0, sizeof(*out));
   const int64_t nd = (c->d.N + 63) / 64;
   out->n_columns = c->d.N;
@@ -5784,7 +5887,7 @@ int mvgx_ba_get_solver_info(mvgx_ba_ctx* c, mvgx_ba_solver_info* out) {
   out->n_point_groups = (int32_t)c->d.grp.n_groups;
   out->n_grouped_points = (int32_t)c->n_grouped_points;
   if (c->d.sp.enabled) {
-    const mvgx_sparse::Plan& pl = c->plan;
+    const mvgx_sparse::Plan& pl = c->solver.plan;
     out->sparse = 1; out->n_padded = pl.N_pad; out->n_parts = pl.n_parts; out->n_border_blocks = pl.n_border_blocks;
     out->n_levels = pl.n_levels; out->n_factor_tiles = (int64_t)pl.n_fill_tiles; out->flops = pl.flops;
   } else {

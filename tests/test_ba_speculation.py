@@ -7,7 +7,7 @@ parameters - and a whole solve must follow the restatement's schedule (iteration
 
 The test hook mvgx_debug_ba_speculation (BaContext.speculation) counts {evaluations launched ahead, consumed as the next Jacobian, gate
 stayed shut}: every case asserts that the path it claims ran - the look-ahead with the default form, nothing with MVGX_BA_SPECULATE=0 and
-under the exclusion rules (pose priors, several shards, MVGX_BA_SEPARATE_COST=1). The emulation maps host memory for the device
+under the exclusion rules (pose priors, several shards, MVGX_BA_SEPARATE_COST=1, MVGX_BA_POLL_SCALARS=0). The emulation maps host memory for the device
 (hipHostGetDevicePointer), so the polled scalars and with them the look-ahead run there too; the gpu-marked twins run the same cases.
 
 Each option set switches off the termination tests it does not exercise (tolerance 0), so that the termination code names the test
@@ -143,17 +143,24 @@ def check_stepping(monkeypatch, scene, perturb_after=None, n_steps=6):
 
 
 def check_excluded(monkeypatch, rule):
-    """the exclusion rules of the look-ahead take the off path: count 0, same results as MVGX_BA_SPECULATE=0"""
+    """the exclusion rules of the look-ahead take the off path: count 0, same results as MVGX_BA_SPECULATE=0; the scalars of a step
+    brought by copy + synchronise ("copied_scalars") change their transport and no operation: the same results as with the polled ones"""
     opts = OPTIONS["function_tolerance"][0]
     sc = _scene("clean", priors=rule == "pose_priors")
     devices = [0, 0] if rule == "two_shards" else None
     if rule == "separate_cost":
         monkeypatch.setenv("MVGX_BA_SEPARATE_COST", "1")
+    if rule == "copied_scalars":
+        s_polled, p_polled, _ = _solved(sc, opts)
+        monkeypatch.setenv("MVGX_BA_POLL_SCALARS", "0")
     (s_off, p_off, n_off), (s_on, p_on, n_on) = _both_forms(monkeypatch, lambda: _solved(sc, opts, devices))
     _same_solve(s_off, s_on)
     assert p_off == p_on
     assert n_off == n_on == (0, 0, 0), (n_off, n_on)
     assert s_on.num_iterations > 1
+    if rule == "copied_scalars":
+        _same_solve(s_polled, s_on)
+        assert p_polled == p_on
 
 
 # ---- emulated ----
@@ -179,7 +186,7 @@ def test_stepping_around_evaluate_residuals_update_emulated(monkeypatch):
         check_stepping(monkeypatch, "clean", perturb_after=1, n_steps=4)
 
 
-@pytest.mark.parametrize("rule", ["pose_priors", "separate_cost"])
+@pytest.mark.parametrize("rule", ["pose_priors", "separate_cost", "copied_scalars"])
 def test_excluded_contexts_take_the_off_path_emulated(rule, monkeypatch):
     with _emu.emulated():
         check_excluded(monkeypatch, rule)
@@ -212,6 +219,6 @@ def test_stepping_around_evaluate_residuals_update(monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rule", ["pose_priors", "separate_cost", "two_shards"])
+@pytest.mark.parametrize("rule", ["pose_priors", "separate_cost", "two_shards", "copied_scalars"])
 def test_excluded_contexts_take_the_off_path(rule, monkeypatch):
     check_excluded(monkeypatch, rule)
