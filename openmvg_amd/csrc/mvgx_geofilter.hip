@@ -35,6 +35,7 @@
 #include <limits>
 #include <numeric>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "mvgx_buffers.h"
@@ -45,19 +46,37 @@ namespace {
 using mvgx::set_error;
 
 constexpr int kBins = 20;        // robust_estimator_ACRansac.hpp:221
-constexpr int kMinSamples = 7, kMaxModels = 3;   // the fundamental-matrix model (SevenPointSolver)
-// The estimated model: the a-contrario loop is the same program for both, what differs is the minimal solver, the residual, the
+// The estimated model: the a-contrario loop is the same program for all, what differs is the minimal solver, the residual, the
 // sample size and - on the host - logalpha0 / multError of the NFA (point-to-line for F, point-to-point for H).
 // kModelEA8 / kModelEU3: the essential matrix with the ANGULAR residual on bearing vectors (E_ACRobust_Angular.hpp:33-191, spherical
 // cameras): EightPointRelativePoseSolver / ThreePointUprightRelativePoseSolver, one model per sample, no normalisation, no pixels.
 // kModelEO: the orthographic essential matrix (Eo_Robust.hpp:35-165): ThreePointSolver (two models per sample) and
 // OrthographicSymmetricEpipolarDistanceError on the hnormalized bearing vectors, which travel in the pixel arrays (no normalisation).
 enum GeoModel { kModelF = 0, kModelH = 1, kModelE = 2, kModelEA8 = 3, kModelEU3 = 4, kModelEO = 5 };
-template <int MODEL> constexpr bool model_is_angular() { return MODEL == kModelEA8 || MODEL == kModelEU3; }
-template <int MODEL> constexpr int model_min_samples() {   // Solver::MINIMUM_SAMPLES
-  return MODEL == kModelH ? 4 : MODEL == kModelE ? 5 : MODEL == kModelEA8 ? 8 : (MODEL == kModelEU3 || MODEL == kModelEO) ? 3 : kMinSamples;
+// ACParametrizationHelper (robust_estimator_ACRansacKernelAdaptator.hpp:38-100): logalpha0 and multError of the NFA
+enum GeoNfa { kNfaPointToLine, kNfaPointToPoint, kNfaSquaredAngle };
+// Everything the host path and the kernel know about a model, in one row each
+struct GeoModelDesc {
+  int min_samples, max_models;   // Solver::MINIMUM_SAMPLES, Solver::MAX_MODELS
+  int sample_slots;              // length of the kernel's sample array
+  bool angular;                  // works on bearing vectors only: no pixels, no image sizes, no normalisation
+  bool bearings;                 // reads bearing vectors
+  bool calibrated;               // takes calibration matrices: residuals under F = K2^-T E K1^-1
+  bool identity_norm;            // ACKernelAdaptorEssential{,Ortho}: N1 = N2 = I, LogAlpha0 at scale 0.5, nothing to un-normalise
+  bool bound_as_given;           // the caller's bound is the residual threshold as it is (Eo_Robust.hpp:96-100)
+  bool ahead_form;               // has the instantiation that draws its samples ahead and solves four side by side
+  GeoNfa nfa;
+};
+constexpr GeoModelDesc geo_model(int model) {
+  switch (model) {   //     min max slots angular bearings calibr. identity as_given ahead  nfa
+    case kModelH:   return {4, 1,  7,    false,  false,   false,  false,   false,   true,  kNfaPointToPoint};   // FourPointSolver
+    case kModelE:   return {5, 10, 7,    false,  true,    true,   true,    false,   true,  kNfaPointToLine};    // FivePointSolver
+    case kModelEA8: return {8, 1,  8,    true,   true,    false,  false,   false,   false, kNfaSquaredAngle};   // EightPointRelativePoseSolver
+    case kModelEU3: return {3, 1,  7,    true,   true,    false,  false,   false,   false, kNfaSquaredAngle};   // ThreePointUprightRelativePoseSolver
+    case kModelEO:  return {3, 2,  7,    false,  false,   false,  true,    true,    false, kNfaPointToLine};    // ThreePointSolver
+    default:        return {7, 3,  7,    false,  false,   false,  false,   false,   false, kNfaPointToLine};    // kModelF: SevenPointSolver
+  }
 }
-template <int MODEL> constexpr int model_sample_slots() { return MODEL == kModelEA8 ? 8 : 7; }   // length of the kernel's sample array
 constexpr int kMtN = 624, kMtM = 397;
 
 struct GeoPair {   // per pair, prepared on the host (glibc's log10 / hypot / sqrt: the reference's values)
@@ -255,12 +274,10 @@ __device__ __forceinline__ double angular_error(const double (&E)[9], Pt3 a, Pt3
 template <int MODEL>
 __device__ __forceinline__ double model_error(const double (&M)[9], Pt3 x, Pt3 y) { return angular_error(M, x, y); }
 // correspondence i of a pair as the model's residual takes it: normalised pixel positions, or - angular models - bearing vectors
-template <int MODEL> struct PointOf { using type = double2; };
-template <> struct PointOf<kModelEA8> { using type = Pt3; };
-template <> struct PointOf<kModelEU3> { using type = Pt3; };
+template <int MODEL> struct PointOf { using type = std::conditional_t<geo_model(MODEL).angular, Pt3, double2>; };
 template <int MODEL>
 __device__ __forceinline__ typename PointOf<MODEL>::type load_point(const double2* __restrict__ x, const double* __restrict__ b, uint32_t i) {
-  if constexpr (model_is_angular<MODEL>()) return Pt3{b[3 * (size_t)i], b[3 * (size_t)i + 1], b[3 * (size_t)i + 2]};
+  if constexpr (geo_model(MODEL).angular) return Pt3{b[3 * (size_t)i], b[3 * (size_t)i + 1], b[3 * (size_t)i + 2]};
   else return x[i];
 }
 
@@ -652,9 +669,14 @@ constexpr int kRowModel = 22;
 // (The seven-point solver of the fundamental model was built in this form too and is not kept: its elimination is 40 % of an iteration, not
 // 75 - 85 %, and what four side by side save went into the exchange of the rows' models and 60 more spilled registers: 55 ms against 48 on
 // 20 000 pairs, profiles/round5_geofilter_f_h_samples_ahead_ab_call_r5_30.txt.)
-template <int MODEL> constexpr bool model_solves_ahead() { return MODEL == kModelE || MODEL == kModelH; }
-template <int MODEL> constexpr int wave_scratch_words() {
-  return kWaveScratch + (MODEL == kModelE ? kEssentialScratch : model_solves_ahead<MODEL>() ? 2 * kAhead * kRowModel : 0);
+constexpr int wave_scratch_words(int model) {
+  return kWaveScratch + (model == kModelE ? kEssentialScratch : geo_model(model).ahead_form ? 2 * kAhead * kRowModel : 0);
+}
+// words of a wave's table of n entries (n + 1 used; even, so that the doubles behind stay 8-byte aligned) and of its LDS: generator |
+// pool | logc_n | logc_k (LDS form) | scratch - the kernel's layout and the host's dynamic-LDS size
+constexpr uint32_t table_cap(uint32_t n) { return (n + 2) & ~1u; }
+constexpr uint32_t wave_lds_words(int model, bool global_tables, uint32_t cap1) {
+  return kMtN + (global_tables ? 0u : 3 * cap1) + wave_scratch_words(model);
 }
 
 // kGlobalTables: the sampling pool and the two log-combinatorial tables of a wave (3 x n words) live in a global scratch block
@@ -684,14 +706,14 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
   if (w >= n_work) return;   // wave-uniform; no workgroup barrier below
   const long long t_start = __builtin_amdgcn_s_memtime();
   uint32_t n_iter_run = 0, n_models_run = 0;
-  constexpr int kMin = model_min_samples<MODEL>();
+  constexpr int kMin = geo_model(MODEL).min_samples;
   const uint32_t pidx = order[w];
   const GeoPair& P = pairs[pidx];   // (read through the scalar data path: wave-uniform)
   const uint32_t n = P.n;
   // LDS form: the class's size for every pair; global form: the pair's own (its tables sit at 3 x (start + 4 x pair) words of the
   // scratch block - start = the pair's first correspondence: no two pairs overlap, whatever their sizes)
-  const uint32_t cap1 = ((kGlobalTables ? n : n_cap) + 2) & ~1u;   // even: the doubles behind stay 8-byte aligned
-  const uint32_t per_wave = kMtN + (kGlobalTables ? 0u : 3 * cap1) + wave_scratch_words<MODEL>();   // words: generator | pool | logc_n | logc_k | scratch
+  const uint32_t cap1 = table_cap(kGlobalTables ? n : n_cap);
+  const uint32_t per_wave = wave_lds_words(MODEL, kGlobalTables, cap1);   // words: generator | pool | logc_n | logc_k | scratch
   uint32_t* const mt = lds_u32 + (size_t)wave * per_wave;
   uint32_t* const pool = kGlobalTables ? table_scratch + 3 * ((size_t)P.start + 4 * (size_t)pidx) : mt + kMtN;
   float* const logc_n = reinterpret_cast<float*>(pool + cap1);
@@ -705,7 +727,7 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
   const double max_threshold = P.max_threshold, bins_by_interval = P.bins_by_interval, loge0 = P.loge0;
   const double2* __restrict__ x1 = x1n + P.start;
   const double2* __restrict__ x2 = x2n + P.start;
-  constexpr bool kBearings = MODEL == kModelE || model_is_angular<MODEL>();
+  constexpr bool kBearings = geo_model(MODEL).bearings;
   const double* __restrict__ bv1 = kBearings ? bear1 + 3 * P.start : nullptr;
   const double* __restrict__ bv2 = kBearings ? bear2 + 3 * P.start : nullptr;
   // lane b < 20 keeps the constants of histogram bin b
@@ -726,7 +748,7 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
   int nIterReserve = (int)(max_iterations / 10);
   unsigned nIter = max_iterations - (unsigned)nIterReserve;
   bool ac_mode = false;
-  constexpr int kS = model_sample_slots<MODEL>();
+  constexpr int kS = geo_model(MODEL).sample_slots;
   uint32_t s[kS];
 #pragma unroll
   for (int k = 0; k < kS; ++k) s[k] = 0;
@@ -827,7 +849,7 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
   // generator's index goes back to where the last used sample left it (a sample drawn ahead never twists the state, so the index is
   // the whole state; the pool is either untouched - warm-up - or rebuilt by the event) and the next batch draws again. Results are those
   // of one sample per iteration, bit for bit (`ahead` = 1 is that form: tests/test_geofilter_e.py compares the two).
-  constexpr bool x4 = kAheadForm && model_solves_ahead<MODEL>();
+  constexpr bool x4 = kAheadForm && geo_model(MODEL).ahead_form;
   double* const row_models = e_scr;   // (fundamental / homography models: the same words of the wave's scratch)
   unsigned iter = 0;
   while (iter < nIter && iter < max_iterations) {
@@ -835,7 +857,7 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
     [[maybe_unused]] uint32_t S[kAhead][kMin];
     [[maybe_unused]] int idx_after[kAhead] = {0, 0, 0, 0};
     [[maybe_unused]] int nm_rows = 0;
-    if constexpr (model_solves_ahead<MODEL>()) {
+    if constexpr (geo_model(MODEL).ahead_form) {
       if (x4) {
         const unsigned left = (nIter < max_iterations ? nIter : max_iterations) - iter;
         const int kb_max = (int)(left < ahead ? left : ahead);
@@ -881,7 +903,7 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
     const bool ac_at_start = ac_mode;
     // ---- sample ----
     if (!x4) (void)draw_sample(true);
-    if constexpr (model_solves_ahead<MODEL>()) {
+    if constexpr (geo_model(MODEL).ahead_form) {
       if (x4) {
 #pragma unroll
         for (int i = 0; i < kMin; ++i) s[i] = j == 0 ? S[0][i] : j == 1 ? S[1][i] : j == 2 ? S[2][i] : S[3][i];
@@ -936,7 +958,7 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
       double F[9];
 #pragma unroll
       for (int u = 0; u < 9; ++u)
-        F[u] = (MODEL == kModelH || model_is_angular<MODEL>()) ? F1[u] : MODEL == kModelEO ? (mi == 0 ? F1[u] : F2[u]) : MODEL == kModelE ? e_Fs[9 * mi + u]
+        F[u] = (MODEL == kModelH || geo_model(MODEL).angular) ? F1[u] : MODEL == kModelEO ? (mi == 0 ? F1[u] : F2[u]) : MODEL == kModelE ? e_Fs[9 * mi + u]
                                                                                                                                                   : F1[u] + root * F2[u];
       if (lane < kBins) hist[lane] = 0;
       wave_sync();
@@ -1044,7 +1066,7 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
     GEO_STAMP(5);
     ++iter;
     if (!(iter < nIter && iter < max_iterations)) break;
-    if constexpr (model_solves_ahead<MODEL>()) {
+    if constexpr (geo_model(MODEL).ahead_form) {
       if (x4 && redraw && j + 1 < kb) {   // the generator as the last sample used left it
         mt_idx = j == 0 ? idx_after[0] : j == 1 ? idx_after[1] : idx_after[2];
         break;
@@ -1072,58 +1094,48 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
 }
 
 using ByteBuf = mvgx::DevBuf<unsigned char>;   // sized in bytes
-// every buffer of a call exists, an empty one too: 16 bytes at the least, as ever
-int alloc(ByteBuf& b, size_t bytes) { return b.ensure(std::max<size_t>(bytes, 1)); }
+// every buffer of a call exists, an empty one too: 16 elements at the least
+template <typename T> int alloc(mvgx::DevBuf<T>& b, size_t n) { return b.ensure(std::max<size_t>(n, 1)); }
 
-template <int WAVES, int MODEL>
-int launch_class(const GeoPair* d_pairs, const uint32_t* d_order, uint32_t n_work, uint32_t n_cap, const double2* x1, const double2* x2,
-                 const float* l10, const uint32_t* mt_init, uint32_t max_it, GeoResult* res, uint8_t* mask, hipStream_t stream,
-                 const double* b1 = nullptr, const double* b2 = nullptr, uint32_t ahead = 1) {
-  if (!n_work) return MVGX_OK;
-  const size_t lds = (size_t)WAVES * (kMtN + 3 * (size_t)((n_cap + 2) & ~1u) + wave_scratch_words<MODEL>()) * sizeof(uint32_t);
-  constexpr bool kHasAheadForm = model_solves_ahead<MODEL>();   // (the other models have one instantiation)
-  if (kHasAheadForm && ahead > 1) {
-    MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&geofilter_f_acransac_kernel<WAVES, false, MODEL, kHasAheadForm>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((geofilter_f_acransac_kernel<WAVES, false, MODEL, kHasAheadForm>), dim3((n_work + WAVES - 1) / WAVES), dim3(64 * WAVES), lds, stream, d_pairs, d_order, n_work,
-                       n_cap, x1, x2, l10, mt_init, max_it, res, mask, (uint32_t*)nullptr, b1, b2, ahead);
-  } else {
-    MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&geofilter_f_acransac_kernel<WAVES, false, MODEL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((geofilter_f_acransac_kernel<WAVES, false, MODEL, false>), dim3((n_work + WAVES - 1) / WAVES), dim3(64 * WAVES), lds, stream, d_pairs, d_order, n_work,
-                       n_cap, x1, x2, l10, mt_init, max_it, res, mask, (uint32_t*)nullptr, b1, b2, ahead);
-  }
+constexpr int kWaves = 4;                   // waves (= pairs) per workgroup of geofilter_f_acransac_kernel
+constexpr uint32_t kCap0 = 256;             // correspondences per pair up to which a wave's tables (3 words per correspondence) live in LDS
+constexpr uint32_t kCapGlobal = 1u << 20;   // above kCap0 they live in global scratch (geofilter_f_acransac_kernel<4, true>)
+
+// One class of pairs of a call as the kernel takes it (plain pointers: the buffers own their memory and must not be captured by value)
+struct GeoLaunch {
+  const GeoPair* pairs; const uint32_t* order; uint32_t n_work, n_cap;
+  const double2 *x1, *x2; const float* l10; const uint32_t* mt_init; uint32_t max_iterations;
+  GeoResult* results; uint8_t* mask; uint32_t* tables; const double *b1, *b2; uint32_t ahead; hipStream_t stream;
+};
+// kGlobalTables: tables in `tables`, workgroups of four waves like the LDS class (the LDS a wave needs does not grow with its pair)
+template <int MODEL, bool kGlobalTables, bool kAheadForm>
+int geo_launch(const GeoLaunch& a) {
+  if (!a.n_work) return MVGX_OK;
+  const size_t lds = (size_t)kWaves * wave_lds_words(MODEL, kGlobalTables, table_cap(a.n_cap)) * sizeof(uint32_t);
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&geofilter_f_acransac_kernel<kWaves, kGlobalTables, MODEL, kAheadForm>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((geofilter_f_acransac_kernel<kWaves, kGlobalTables, MODEL, kAheadForm>), dim3((a.n_work + kWaves - 1) / kWaves), dim3(64 * kWaves), lds, a.stream,
+                     a.pairs, a.order, a.n_work, a.n_cap, a.x1, a.x2, a.l10, a.mt_init, a.max_iterations, a.results, a.mask, a.tables, a.b1, a.b2, a.ahead);
   MVGX_HIP(hipGetLastError());
   return MVGX_OK;
 }
-// the class above the LDS classes: tables in `scratch` (n_work x 3 x ((n_cap + 2) & ~1) words), workgroups of four waves like the small classes
-// (the LDS a wave needs no longer grows with its pair: the occupancy of the small classes at any size)
-template <int MODEL>
-int launch_class_global(const GeoPair* d_pairs, const uint32_t* d_order, uint32_t n_work, uint32_t n_cap, const double2* x1, const double2* x2,
-                        const float* l10, const uint32_t* mt_init, uint32_t max_it, GeoResult* res, uint8_t* mask, uint32_t* scratch, hipStream_t stream,
-                        const double* b1 = nullptr, const double* b2 = nullptr, uint32_t ahead = 1) {
-  if (!n_work) return MVGX_OK;
-  constexpr int W = 4;
-  const size_t lds = (size_t)W * (kMtN + wave_scratch_words<MODEL>()) * sizeof(uint32_t);
-  constexpr bool kHasAheadForm = model_solves_ahead<MODEL>();
-  if (kHasAheadForm && ahead > 1) {
-    MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&geofilter_f_acransac_kernel<W, true, MODEL, kHasAheadForm>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((geofilter_f_acransac_kernel<W, true, MODEL, kHasAheadForm>), dim3((n_work + W - 1) / W), dim3(64 * W), lds, stream, d_pairs, d_order, n_work, n_cap, x1, x2,
-                       l10, mt_init, max_it, res, mask, scratch, b1, b2, ahead);
-  } else {
-    MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&geofilter_f_acransac_kernel<W, true, MODEL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((geofilter_f_acransac_kernel<W, true, MODEL, false>), dim3((n_work + W - 1) / W), dim3(64 * W), lds, stream, d_pairs, d_order, n_work, n_cap, x1, x2,
-                       l10, mt_init, max_it, res, mask, scratch, b1, b2, ahead);
+// the run-time model as a compile-time one: fn(std::integral_constant<int, MODEL>)
+template <typename Fn>
+int with_geo_model(int model, Fn&& fn) {
+  switch (model) {
+    case kModelH: return fn(std::integral_constant<int, kModelH>{});
+    case kModelE: return fn(std::integral_constant<int, kModelE>{});
+    case kModelEA8: return fn(std::integral_constant<int, kModelEA8>{});
+    case kModelEU3: return fn(std::integral_constant<int, kModelEU3>{});
+    case kModelEO: return fn(std::integral_constant<int, kModelEO>{});
+    default: return fn(std::integral_constant<int, kModelF>{});
   }
-  MVGX_HIP(hipGetLastError());
-  return MVGX_OK;
 }
-
-}  // namespace
-
-namespace {
 
 // Where the correspondences come from: gathered coordinates (xI / xJ, image_wh per pair) or, `indexed`, the feature positions of
 // every image plus index pairs (image_wh per image)
 struct GeoSource {
+  const char* entry = "";   // the C entry that was called (error messages)
   bool indexed = false;
   const double* xI = nullptr; const double* xJ = nullptr;
   const double* feat_xy = nullptr; const uint64_t* feat_start = nullptr; uint32_t n_images = 0;
@@ -1134,341 +1146,355 @@ struct GeoSource {
   const double* pair_precision = nullptr;   // orthographic model: the bound of every pair (NULL: opt->precision for all)
 };
 
+// The form of a run, resolved once per call: MVGX_GEO_GLOBAL_ABOVE = a smaller bound than kCap0 for the LDS class (tests: the global form on
+// small pairs); MVGX_GEO_AHEAD (older name MVGX_GEO_E_AHEAD, which yields to it) = samples drawn and solved ahead of their iterations, 1 ..
+// kAhead (1: one minimal solve per iteration; results equal); MVGX_GEO_TIMING = where a call's time goes, on stderr
+struct GeoForm { uint32_t global_above; uint32_t ahead; bool timing; };
+GeoForm geo_form_from_env() {
+  GeoForm f{kCap0, (uint32_t)kAhead, getenv("MVGX_GEO_TIMING") != nullptr};
+  if (const char* e = getenv("MVGX_GEO_GLOBAL_ABOVE")) f.global_above = (uint32_t)std::min<int>((int)kCap0, std::max(1, atoi(e)));
+  const char* a = getenv("MVGX_GEO_AHEAD") ? getenv("MVGX_GEO_AHEAD") : getenv("MVGX_GEO_E_AHEAD");
+  if (a) f.ahead = (uint32_t)std::min(kAhead, std::max(1, atoi(a)));
+  return f;
+}
+
+int geo_check_arguments(const GeoModelDesc& d, const GeoSource& src, const uint64_t* match_start, const uint32_t* image_wh, uint64_t n_pairs,
+                        const mvgx_geofilter_options* opt, const uint8_t* inlier_mask, const mvgx_geofilter_result* results) {
+  if (d.calibrated) MVGX_REQUIRE(n_pairs == 0 || src.K, MVGX_ERR_ARG, "%s: NULL calibration matrices", src.entry);
+  const bool have_bearings = src.indexed ? src.feat_bearing != nullptr : (src.bI && src.bJ);
+  if (d.bearings) MVGX_REQUIRE(!match_start || match_start[n_pairs] == 0 || have_bearings, MVGX_ERR_ARG, "%s: NULL bearing vectors", src.entry);
+  MVGX_REQUIRE(opt && match_start && (n_pairs == 0 || ((image_wh || d.angular) && results)), MVGX_ERR_ARG, "%s: NULL argument", src.entry);
+  const uint64_t n_total = match_start[n_pairs];
+  MVGX_REQUIRE(n_total == 0 || inlier_mask, MVGX_ERR_ARG, "%s: NULL inlier mask", src.entry);
+  if (src.indexed) {
+    MVGX_REQUIRE(n_pairs == 0 || (src.pair_images && src.feat_start), MVGX_ERR_ARG, "%s: NULL pair / feature-start array", src.entry);
+    MVGX_REQUIRE(n_total == 0 || ((src.feat_xy || d.angular) && src.ij), MVGX_ERR_ARG, "%s: NULL position / index array", src.entry);
+    for (uint64_t p = 0; p < n_pairs; ++p)
+      MVGX_REQUIRE(src.pair_images[2 * p] < src.n_images && src.pair_images[2 * p + 1] < src.n_images, MVGX_ERR_ARG, "%s: pair %llu names an image out of range", src.entry, (unsigned long long)p);
+  } else {
+    MVGX_REQUIRE(n_total == 0 || d.angular || (src.xI && src.xJ), MVGX_ERR_ARG, "%s: NULL correspondence array", src.entry);
+  }
+  for (uint64_t p = 0; src.pair_precision && p < n_pairs; ++p)
+    MVGX_REQUIRE(std::isfinite(src.pair_precision[p]) && src.pair_precision[p] > 0.0, MVGX_ERR_UNSUPPORTED,
+                 "%s: pair %llu: precision must be a finite upper bound", src.entry, (unsigned long long)p);
+  MVGX_REQUIRE(src.pair_precision || (std::isfinite(opt->precision) && opt->precision > 0.0), MVGX_ERR_UNSUPPORTED,
+               "%s: precision must be a finite upper bound (the exhaustive NFA form of an unbounded precision is not reproduced on the "
+               "device; main_GeometricFilter passes 4.0)", src.entry);
+  MVGX_REQUIRE(opt->max_iterations >= 1, MVGX_ERR_ARG, "%s: max_iterations must be at least 1", src.entry);
+  for (uint64_t p = 0; p < n_pairs; ++p) {
+    MVGX_REQUIRE(match_start[p + 1] >= match_start[p], MVGX_ERR_ARG, "%s: match_start must be non-decreasing", src.entry);
+    MVGX_REQUIRE(match_start[p + 1] - match_start[p] <= kCapGlobal, MVGX_ERR_UNSUPPORTED, "%s: pair %llu has %llu correspondences (limit %u)",
+                 src.entry, (unsigned long long)p, (unsigned long long)(match_start[p + 1] - match_start[p]), kCapGlobal);
+  }
+  return MVGX_OK;
+}
+
 // inverse of a 3 x 3 matrix by cofactors (what Eigen's Matrix3d::inverse() evaluates: cofactors x 1 / det)
 inline void inverse3(const double* m, double* inv) {
   const double c00 = m[4] * m[8] - m[5] * m[7], c10 = m[5] * m[6] - m[3] * m[8], c20 = m[3] * m[7] - m[4] * m[6];
-  const double det = c00 * m[0] + c10 * m[1] + c20 * m[2];
-  const double id = 1.0 / det;
+  const double det = c00 * m[0] + c10 * m[1] + c20 * m[2], id = 1.0 / det;
   inv[0] = c00 * id; inv[3] = c10 * id; inv[6] = c20 * id;
   inv[1] = (m[2] * m[7] - m[1] * m[8]) * id; inv[4] = (m[0] * m[8] - m[2] * m[6]) * id; inv[7] = (m[1] * m[6] - m[0] * m[7]) * id;
   inv[2] = (m[1] * m[5] - m[2] * m[4]) * id; inv[5] = (m[2] * m[3] - m[0] * m[5]) * id; inv[8] = (m[0] * m[4] - m[1] * m[3]) * id;
 }
 
-// the launches of the two forms for one model: pairs of more than kCap0 correspondences (largest first) with their tables in global
-// scratch, the others with them in LDS. (Until the end of round 5 there were three more LDS classes - up to 1 024, 4 096 and 12 000
-// correspondences at 4 / 2 / 1 waves per workgroup: their LDS left one workgroup per CU, and a pair of 2 000 correspondences ran 2.5 x
-// slower per iteration than it does in the global form, call r5_61.)
-template <int MODEL>
-int launch_classes(const GeoPair* d_pairs, const uint32_t* ord, const std::vector<uint32_t>& order, uint32_t c_global, uint32_t cap0, uint64_t n_total, uint64_t n_pairs,
-                   const double2* px1, const double2* px2, const float* l10, const uint32_t* mt, uint32_t max_it, GeoResult* res, uint8_t* mask, ByteBuf& d_tables,
-                   hipStream_t stream, const double* b1 = nullptr, const double* b2 = nullptr, uint32_t ahead = 1) {
-  int rc;
-  if (c_global) {
-    if ((rc = alloc(d_tables, 3 * ((size_t)n_total + 4 * (size_t)n_pairs + 4) * sizeof(uint32_t)))) return rc;
-    if ((rc = launch_class_global<MODEL>(d_pairs, ord, c_global, 0, px1, px2, l10, mt, max_it, res, mask, reinterpret_cast<uint32_t*>(d_tables.p), stream, b1, b2, ahead))) return rc;
+// The constants of one pair (ACKernelAdaptor's constructor + NFA_Interface's) from the two image sizes {w, h}, the calibration matrices where the
+// model takes them and the caller's precision `bound`; norm = {s1, tx1, ty1, s2, tx2, ty2}: the points are normalised on the device. Every field of
+// g is written. The expressions and their order are the reference's: glibc's log10 / hypot / sqrt give its values bit for bit.
+void geo_pair_constants(const GeoModelDesc& d, uint64_t start, uint32_t n, const uint32_t* wh1, const uint32_t* wh2, const double* K1, const double* K2,
+                        double bound, GeoPair& g, double* norm) {
+  g.start = start; g.n = n; g.pad_ = 0;
+  double t[2][3] = {{1.0, 0.0, 0.0}, {1.0, 0.0, 0.0}};
+  if (d.angular) for (int k = 0; k < 6; ++k) norm[k] = 0.0;   // (uploaded, never read: no uninitialised bytes on the wire)
+  for (int im = 0; im < 2 && !d.angular; ++im) {   // conditioning.cpp:44-53
+    const uint32_t* whp = im ? wh2 : wh1;
+    const int w = (int)whp[0], h = (int)whp[1];
+    const double dNorm = 1.0 / std::sqrt(static_cast<double>(w * h));
+    t[im][0] = dNorm; t[im][1] = -.5f * w * dNorm; t[im][2] = -.5 * h * dNorm;
+    if (d.identity_norm) { t[im][0] = 1.0; t[im][1] = 0.0; t[im][2] = 0.0; }
+    for (int k = 0; k < 3; ++k) norm[3 * im + k] = t[im][k];
   }
-  return launch_class<4, MODEL>(d_pairs, ord + c_global, (uint32_t)order.size() - c_global, cap0, px1, px2, l10, mt, max_it, res, mask, stream, b1, b2, ahead);
+  if (d.calibrated) {
+    double k2i[9];
+    inverse3(K1, g.k1i); inverse3(K2, k2i);
+    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) g.k2it[3 * a + b] = k2i[3 * b + a];
+  } else {
+    for (int u = 0; u < 9; ++u) { g.k1i[u] = 0.0; g.k2it[u] = 0.0; }
+  }
+  const int w2 = (int)wh2[0], h2 = (int)wh2[1];
+  // ACParametrizationHelper (robust_estimator_ACRansacKernelAdaptator.hpp:38-81): point-to-line at the scale of the second image's
+  // normalisation (0.5 where there is none: LogAlpha0(w2, h2, 0.5)), point-to-point; RADIAN_ANGLE (:85-100): log10(1 / 2), multError
+  // 1 / 4 - the residual is a squared angle
+  const double line_scale = d.identity_norm ? 0.5 : t[1][0];
+  const double logalpha0 = d.nfa == kNfaSquaredAngle ? std::log10(1. / 2.)
+                           : d.nfa == kNfaPointToPoint ? std::log10(M_PI / (w2 * static_cast<double>(h2)) / (t[1][0] * t[1][0]))
+                                                       : std::log10(2. * std::hypot(w2, h2) / (w2 * static_cast<double>(h2)) / line_scale);
+  const double mult_error = d.nfa == kNfaSquaredAngle ? 1. / 4. : d.nfa == kNfaPointToPoint ? 1.0 : 0.5;
+  // angular models: E_ACRobust_Angular.hpp:117-119 hands ACRANSAC D2R(precision in degrees), which ACRANSAC compares with the
+  // SQUARED angles as it is (robust_estimator_ACRansac.hpp:351-353: maxThreshold = precision * normalizer2()(0,0)^2, the identity here)
+  // orthographic model: the value the functor hands to ACRANSAC (Eo_Robust.hpp:96-100: the mean of the two cameras'
+  // imagePlane_toCameraPlaneError(precision^2)), per pair or one for all
+  g.max_threshold = d.bound_as_given ? bound : d.angular ? bound * M_PI / 180.0 : bound * bound * t[1][0] * t[1][0];
+  g.loge0 = n > (uint32_t)d.min_samples ? std::log10((double)d.max_models * (n - d.min_samples)) : 0.0;
+  g.bins_by_interval = kBins / (g.max_threshold - 0.0);
+  const double val = (g.max_threshold - 0.0) / static_cast<double>(kBins - 1);
+  for (int b = 0; b < kBins; ++b) {
+    g.bin_value[b] = val * static_cast<double>(b) + 0.0;
+    g.logalpha_bin[b] = logalpha0 + mult_error * std::log10(g.bin_value[b] + std::numeric_limits<float>::epsilon());
+  }
 }
 
-int geofilter_run(int device, int model, const GeoSource& src, const uint64_t* match_start, const uint32_t* image_wh,
-                  uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
-                  mvgx_geofilter_stats* stats) {
-  const bool angular = model == kModelEA8 || model == kModelEU3;   // bearing vectors only: no pixels, no image sizes, no normalisation
-  const bool bearings = model == kModelE || angular;
-  const int min_samples = model == kModelH ? 4 : model == kModelE ? 5 : model == kModelEA8 ? 8 : (model == kModelEU3 || model == kModelEO) ? 3 : kMinSamples;
-  const int max_models = (model == kModelH || angular) ? 1 : model == kModelE ? 10 : model == kModelEO ? 2 : kMaxModels;
-  if (angular)
-    MVGX_REQUIRE(!match_start || match_start[n_pairs] == 0 || (src.indexed ? src.feat_bearing != nullptr : (src.bI && src.bJ)), MVGX_ERR_ARG,
-                 "mvgx_geofilter_e_angular_acransac: NULL bearing vectors");
-  if (model == kModelE) {
-    MVGX_REQUIRE(n_pairs == 0 || src.K, MVGX_ERR_ARG, "mvgx_geofilter_e_acransac: NULL calibration matrices");
-    MVGX_REQUIRE(!match_start || match_start[n_pairs] == 0 || (src.indexed ? src.feat_bearing != nullptr : (src.bI && src.bJ)), MVGX_ERR_ARG,
-                 "mvgx_geofilter_e_acransac: NULL bearing vectors");
-  }
-  MVGX_REQUIRE(opt && match_start && (n_pairs == 0 || ((image_wh || angular) && results)), MVGX_ERR_ARG, "mvgx_geofilter_f_acransac: NULL argument");
-  const uint64_t n_total = match_start[n_pairs];
-  MVGX_REQUIRE(n_total == 0 || inlier_mask, MVGX_ERR_ARG, "mvgx_geofilter_f_acransac: NULL inlier mask");
-  if (src.indexed) {
-    MVGX_REQUIRE(n_pairs == 0 || (src.pair_images && src.feat_start), MVGX_ERR_ARG, "mvgx_geofilter_f_acransac_indexed: NULL pair / feature-start array");
-    MVGX_REQUIRE(n_total == 0 || ((src.feat_xy || angular) && src.ij), MVGX_ERR_ARG, "mvgx_geofilter_f_acransac_indexed: NULL position / index array");
-    for (uint64_t p = 0; p < n_pairs; ++p)
-      MVGX_REQUIRE(src.pair_images[2 * p] < src.n_images && src.pair_images[2 * p + 1] < src.n_images, MVGX_ERR_ARG,
-                   "mvgx_geofilter_f_acransac_indexed: pair %llu names an image out of range", (unsigned long long)p);
-  } else {
-    MVGX_REQUIRE(n_total == 0 || angular || (src.xI && src.xJ), MVGX_ERR_ARG, "mvgx_geofilter_f_acransac: NULL correspondence array");
-  }
-  for (uint64_t p = 0; src.pair_precision && p < n_pairs; ++p)
-    MVGX_REQUIRE(std::isfinite(src.pair_precision[p]) && src.pair_precision[p] > 0.0, MVGX_ERR_UNSUPPORTED,
-                 "mvgx_geofilter_eo_acransac: pair %llu: precision must be a finite upper bound", (unsigned long long)p);
-  MVGX_REQUIRE(src.pair_precision || (std::isfinite(opt->precision) && opt->precision > 0.0), MVGX_ERR_UNSUPPORTED,
-               "mvgx_geofilter_f_acransac: precision must be a finite upper bound (the exhaustive NFA form of an unbounded precision is not "
-               "reproduced on the device; main_GeometricFilter passes 4.0)");
-  MVGX_REQUIRE(opt->max_iterations >= 1, MVGX_ERR_ARG, "mvgx_geofilter_f_acransac: max_iterations must be at least 1");
-  constexpr uint32_t kCap0 = 256;             // correspondences per pair up to which a wave's tables (3 words per correspondence) live in LDS
-  constexpr uint32_t kCapGlobal = 1u << 20;   // above kCap0 they live in global scratch (geofilter_f_acransac_kernel<4, true>)
-  for (uint64_t p = 0; p < n_pairs; ++p) {
-    MVGX_REQUIRE(match_start[p + 1] >= match_start[p], MVGX_ERR_ARG, "mvgx_geofilter_f_acransac: match_start must be non-decreasing");
-    MVGX_REQUIRE(match_start[p + 1] - match_start[p] <= kCapGlobal, MVGX_ERR_UNSUPPORTED,
-                 "mvgx_geofilter_f_acransac: pair %llu has %llu correspondences (limit %u)", (unsigned long long)p,
-                 (unsigned long long)(match_start[p + 1] - match_start[p]), kCapGlobal);
-  }
-  const auto t_begin = std::chrono::steady_clock::now();
-  int rc = mvgx::select_device(device < 0 ? -1 : device);
-  if (rc) return rc;
-  // ---- host preparation (ACKernelAdaptor's constructor + NFA_Interface's constants), on host threads ----
-  // (page-locked memory from the library's cache, not zeroed - every field of every pair is written below: a fresh std::vector of
-  // 100 000 pairs was 50 MB of page faults per call, two thirds of this phase; the uploads from it are asynchronous DMA)
-  mvgx::HostArena host_mem;
-  GeoPair* hp = nullptr;
-  double* norm = nullptr;   // {s1, tx1, ty1, s2, tx2, ty2}; the points are normalised on the device
-  GeoResult* hr = nullptr;
-  if ((rc = host_mem.array(&hp, std::max<uint64_t>(n_pairs, 1))) || (rc = host_mem.array(&norm, std::max<uint64_t>(n_pairs, 1) * 6)) ||
-      (rc = host_mem.array(&hr, std::max<uint64_t>(n_pairs, 1))))
-    return rc;
-  const size_t norm_size = n_pairs * 6;
-  uint32_t n_max = 0;
-  for (uint64_t p = 0; p < n_pairs; ++p) n_max = std::max<uint32_t>(n_max, (uint32_t)(match_start[p + 1] - match_start[p]));
+// geo_pair_constants for every pair, on host threads; an indexed pair's feature indices are checked on the way
+int geo_prepare_pairs(const GeoModelDesc& d, const GeoSource& src, const uint64_t* match_start, const uint32_t* image_wh, uint64_t n_pairs,
+                      const mvgx_geofilter_options* opt, GeoPair* hp, double* norm) {
   const unsigned T = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)32, (size_t)(n_pairs / 4096 + 1)}));
   std::atomic<int64_t> bad_pair{-1};
   auto prep = [&](unsigned tix) {
     for (uint64_t p = tix; p < n_pairs; p += T) {
       const uint64_t lo = match_start[p];
-      const uint32_t n = (uint32_t)(match_start[p + 1] - lo);
-      GeoPair& g = hp[p];
-      g.start = lo; g.n = n; g.pad_ = 0;
+      const uint32_t n = (uint32_t)(match_start[p + 1] - lo), I = src.indexed ? src.pair_images[2 * p] : 0, J = src.indexed ? src.pair_images[2 * p + 1] : 0;
       if (src.indexed) {
-        const uint32_t I = src.pair_images[2 * p], J = src.pair_images[2 * p + 1];
         const uint64_t nI = src.feat_start[I + 1] - src.feat_start[I], nJ = src.feat_start[J + 1] - src.feat_start[J];
         bool bad = false;
         for (uint32_t m = 0; m < n; ++m) bad = bad || src.ij[2 * (lo + m)] >= nI || src.ij[2 * (lo + m) + 1] >= nJ;
         if (bad) bad_pair.store((int64_t)p);
       }
-      double t[2][3] = {{1.0, 0.0, 0.0}, {1.0, 0.0, 0.0}};
-      if (angular) for (int k = 0; k < 6; ++k) norm[6 * p + k] = 0.0;   // (uploaded, never read: no uninitialised bytes on the wire)
-      for (int im = 0; im < 2 && !angular; ++im) {   // conditioning.cpp:44-53
-        const uint32_t* whp = src.indexed ? image_wh + 2 * (size_t)src.pair_images[2 * p + im] : image_wh + 4 * p + 2 * im;
-        const int w = (int)whp[0], h = (int)whp[1];
-        const double dNorm = 1.0 / std::sqrt(static_cast<double>(w * h));
-        t[im][0] = dNorm; t[im][1] = -.5f * w * dNorm; t[im][2] = -.5 * h * dNorm;
-        if (model == kModelE || model == kModelEO) { t[im][0] = 1.0; t[im][1] = 0.0; t[im][2] = 0.0; }   // ACKernelAdaptorEssential{,Ortho}: N1 = N2 = I
-        for (int k = 0; k < 3; ++k) norm[6 * p + 3 * im + k] = t[im][k];
-      }
-      if (model == kModelE) {
-        const double* K1 = src.indexed ? src.K + 9 * (size_t)src.pair_images[2 * p] : src.K + 18 * p;
-        const double* K2 = src.indexed ? src.K + 9 * (size_t)src.pair_images[2 * p + 1] : src.K + 18 * p + 9;
-        double k2i[9];
-        inverse3(K1, g.k1i);
-        inverse3(K2, k2i);
-        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) g.k2it[3 * a + b] = k2i[3 * b + a];
-      } else {
-        for (int u = 0; u < 9; ++u) { g.k1i[u] = 0.0; g.k2it[u] = 0.0; }
-      }
-      static const uint32_t kNoSize[2] = {1, 1};
-      const uint32_t* wh2 = angular ? kNoSize : src.indexed ? image_wh + 2 * (size_t)src.pair_images[2 * p + 1] : image_wh + 4 * p + 2;
-      const int w2 = (int)wh2[0], h2 = (int)wh2[1];
-      // ACParametrizationHelper (robust_estimator_ACRansacKernelAdaptator.hpp:38-81): point-to-line for F, point-to-point for H
-      // (RADIAN_ANGLE, :85-100: log10(1 / 2), multError 1 / 4 - the residual is a squared angle)
-      const double logalpha0 = angular ? std::log10(1. / 2.)
-                               : model == kModelH ? std::log10(M_PI / (w2 * static_cast<double>(h2)) / (t[1][0] * t[1][0]))
-                               : (model == kModelE || model == kModelEO) ? std::log10(2. * std::hypot(w2, h2) / (w2 * static_cast<double>(h2)) / 0.5)   // LogAlpha0(w2, h2, 0.5)
-                                                  : std::log10(2. * std::hypot(w2, h2) / (w2 * static_cast<double>(h2)) / t[1][0]);
-      const double mult_error = angular ? 1. / 4. : model == kModelH ? 1.0 : 0.5;
-      // angular models: E_ACRobust_Angular.hpp:117-119 hands ACRANSAC D2R(precision in degrees), which ACRANSAC compares with the
-      // SQUARED angles as it is (robust_estimator_ACRansac.hpp:351-353: maxThreshold = precision * normalizer2()(0,0)^2, the identity here)
-      // orthographic model: the value the functor hands to ACRANSAC (Eo_Robust.hpp:96-100: the mean of the two cameras'
-      // imagePlane_toCameraPlaneError(precision^2)), per pair or one for all
-      g.max_threshold = model == kModelEO ? (src.pair_precision ? src.pair_precision[p] : opt->precision)
-                        : angular ? opt->precision * M_PI / 180.0 : opt->precision * opt->precision * t[1][0] * t[1][0];
-      g.loge0 = n > (uint32_t)min_samples ? std::log10((double)max_models * (n - min_samples)) : 0.0;
-      g.bins_by_interval = kBins / (g.max_threshold - 0.0);
-      const double val = (g.max_threshold - 0.0) / static_cast<double>(kBins - 1);
-      for (int b = 0; b < kBins; ++b) {
-        g.bin_value[b] = val * static_cast<double>(b) + 0.0;
-        g.logalpha_bin[b] = logalpha0 + mult_error * std::log10(g.bin_value[b] + std::numeric_limits<float>::epsilon());
-      }
+      static const uint32_t kNoSize[2] = {1, 1};   // (the angular models: no image, w2 = h2 = 1 in the formulas)
+      const uint32_t* wh1 = d.angular ? kNoSize : src.indexed ? image_wh + 2 * (size_t)I : image_wh + 4 * p;
+      const uint32_t* wh2 = d.angular ? kNoSize : src.indexed ? image_wh + 2 * (size_t)J : image_wh + 4 * p + 2;
+      const double* K1 = !d.calibrated ? nullptr : src.indexed ? src.K + 9 * (size_t)I : src.K + 18 * p;
+      const double* K2 = !d.calibrated ? nullptr : src.indexed ? src.K + 9 * (size_t)J : src.K + 18 * p + 9;
+      geo_pair_constants(d, lo, n, wh1, wh2, K1, K2, src.pair_precision ? src.pair_precision[p] : opt->precision, hp[p], norm + 6 * p);
     }
   };
-  {
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < T; ++t) pool.emplace_back(prep, t);
-    prep(0);
-    for (auto& th : pool) th.join();
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < T; ++t) pool.emplace_back(prep, t);
+  prep(0);
+  for (auto& th : pool) th.join();
+  MVGX_REQUIRE(bad_pair.load() < 0, MVGX_ERR_ARG, "%s: pair %lld has a feature index out of range", src.entry, (long long)bad_pair.load());
+  return MVGX_OK;
+}
+
+// The work of a call: the pairs that run the estimation (more correspondences than a minimal sample), largest first - [0, c_global) with more than
+// `global_above` correspondences (tables in global scratch), the rest with their tables in LDS - and the two tables every wave reads. (Three more LDS
+// classes for larger pairs are not kept: one workgroup per CU, a pair of 2 000 correspondences 2.5 x slower per iteration than in the global form, call r5_61.)
+struct GeoPlan {
+  std::vector<uint32_t> order; uint32_t c_global = 0;
+  std::vector<float> l10;   // log10 of 0 .. n_max + 1
+  uint32_t mt_init[kMtN];   // std::mt19937(5489) before its first twist
+};
+void geo_plan(const GeoPair* hp, uint64_t n_pairs, int min_samples, uint32_t global_above, GeoPlan& plan) {
+  uint32_t n_max = 0;
+  plan.order.reserve(n_pairs);
+  for (uint64_t p = 0; p < n_pairs; ++p) {
+    n_max = std::max(n_max, hp[p].n);
+    if (hp[p].n > (uint32_t)min_samples) plan.order.push_back((uint32_t)p);
   }
-  MVGX_REQUIRE(bad_pair.load() < 0, MVGX_ERR_ARG, "mvgx_geofilter_f_acransac_indexed: pair %lld has a feature index out of range", (long long)bad_pair.load());
-  // pairs that run the estimation (more correspondences than a minimal sample), by size class, largest first inside a class
-  std::vector<uint32_t> order;
-  order.reserve(n_pairs);
-  for (uint64_t p = 0; p < n_pairs; ++p) if (hp[p].n > (uint32_t)min_samples) order.push_back((uint32_t)p);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hp[a].n > hp[b].n; });
-  // [0, c_global): more than kCap0 correspondences (tables in global scratch); the rest: tables in LDS. MVGX_GEO_GLOBAL_ABOVE = a smaller
-  // bound (tests: the global form on small pairs)
-  uint32_t global_above = kCap0;
-  if (const char* e = getenv("MVGX_GEO_GLOBAL_ABOVE")) global_above = (uint32_t)std::min<int>((int)kCap0, std::max(1, atoi(e)));
-  uint32_t c_global = 0;
-  while (c_global < order.size() && hp[order[c_global]].n > global_above) ++c_global;
-  std::vector<float> l10(n_max + 2);
-  for (uint32_t i = 0; i <= n_max + 1; ++i) l10[i] = (float)::log10((double)static_cast<float>(i));   // log10 of a float through the C function, as the reference's unqualified call resolves
-  uint32_t mt_init[kMtN];
-  mt_init[0] = 5489u;
-  for (int i = 1; i < kMtN; ++i) mt_init[i] = 1812433253u * (mt_init[i - 1] ^ (mt_init[i - 1] >> 30)) + (uint32_t)i;
-  const auto t_prep = std::chrono::steady_clock::now();
-  // MVGX_GEO_TIMING=1: where a call's time goes, on stderr (host preparation | device memory | uploads issued | kernels + downloads | results)
-  const bool timing = getenv("MVGX_GEO_TIMING") != nullptr;
-  auto t_mark = t_prep;
-  double t_phase[4] = {0, 0, 0, 0};
-  auto mark = [&](int k) { const auto t = std::chrono::steady_clock::now(); t_phase[k] += std::chrono::duration<double, std::milli>(t - t_mark).count(); t_mark = t; };
+  std::stable_sort(plan.order.begin(), plan.order.end(), [&](uint32_t a, uint32_t b) { return hp[a].n > hp[b].n; });
+  while (plan.c_global < plan.order.size() && hp[plan.order[plan.c_global]].n > global_above) ++plan.c_global;
+  plan.l10.resize(n_max + 2);
+  for (uint32_t i = 0; i <= n_max + 1; ++i) plan.l10[i] = (float)::log10((double)static_cast<float>(i));   // log10 of a float through the C function, as the reference's unqualified call resolves
+  plan.mt_init[0] = 5489u;
+  for (int i = 1; i < kMtN; ++i) plan.mt_init[i] = 1812433253u * (plan.mt_init[i - 1] ^ (plan.mt_init[i - 1] >> 30)) + (uint32_t)i;
+}
+
+// Every device buffer of a call. Declare it BEFORE the StreamGuard of the stream its members enqueue on: drained first, freed after, on any exit.
+struct GeoDevice {
+  mvgx::DevBuf<GeoPair> pairs; mvgx::DevBuf<uint32_t> order; mvgx::DevBuf<float> l10; mvgx::DevBuf<uint32_t> mt; mvgx::DevBuf<double> norm;
+  mvgx::DevBuf<GeoResult> res; mvgx::DevBuf<uint8_t> mask; mvgx::DevBuf<uint32_t> tables;
+  mvgx::DevBuf<double2> x1, x2;       // normalised positions
+  mvgx::DevBuf<double> b1, b2;        // bearing vectors per match
+  mvgx::DevBuf<double2> raw1, raw2;   // gathered source: positions as given
+  mvgx::DevBuf<uint2> ij, pimg; mvgx::DevBuf<double2> feat; mvgx::DevBuf<uint64_t> fstart; mvgx::DevBuf<double> fbear;   // indexed source
+  uint64_t n_pairs = 0, n_total = 0, n_xy = 0, n_feat = 0;
+
+  int allocate(const GeoModelDesc& d, const GeoSource& src, uint64_t np, uint64_t nt, const GeoPlan& plan) {
+    n_pairs = np; n_total = nt;
+    n_xy = d.angular ? 0 : n_total;   // (the angular models never touch pixel positions)
+    n_feat = src.indexed && src.n_images ? src.feat_start[src.n_images] : 0;
+    int rc;
+    if ((rc = alloc(pairs, n_pairs)) || (rc = alloc(order, plan.order.size())) || (rc = alloc(x1, n_xy)) || (rc = alloc(x2, n_xy)) ||
+        (rc = alloc(l10, plan.l10.size())) || (rc = alloc(mt, kMtN)) || (rc = alloc(res, n_pairs)) || (rc = alloc(mask, n_total)) ||
+        (rc = alloc(norm, n_pairs * 6)))
+      return rc;
+    if (src.indexed && ((rc = alloc(ij, n_total)) || (rc = alloc(feat, d.angular ? 0 : n_feat)) || (rc = alloc(fstart, (size_t)src.n_images + 1)) || (rc = alloc(pimg, n_pairs)))) return rc;
+    if (!src.indexed && ((rc = alloc(raw1, n_xy)) || (rc = alloc(raw2, n_xy)))) return rc;
+    if (d.bearings && ((rc = alloc(b1, n_total * 3)) || (rc = alloc(b2, n_total * 3)) || (src.indexed && (rc = alloc(fbear, n_feat * 3))))) return rc;
+    return MVGX_OK;
+  }
+  template <typename T> static hipError_t up(mvgx::DevBuf<T>& dst, const void* src, size_t n, hipStream_t stream) {
+    return hipMemcpyAsync(dst.p, src, n * sizeof(T), hipMemcpyHostToDevice, stream);
+  }
+  int upload(const GeoModelDesc& d, const GeoSource& src, const GeoPair* hp, const double* hnorm, const GeoPlan& plan, hipStream_t stream) {
+    if (n_pairs) MVGX_HIP(up(pairs, hp, n_pairs, stream));
+    if (!plan.order.empty()) MVGX_HIP(up(order, plan.order.data(), plan.order.size(), stream));
+    if (n_total) {
+      if (src.indexed) {
+        MVGX_HIP(up(ij, src.ij, n_total, stream));
+        if (!d.angular) MVGX_HIP(up(feat, src.feat_xy, n_feat, stream));
+        MVGX_HIP(up(fstart, src.feat_start, (size_t)src.n_images + 1, stream));
+        MVGX_HIP(up(pimg, src.pair_images, n_pairs, stream));
+      } else if (!d.angular) {
+        MVGX_HIP(up(raw1, src.xI, n_total, stream));
+        MVGX_HIP(up(raw2, src.xJ, n_total, stream));
+      }
+      MVGX_HIP(up(norm, hnorm, n_pairs * 6, stream));
+      MVGX_HIP(hipMemsetAsync(mask.p, 0, n_total, stream));
+      if (d.bearings && src.indexed) MVGX_HIP(up(fbear, src.feat_bearing, n_feat * 3, stream));
+      if (d.bearings && !src.indexed) {
+        MVGX_HIP(up(b1, src.bI, n_total * 3, stream));
+        MVGX_HIP(up(b2, src.bJ, n_total * 3, stream));
+      }
+    }
+    MVGX_HIP(up(l10, plan.l10.data(), plan.l10.size(), stream));
+    MVGX_HIP(up(mt, plan.mt_init, kMtN, stream));
+    if (n_pairs) MVGX_HIP(hipMemsetAsync(res.p, 0, n_pairs * sizeof(GeoResult), stream));
+    return MVGX_OK;
+  }
+  // x1 / x2 (and b1 / b2 of an indexed source) from what was uploaded
+  int gather_normalize(const GeoModelDesc& d, const GeoSource& src, hipStream_t stream) {
+    if (!n_total) return MVGX_OK;
+    const dim3 grid((unsigned)n_pairs), block(256);
+    const uint32_t np = (uint32_t)n_pairs;
+    if (src.indexed) {
+      if (!d.angular) hipLaunchKernelGGL(geofilter_normalize_indexed_kernel, grid, block, 0, stream, pairs.p, norm.p, np, feat.p, fstart.p, pimg.p, ij.p, x1.p, x2.p);
+      if (d.bearings) hipLaunchKernelGGL(geofilter_gather_bearings_kernel, grid, block, 0, stream, pairs.p, np, fbear.p, fstart.p, pimg.p, ij.p, b1.p, b2.p);
+    } else if (!d.angular) {
+      hipLaunchKernelGGL(geofilter_normalize_kernel, grid, block, 0, stream, pairs.p, norm.p, np, raw1.p, raw2.p, x1.p, x2.p);
+    }
+    MVGX_HIP(hipGetLastError());
+    return MVGX_OK;
+  }
+  // the two classes of the plan: the same launch with the tables in global scratch and in LDS
+  int launch(int model, const GeoPlan& plan, const GeoForm& form, uint32_t max_iterations, hipStream_t stream) {
+    int rc;
+    if (plan.c_global && (rc = alloc(tables, 3 * ((size_t)n_total + 4 * (size_t)n_pairs + 4)))) return rc;
+    const GeoLaunch in_global{pairs.p, order.p, plan.c_global, 0, x1.p, x2.p, l10.p, mt.p, max_iterations, res.p, mask.p, tables.p, b1.p, b2.p, form.ahead, stream};
+    GeoLaunch in_lds = in_global;
+    in_lds.order = order.p + plan.c_global; in_lds.n_work = (uint32_t)plan.order.size() - plan.c_global; in_lds.n_cap = kCap0; in_lds.tables = nullptr;
+    return with_geo_model(model, [&](auto m) {
+      constexpr int MODEL = decltype(m)::value;
+      auto both = [&](auto ahead_form) {
+        constexpr bool kAheadForm = decltype(ahead_form)::value;
+        const int rcg = geo_launch<MODEL, true, kAheadForm>(in_global);
+        return rcg ? rcg : geo_launch<MODEL, false, kAheadForm>(in_lds);
+      };
+      if constexpr (geo_model(MODEL).ahead_form) {   // (the other models have one instantiation)
+        if (form.ahead > 1) return both(std::true_type{});
+      }
+      return both(std::false_type{});
+    });
+  }
+  int download(GeoResult* hr, uint8_t* inlier_mask, hipStream_t stream) {
+    if (n_pairs) MVGX_HIP(hipMemcpyAsync(hr, res.p, n_pairs * sizeof(GeoResult), hipMemcpyDeviceToHost, stream));
+    if (n_total) MVGX_HIP(hipMemcpyAsync(inlier_mask, mask.p, n_total, hipMemcpyDeviceToHost, stream));
+    MVGX_HIP(hipStreamSynchronize(stream));
+    return MVGX_OK;
+  }
+};
+
+// One pair's result in the reference's terms: Unnormalize (conditioning.cpp:80-89), unormalizeError, the 2.5 x minimal-sample
+// acceptance. ran: the pair had more correspondences than a minimal sample; t: its normalisation triple pair.
+void geo_result(const GeoModelDesc& d, bool ran, const GeoResult& r, const double* t, mvgx_geofilter_result& o) {
+  double Fm[9];
+  for (int u = 0; u < 9; ++u) Fm[u] = (ran && r.have_model) ? r.F[u] : ((u % 4 == 0) ? 1.0 : 0.0);   // m_F starts as the identity
+  double err = ran ? r.error_max : 0.0;
+  if (d.identity_norm) {
+    // ACKernelAdaptorEssential{,Ortho}: Unnormalize does nothing, unormalizeError(val) = val (the residual as it is)
+  } else if (d.angular) {
+    // ACKernelAdaptor_AngularRadianError: Unnormalize does nothing, unormalizeError(val) = sqrt(val): an angle in radians. The
+    // reference's solvers return unit vectors (eigenvectors): the model is scaled to unit Frobenius norm (its sign stays free).
+    if (ran && r.n_inliers > 0) err = std::sqrt(err);
+    if (ran && r.have_model) {
+      double n2 = 0.0;
+      for (int u = 0; u < 9; ++u) n2 += Fm[u] * Fm[u];
+      if (n2 > 0.0) for (int u = 0; u < 9; ++u) Fm[u] /= std::sqrt(n2);
+    }
+  } else if (ran && r.n_inliers > 0) {
+    const double N1[9] = {t[0], 0, t[1], 0, t[0], t[2], 0, 0, 1}, N2[9] = {t[3], 0, t[4], 0, t[3], t[5], 0, 0, 1};
+    double tmp[9], res[9];
+    if (d.nfa == kNfaPointToPoint) {   // UnnormalizerI (conditioning.cpp:80-82): H = N2^-1 H N1; N2 = [s 0 tx; 0 s ty; 0 0 1]
+      const double is = 1.0 / t[3];
+      const double N2i[9] = {is, 0, -t[4] * is, 0, is, -t[5] * is, 0, 0, 1};
+      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s_ = 0; for (int k = 0; k < 3; ++k) s_ += N2i[3 * a + k] * Fm[3 * k + b]; tmp[3 * a + b] = s_; }
+    } else {   // UnnormalizerT: F = N2^T F N1
+      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s_ = 0; for (int k = 0; k < 3; ++k) s_ += N2[3 * k + a] * Fm[3 * k + b]; tmp[3 * a + b] = s_; }
+    }
+    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s_ = 0; for (int k = 0; k < 3; ++k) s_ += tmp[3 * a + k] * N1[3 * k + b]; res[3 * a + b] = s_; }
+    std::memcpy(Fm, res, sizeof(res));
+    err = std::sqrt(err) / t[3];
+  }
+  std::memcpy(o.F, Fm, sizeof(Fm));
+  o.precision_robust = err;
+  o.nfa = ran ? r.min_nfa : 0.0;
+  o.n_inliers = ran ? r.n_inliers : 0;
+  o.ok = ran && (double)r.n_inliers > d.min_samples * 2.5;   // F_ACRobust.hpp:103, H_ACRobust.hpp:98
+}
+
+int geofilter_run(int device, int model, const GeoSource& src, const uint64_t* match_start, const uint32_t* image_wh,
+                  uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
+                  mvgx_geofilter_stats* stats) {
+  using clock = std::chrono::steady_clock;
+  const auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  const GeoModelDesc d = geo_model(model);
+  int rc;
+  if ((rc = geo_check_arguments(d, src, match_start, image_wh, n_pairs, opt, inlier_mask, results))) return rc;
+  const uint64_t n_total = match_start[n_pairs];
+  const auto t_begin = clock::now();
+  const GeoForm form = geo_form_from_env();
+  if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
+  // ---- host: the constants of every pair, the work plan. (Page-locked memory from the library's cache, not zeroed - every field of every pair is
+  // written: a fresh std::vector of 100 000 pairs was 50 MB of page faults per call, two thirds of this phase; the uploads from it are asynchronous DMA)
+  mvgx::HostArena host_mem;
+  GeoPair* hp = nullptr; double* norm = nullptr; GeoResult* hr = nullptr;   // (norm: {s1, tx1, ty1, s2, tx2, ty2} per pair)
+  if ((rc = host_mem.array(&hp, std::max<uint64_t>(n_pairs, 1))) || (rc = host_mem.array(&norm, std::max<uint64_t>(n_pairs, 1) * 6)) ||
+      (rc = host_mem.array(&hr, std::max<uint64_t>(n_pairs, 1))))
+    return rc;
+  if ((rc = geo_prepare_pairs(d, src, match_start, image_wh, n_pairs, opt, hp, norm))) return rc;
+  GeoPlan plan;
+  geo_plan(hp, n_pairs, d.min_samples, form.global_above, plan);
+  const double prepare_ms = ms_since(t_begin);
+  auto t_mark = clock::now();
+  double t_phase[4] = {0, 0, 0, 0};   // MVGX_GEO_TIMING: device memory | uploads issued | kernels + downloads | results
+  auto mark = [&](int k) { t_phase[k] += ms_since(t_mark); t_mark = clock::now(); };
   // ---- device ----
+  GeoDevice dev;   // (before the stream guard: drained first, freed after)
   hipStream_t stream = nullptr;
   if ((rc = mvgx::acquire_stream(&stream))) return rc;
   int stream_device = 0;
   MVGX_HIP(hipGetDevice(&stream_device));
   mvgx::StreamGuard sg{stream_device, stream};
-  ByteBuf d_pairs, d_order, d_x1, d_x2, d_l10, d_mt, d_res, d_mask, d_raw1, d_raw2, d_norm, d_feat, d_fstart, d_pimg, d_b1, d_b2, d_fbear;
-  const uint64_t n_feat = src.indexed && src.n_images ? src.feat_start[src.n_images] : 0;
-  const uint64_t n_xy = angular ? 0 : n_total;   // (the angular models never touch pixel positions)
-  if ((rc = alloc(d_pairs, n_pairs * sizeof(GeoPair))) || (rc = alloc(d_order, order.size() * sizeof(uint32_t))) || (rc = alloc(d_x1, n_xy * sizeof(double2))) ||
-      (rc = alloc(d_x2, n_xy * sizeof(double2))) || (rc = alloc(d_l10, l10.size() * sizeof(float))) || (rc = alloc(d_mt, sizeof(mt_init))) ||
-      (rc = alloc(d_res, n_pairs * sizeof(GeoResult))) || (rc = alloc(d_mask, n_total)) || (rc = alloc(d_norm, norm_size * sizeof(double))))
-    return rc;
-  if (src.indexed) {   // d_raw1: the index pairs
-    if ((rc = alloc(d_raw1, n_total * sizeof(uint2))) || (rc = alloc(d_feat, (angular ? 0 : n_feat) * sizeof(double2))) ||
-        (rc = alloc(d_fstart, ((size_t)src.n_images + 1) * sizeof(uint64_t))) || (rc = alloc(d_pimg, n_pairs * sizeof(uint2))))
-      return rc;
-  } else if ((rc = alloc(d_raw1, n_xy * sizeof(double2))) || (rc = alloc(d_raw2, n_xy * sizeof(double2)))) {
-    return rc;
-  }
-  if (bearings) {
-    if ((rc = alloc(d_b1, n_total * 3 * sizeof(double))) || (rc = alloc(d_b2, n_total * 3 * sizeof(double)))) return rc;
-    if (src.indexed && (rc = alloc(d_fbear, n_feat * 3 * sizeof(double)))) return rc;
-  }
+  if ((rc = dev.allocate(d, src, n_pairs, n_total, plan))) return rc;
   mark(0);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   MVGX_HIP(hipEventCreate(&e0));
   MVGX_HIP(hipEventCreate(&e1));
   mvgx::EventGuard eg{e0, e1};
-  if (n_pairs) MVGX_HIP(hipMemcpyAsync(d_pairs.p, hp, n_pairs * sizeof(GeoPair), hipMemcpyHostToDevice, stream));
-  if (!order.empty()) MVGX_HIP(hipMemcpyAsync(d_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-  if (n_total) {
-    if (src.indexed) {
-      MVGX_HIP(hipMemcpyAsync(d_raw1.p, src.ij, n_total * sizeof(uint2), hipMemcpyHostToDevice, stream));
-      if (!angular) MVGX_HIP(hipMemcpyAsync(d_feat.p, src.feat_xy, n_feat * sizeof(double2), hipMemcpyHostToDevice, stream));
-      MVGX_HIP(hipMemcpyAsync(d_fstart.p, src.feat_start, ((size_t)src.n_images + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-      MVGX_HIP(hipMemcpyAsync(d_pimg.p, src.pair_images, n_pairs * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    } else if (!angular) {
-      MVGX_HIP(hipMemcpyAsync(d_raw1.p, src.xI, n_total * sizeof(double2), hipMemcpyHostToDevice, stream));
-      MVGX_HIP(hipMemcpyAsync(d_raw2.p, src.xJ, n_total * sizeof(double2), hipMemcpyHostToDevice, stream));
-    }
-    MVGX_HIP(hipMemcpyAsync(d_norm.p, norm, norm_size * sizeof(double), hipMemcpyHostToDevice, stream));
-    MVGX_HIP(hipMemsetAsync(d_mask.p, 0, n_total, stream));
-    if (bearings) {
-      if (src.indexed) {
-        MVGX_HIP(hipMemcpyAsync(d_fbear.p, src.feat_bearing, n_feat * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-      } else {
-        MVGX_HIP(hipMemcpyAsync(d_b1.p, src.bI, n_total * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-        MVGX_HIP(hipMemcpyAsync(d_b2.p, src.bJ, n_total * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-      }
-    }
-  }
-  MVGX_HIP(hipMemcpyAsync(d_l10.p, l10.data(), l10.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-  MVGX_HIP(hipMemcpyAsync(d_mt.p, mt_init, sizeof(mt_init), hipMemcpyHostToDevice, stream));
-  if (n_pairs) MVGX_HIP(hipMemsetAsync(d_res.p, 0, n_pairs * sizeof(GeoResult), stream));
+  if ((rc = dev.upload(d, src, hp, norm, plan, stream))) return rc;
   MVGX_HIP(hipEventRecord(e0, stream));
   mark(1);
-  const uint32_t* ord = reinterpret_cast<const uint32_t*>(d_order.p);
-  const auto* px1 = reinterpret_cast<const double2*>(d_x1.p);
-  const auto* px2 = reinterpret_cast<const double2*>(d_x2.p);
-  if (n_total) {   // (plain pointers in the launch: the buffers own their memory and must not be captured by value)
-    const auto* pp = reinterpret_cast<const GeoPair*>(d_pairs.p);
-    const auto* pn = reinterpret_cast<const double*>(d_norm.p);
-    const auto *r1 = reinterpret_cast<const double2*>(d_raw1.p), *r2 = reinterpret_cast<const double2*>(d_raw2.p);
-    auto *o1 = reinterpret_cast<double2*>(d_x1.p), *o2 = reinterpret_cast<double2*>(d_x2.p);
-    if (src.indexed) {
-      const auto* ft = reinterpret_cast<const double2*>(d_feat.p);
-      const auto* fs = reinterpret_cast<const uint64_t*>(d_fstart.p);
-      const auto *pim = reinterpret_cast<const uint2*>(d_pimg.p), *mij = reinterpret_cast<const uint2*>(d_raw1.p);
-      if (!angular) hipLaunchKernelGGL(geofilter_normalize_indexed_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, pp, pn, (uint32_t)n_pairs, ft, fs, pim, mij, o1, o2);
-      if (bearings) {
-        const double* fb = reinterpret_cast<const double*>(d_fbear.p);
-        double *ob1 = reinterpret_cast<double*>(d_b1.p), *ob2 = reinterpret_cast<double*>(d_b2.p);
-        hipLaunchKernelGGL(geofilter_gather_bearings_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, pp, (uint32_t)n_pairs, fb, fs, pim, mij, ob1, ob2);
-      }
-    } else if (!angular) {
-      hipLaunchKernelGGL(geofilter_normalize_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, pp, pn, (uint32_t)n_pairs, r1, r2, o1, o2);
-    }
-    MVGX_HIP(hipGetLastError());
-  }
-  ByteBuf d_tables;
-  {
-    // fundamental / homography / essential models: samples drawn and solved ahead of their iterations, four side by side (1: one minimal solve per
-    // iteration, the form of rounds 3-4; results equal)
-    uint32_t e_ahead = kAhead;
-    if (const char* env = getenv("MVGX_GEO_AHEAD")) e_ahead = (uint32_t)std::min(kAhead, std::max(1, atoi(env)));
-    else if (const char* env2 = getenv("MVGX_GEO_E_AHEAD")) e_ahead = (uint32_t)std::min(kAhead, std::max(1, atoi(env2)));
-    auto* dp = reinterpret_cast<const GeoPair*>(d_pairs.p);
-    auto* dl = reinterpret_cast<const float*>(d_l10.p);
-    auto* dm = reinterpret_cast<const uint32_t*>(d_mt.p);
-    auto* dr = reinterpret_cast<GeoResult*>(d_res.p);
-    auto* dk = reinterpret_cast<uint8_t*>(d_mask.p);
-    const double *pb1 = reinterpret_cast<const double*>(d_b1.p), *pb2 = reinterpret_cast<const double*>(d_b2.p);
-    rc = model == kModelH ? launch_classes<kModelH>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, nullptr, nullptr, e_ahead)
-         : model == kModelEO ? launch_classes<kModelEO>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream)
-         : model == kModelEA8 ? launch_classes<kModelEA8>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, pb1, pb2)
-         : model == kModelEU3 ? launch_classes<kModelEU3>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, pb1, pb2)
-         : model == kModelE ? launch_classes<kModelE>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream,
-                                                      reinterpret_cast<const double*>(d_b1.p), reinterpret_cast<const double*>(d_b2.p), e_ahead)
-                            : launch_classes<kModelF>(dp, ord, order, c_global, kCap0, n_total, n_pairs, px1, px2, dl, dm, opt->max_iterations, dr, dk, d_tables, stream, nullptr, nullptr, e_ahead);
-    if (rc) return rc;
-  }
+  if ((rc = dev.gather_normalize(d, src, stream)) || (rc = dev.launch(model, plan, form, opt->max_iterations, stream))) return rc;
   MVGX_HIP(hipEventRecord(e1, stream));
-  if (n_pairs) MVGX_HIP(hipMemcpyAsync(hr, d_res.p, n_pairs * sizeof(GeoResult), hipMemcpyDeviceToHost, stream));
-  if (n_total) MVGX_HIP(hipMemcpyAsync(inlier_mask, d_mask.p, n_total, hipMemcpyDeviceToHost, stream));
-  MVGX_HIP(hipStreamSynchronize(stream));
+  if ((rc = dev.download(hr, inlier_mask, stream))) return rc;
   mark(2);
   float kernel_ms = 0.f;
   (void)hipEventElapsedTime(&kernel_ms, e0, e1);
-  // ---- results in the reference's terms: Unnormalize (conditioning.cpp:87-89), unormalizeError, the 2.5 x 7 acceptance ----
+  // ---- results, statistics ----
   uint64_t n_ok = 0, n_inl = 0, n_iter = 0, n_mod = 0, clocks = 0;
   for (uint64_t p = 0; p < n_pairs; ++p) {
-    mvgx_geofilter_result& o = results[p];
-    const GeoResult& r = hr[p];
-    const bool ran = hp[p].n > (uint32_t)min_samples;
-    if (ran) { n_iter += r.n_iterations; n_mod += r.n_models; clocks += r.clocks; }
-    double Fm[9];
-    for (int u = 0; u < 9; ++u) Fm[u] = (ran && r.have_model) ? r.F[u] : ((u % 4 == 0) ? 1.0 : 0.0);   // m_F starts as the identity
-    double err = ran ? r.error_max : 0.0;
-    if (ran && r.n_inliers > 0 && (model == kModelE || model == kModelEO)) {
-      // ACKernelAdaptorEssential{,Ortho}: Unnormalize does nothing, unormalizeError(val) = val (the residual as it is)
-    } else if (angular) {
-      // ACKernelAdaptor_AngularRadianError: Unnormalize does nothing, unormalizeError(val) = sqrt(val): an angle in radians. The
-      // reference's solvers return unit vectors (eigenvectors): the model is scaled to unit Frobenius norm (its sign stays free).
-      if (ran && r.n_inliers > 0) err = std::sqrt(err);
-      if (ran && r.have_model) {
-        double n2 = 0.0;
-        for (int u = 0; u < 9; ++u) n2 += Fm[u] * Fm[u];
-        if (n2 > 0.0) for (int u = 0; u < 9; ++u) Fm[u] /= std::sqrt(n2);
-      }
-    } else if (ran && r.n_inliers > 0) {
-      const double* t = &norm[6 * p];
-      const double N1[9] = {t[0], 0, t[1], 0, t[0], t[2], 0, 0, 1}, N2[9] = {t[3], 0, t[4], 0, t[3], t[5], 0, 0, 1};
-      double tmp[9], res[9];
-      if (model == kModelH) {   // UnnormalizerI (conditioning.cpp:80-82): H = N2^-1 H N1; N2 = [s 0 tx; 0 s ty; 0 0 1]
-        const double is = 1.0 / t[3];
-        const double N2i[9] = {is, 0, -t[4] * is, 0, is, -t[5] * is, 0, 0, 1};
-        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s_ = 0; for (int k = 0; k < 3; ++k) s_ += N2i[3 * a + k] * Fm[3 * k + b]; tmp[3 * a + b] = s_; }
-      } else   // UnnormalizerT: F = N2^T F N1
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s_ = 0; for (int k = 0; k < 3; ++k) s_ += N2[3 * k + a] * Fm[3 * k + b]; tmp[3 * a + b] = s_; }
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s_ = 0; for (int k = 0; k < 3; ++k) s_ += tmp[3 * a + k] * N1[3 * k + b]; res[3 * a + b] = s_; }
-      std::memcpy(Fm, res, sizeof(res));
-      err = std::sqrt(err) / t[3];
-    }
-    std::memcpy(o.F, Fm, sizeof(Fm));
-    o.precision_robust = err;
-    o.nfa = ran ? r.min_nfa : 0.0;
-    o.n_inliers = ran ? r.n_inliers : 0;
-    o.ok = ran && (double)r.n_inliers > min_samples * 2.5;
-    n_ok += o.ok; n_inl += o.ok ? o.n_inliers : 0;
+    const bool ran = hp[p].n > (uint32_t)d.min_samples;
+    if (ran) { n_iter += hr[p].n_iterations; n_mod += hr[p].n_models; clocks += hr[p].clocks; }
+    geo_result(d, ran, hr[p], norm + 6 * p, results[p]);
+    n_ok += results[p].ok; n_inl += results[p].ok ? results[p].n_inliers : 0;
   }
   if (stats) {
-    stats->n_pairs = n_pairs; stats->n_pairs_estimated = order.size(); stats->n_pairs_ok = n_ok; stats->n_inliers = n_inl;
-    stats->kernel_ms = kernel_ms;
-    mark(3);
-    if (timing)
-      fprintf(stderr, "[mvgx geofilter] %llu pairs, %llu matches: host preparation %.2f ms | device memory %.2f | uploads issued %.2f | kernels + downloads %.2f (kernels %.2f) | results %.2f\n",
-              (unsigned long long)n_pairs, (unsigned long long)n_total, std::chrono::duration<double, std::milli>(t_prep - t_begin).count(), t_phase[0], t_phase[1], t_phase[2],
-              (double)kernel_ms, t_phase[3]);
-    stats->host_prepare_ms = std::chrono::duration<double, std::milli>(t_prep - t_begin).count();
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    stats->n_pairs = n_pairs; stats->n_pairs_estimated = plan.order.size(); stats->n_pairs_ok = n_ok; stats->n_inliers = n_inl;
     stats->n_iterations = n_iter; stats->n_models = n_mod; stats->wave_clocks = clocks;
+    mark(3);
+    if (form.timing)
+      fprintf(stderr, "[mvgx geofilter] %llu pairs, %llu matches: host preparation %.2f ms | device memory %.2f | uploads issued %.2f | kernels + downloads %.2f (kernels %.2f) | results %.2f\n",
+              (unsigned long long)n_pairs, (unsigned long long)n_total, prepare_ms, t_phase[0], t_phase[1], t_phase[2], (double)kernel_ms, t_phase[3]);
+    stats->kernel_ms = kernel_ms; stats->host_prepare_ms = prepare_ms; stats->total_ms = ms_since(t_begin);
   }
   return MVGX_OK;
 }
@@ -1480,7 +1506,7 @@ extern "C" {
 int mvgx_geofilter_f_acransac(int device, const double* xI, const double* xJ, const uint64_t* match_start, const uint32_t* image_wh,
                               uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
                               mvgx_geofilter_stats* stats) {
-  GeoSource src;
+  GeoSource src{__func__};
   src.xI = xI; src.xJ = xJ;
   return geofilter_run(device, kModelF, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1488,7 +1514,7 @@ int mvgx_geofilter_f_acransac(int device, const double* xI, const double* xJ, co
 int mvgx_geofilter_h_acransac(int device, const double* xI, const double* xJ, const uint64_t* match_start, const uint32_t* image_wh,
                               uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
                               mvgx_geofilter_stats* stats) {
-  GeoSource src;
+  GeoSource src{__func__};
   src.xI = xI; src.xJ = xJ;
   return geofilter_run(device, kModelH, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1497,8 +1523,7 @@ int mvgx_geofilter_f_acransac_indexed(int device, const double* feat_xy, const u
                                       const uint32_t* pairs, const uint64_t* match_start, const uint32_t* ij, uint64_t n_pairs,
                                       const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
                                       mvgx_geofilter_stats* stats) {
-  GeoSource src;
-  src.indexed = true;
+  GeoSource src{__func__, true};
   src.feat_xy = feat_xy; src.feat_start = feat_start; src.n_images = n_images; src.pair_images = pairs; src.ij = ij;
   return geofilter_run(device, kModelF, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1507,8 +1532,7 @@ int mvgx_geofilter_h_acransac_indexed(int device, const double* feat_xy, const u
                                       const uint32_t* pairs, const uint64_t* match_start, const uint32_t* ij, uint64_t n_pairs,
                                       const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
                                       mvgx_geofilter_stats* stats) {
-  GeoSource src;
-  src.indexed = true;
+  GeoSource src{__func__, true};
   src.feat_xy = feat_xy; src.feat_start = feat_start; src.n_images = n_images; src.pair_images = pairs; src.ij = ij;
   return geofilter_run(device, kModelH, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1517,7 +1541,7 @@ int mvgx_geofilter_h_acransac_indexed(int device, const double* feat_xy, const u
 int mvgx_geofilter_e_acransac(int device, const double* xI, const double* xJ, const double* bearingI, const double* bearingJ, const uint64_t* match_start,
                               const uint32_t* image_wh, const double* K, uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask,
                               mvgx_geofilter_result* results, mvgx_geofilter_stats* stats) {
-  GeoSource src;
+  GeoSource src{__func__};
   src.xI = xI; src.xJ = xJ; src.bI = bearingI; src.bJ = bearingJ; src.K = K;
   return geofilter_run(device, kModelE, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1526,10 +1550,8 @@ int mvgx_geofilter_e_acransac_indexed(int device, const double* feat_xy, const d
                                       const double* image_K, uint32_t n_images, const uint32_t* pairs, const uint64_t* match_start, const uint32_t* ij,
                                       uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
                                       mvgx_geofilter_stats* stats) {
-  GeoSource src;
-  src.indexed = true;
-  src.feat_xy = feat_xy; src.feat_start = feat_start; src.n_images = n_images; src.pair_images = pairs; src.ij = ij;
-  src.feat_bearing = feat_bearing; src.K = image_K;
+  GeoSource src{__func__, true};
+  src.feat_xy = feat_xy; src.feat_start = feat_start; src.n_images = n_images; src.pair_images = pairs; src.ij = ij; src.feat_bearing = feat_bearing; src.K = image_K;
   return geofilter_run(device, kModelE, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }
 
@@ -1537,7 +1559,7 @@ int mvgx_geofilter_e_acransac_indexed(int device, const double* feat_xy, const d
 // solver, 1 the three-point upright solver.
 int mvgx_geofilter_e_angular_acransac(int device, const double* bearingI, const double* bearingJ, const uint64_t* match_start, uint64_t n_pairs, int upright,
                                       const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results, mvgx_geofilter_stats* stats) {
-  GeoSource src;
+  GeoSource src{__func__};
   src.bI = bearingI; src.bJ = bearingJ;
   return geofilter_run(device, upright ? kModelEU3 : kModelEA8, src, match_start, nullptr, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1545,8 +1567,7 @@ int mvgx_geofilter_e_angular_acransac(int device, const double* bearingI, const 
 int mvgx_geofilter_e_angular_acransac_indexed(int device, const double* feat_bearing, const uint64_t* feat_start, uint32_t n_images, const uint32_t* pairs,
                                               const uint64_t* match_start, const uint32_t* ij, uint64_t n_pairs, int upright, const mvgx_geofilter_options* opt,
                                               uint8_t* inlier_mask, mvgx_geofilter_result* results, mvgx_geofilter_stats* stats) {
-  GeoSource src;
-  src.indexed = true;
+  GeoSource src{__func__, true};
   src.feat_start = feat_start; src.n_images = n_images; src.pair_images = pairs; src.ij = ij; src.feat_bearing = feat_bearing;
   return geofilter_run(device, upright ? kModelEU3 : kModelEA8, src, match_start, nullptr, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1554,7 +1575,7 @@ int mvgx_geofilter_e_angular_acransac_indexed(int device, const double* feat_bea
 // The orthographic essential matrix (Eo_Robust.hpp:35-165): xI / xJ (feat_xy) carry the hnormalized bearing vectors.
 int mvgx_geofilter_eo_acransac(int device, const double* xI, const double* xJ, const uint64_t* match_start, const uint32_t* image_wh, const double* pair_precision,
                                uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results, mvgx_geofilter_stats* stats) {
-  GeoSource src;
+  GeoSource src{__func__};
   src.xI = xI; src.xJ = xJ; src.pair_precision = pair_precision;
   return geofilter_run(device, kModelEO, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }
@@ -1562,8 +1583,7 @@ int mvgx_geofilter_eo_acransac(int device, const double* xI, const double* xJ, c
 int mvgx_geofilter_eo_acransac_indexed(int device, const double* feat_xy, const uint64_t* feat_start, const uint32_t* image_wh, uint32_t n_images,
                                        const uint32_t* pairs, const uint64_t* match_start, const uint32_t* ij, const double* pair_precision, uint64_t n_pairs,
                                        const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results, mvgx_geofilter_stats* stats) {
-  GeoSource src;
-  src.indexed = true;
+  GeoSource src{__func__, true};
   src.feat_xy = feat_xy; src.feat_start = feat_start; src.n_images = n_images; src.pair_images = pairs; src.ij = ij; src.pair_precision = pair_precision;
   return geofilter_run(device, kModelEO, src, match_start, image_wh, n_pairs, opt, inlier_mask, results, stats);
 }

@@ -56,14 +56,7 @@ def filter_pairs_angular(bI, bJ, match_start, functor=None, device=-1):
     n_pairs = len(start) - 1
     if int(start[-1]) != len(bI) or len(bI) != len(bJ):
         raise ValueError("filter_pairs_angular: inconsistent array sizes")
-    mask = np.zeros(max(len(bI), 1), np.uint8)
-    res = (_capi.GeofilterResult * max(n_pairs, 1))()
-    st = _capi.GeofilterStats()
-    opt = _capi.GeofilterOptions(functor.m_dPrecision, functor.m_stIteration)
-    P = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    _capi.check(_capi.lib().mvgx_geofilter_e_angular_acransac(int(device), P(bI), P(bJ), P(start), n_pairs, int(functor.isUprightEssentialMatrix),
-                                                              C.byref(opt), P(mask), C.cast(res, C.c_void_p), C.byref(st)))
-    return mask[:len(bI)].astype(bool), _results_array(res, n_pairs), st
+    return _run("mvgx_geofilter_e_angular_acransac", device, [bI, bJ, start, n_pairs, int(functor.isUprightEssentialMatrix)], len(bI), n_pairs, functor)
 
 
 class GeometricFilter_EOMatrix_RA(GeometricFilter_FMatrix_AC):
@@ -97,14 +90,7 @@ def filter_pairs_ortho_prepared(hI, hJ, match_start, image_wh, pair_precision, f
     n_pairs = len(start) - 1
     if len(wh) != n_pairs or len(prec) < n_pairs or int(start[-1]) != len(hI) or len(hI) != len(hJ):
         raise ValueError("filter_pairs_ortho_prepared: inconsistent array sizes")
-    mask = np.zeros(max(len(hI), 1), np.uint8)
-    res = (_capi.GeofilterResult * max(n_pairs, 1))()
-    st = _capi.GeofilterStats()
-    opt = _capi.GeofilterOptions(functor.m_dPrecision, functor.m_stIteration)
-    P = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    _capi.check(_capi.lib().mvgx_geofilter_eo_acransac(int(device), P(hI), P(hJ), P(start), P(wh), P(prec), n_pairs, C.byref(opt), P(mask),
-                                                       C.cast(res, C.c_void_p), C.byref(st)))
-    return mask[:len(hI)].astype(bool), _results_array(res, n_pairs), st
+    return _run("mvgx_geofilter_eo_acransac", device, [hI, hJ, start, wh, prec, n_pairs], len(hI), n_pairs, functor)
 
 
 def ortho_inputs(xI, xJ, start, K, precision):
@@ -151,14 +137,7 @@ def filter_pairs_e(xI, xJ, match_start, image_wh, K, functor=None, device=-1, be
     else:
         bI, bJ = (np.ascontiguousarray(b, np.float64).reshape(-1, 3) for b in bearings)
     bI = np.ascontiguousarray(bI); bJ = np.ascontiguousarray(bJ)
-    mask = np.zeros(max(len(xI), 1), np.uint8)
-    res = (_capi.GeofilterResult * max(n_pairs, 1))()
-    st = _capi.GeofilterStats()
-    opt = _capi.GeofilterOptions(functor.m_dPrecision, functor.m_stIteration)
-    P = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    _capi.check(_capi.lib().mvgx_geofilter_e_acransac(int(device), P(xI), P(xJ), P(bI), P(bJ), P(start), P(wh), P(K), n_pairs, C.byref(opt), P(mask),
-                                                      C.cast(res, C.c_void_p), C.byref(st)))
-    return mask[:len(xI)].astype(bool), _results_array(res, n_pairs), st
+    return _run("mvgx_geofilter_e_acransac", device, [xI, xJ, bI, bJ, start, wh, K, n_pairs], len(xI), n_pairs, functor)
 
 
 def filter_pairs(xI, xJ, match_start, image_wh, functor=None, device=-1):
@@ -173,15 +152,19 @@ def filter_pairs(xI, xJ, match_start, image_wh, functor=None, device=-1):
     n_pairs = len(start) - 1
     if len(wh) != n_pairs or int(start[-1]) != len(xI) or len(xI) != len(xJ):
         raise ValueError("filter_pairs: inconsistent array sizes")
-    mask = np.zeros(max(len(xI), 1), np.uint8)
+    return _run(functor._entry, device, [xI, xJ, start, wh, n_pairs], len(xI), n_pairs, functor)
+
+
+def _run(entry, device, head, n_matches, n_pairs, functor):
+    """One call of a mvgx_geofilter_* entry: entry(device, *head, &options, mask, results, &stats), the arrays of `head` as pointers.
+    Returns (inlier_mask (n_matches,) bool, results structured array, stats)."""
+    mask = np.zeros(max(n_matches, 1), np.uint8)
     res = (_capi.GeofilterResult * max(n_pairs, 1))()
     st = _capi.GeofilterStats()
     opt = _capi.GeofilterOptions(functor.m_dPrecision, functor.m_stIteration)
-    P = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    _capi.check(getattr(_capi.lib(), functor._entry)(int(device), P(xI), P(xJ), P(start), P(wh), n_pairs, C.byref(opt), P(mask),
-                                                      C.cast(res, C.c_void_p), C.byref(st)))
-    out = _results_array(res, n_pairs)
-    return mask[:len(xI)].astype(bool), out, st
+    P = lambda a: a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else a   # noqa: E731
+    _capi.check(getattr(_capi.lib(), entry)(int(device), *map(P, head), C.byref(opt), P(mask), C.cast(res, C.c_void_p), C.byref(st)))
+    return mask[:n_matches].astype(bool), _results_array(res, n_pairs), st
 
 
 def _results_array(res, n_pairs):
@@ -216,14 +199,7 @@ def filter_pairs_indexed(feats_xy, image_sizes, pairs, match_start, ij, functor=
     n_pairs = len(pairs)
     if len(wh) != n_images or len(start) != n_pairs + 1 or int(start[-1]) != len(ij):
         raise ValueError("filter_pairs_indexed: inconsistent array sizes")
-    mask = np.zeros(max(len(ij), 1), np.uint8)
-    res = (_capi.GeofilterResult * max(n_pairs, 1))()
-    st = _capi.GeofilterStats()
-    opt = _capi.GeofilterOptions(functor.m_dPrecision, functor.m_stIteration)
-    P = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    _capi.check(getattr(_capi.lib(), functor._entry_indexed)(int(device), P(feat), P(fstart), P(wh), n_images, P(pairs), P(start), P(ij), n_pairs,
-                                                              C.byref(opt), P(mask), C.cast(res, C.c_void_p), C.byref(st)))
-    return mask[:len(ij)].astype(bool), _results_array(res, n_pairs), st
+    return _run(functor._entry_indexed, device, [feat, fstart, wh, n_images, pairs, start, ij, n_pairs], len(ij), n_pairs, functor)
 
 
 def Robust_model_estimation(putative_matches, feats_xy, image_sizes, functor=None, device=-1):
