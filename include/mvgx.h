@@ -36,7 +36,8 @@ int mvgx_device_count(int* count);
  * 3: mvgx_ba_get_solver_info; 4: multi-device contexts, mvgx_match_run_stream; 5: geometric filter; 6: indexed filter entry,
  * cascade hashing on the device; 7: homography model of the geometric filter; 8: iteration / clock counters in
  * mvgx_geofilter_stats, essential-matrix model of the geometric filter; 9: mvgx_host_parallel_for; 10: guided matching;
- * 11: mvgx_cascade_hash_regions_typed; 12: mvgx_guided_match for float and binary regions) */
+ * 11: mvgx_cascade_hash_regions_typed; 12: mvgx_guided_match for float and binary regions). Pure additions keep the number:
+ * mvgx_triangulate_tracks came without a bump - a caller detects it by the symbol's presence (dlsym). */
 int mvgx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -598,6 +599,47 @@ int mvgx_guided_match(int device, const double* feat_xy, const void* desc, int d
                       uint32_t n_images, const uint32_t* pairs, const double* models, const double* error_th, uint64_t n_pairs, int kind,
                       double dist_ratio_sq, uint64_t* match_start, uint32_t** matches_ij, mvgx_guided_stats* stats /* may be NULL */);
 void mvgx_host_free(void* p);   /* releases an array the library allocated for the caller (mvgx_guided_match{,_u8}) */
+
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Triangulation of the tracks of a scene (no ABI bump: detect it by the symbol): the step between "tracks + poses" and the points
+ * bundle adjustment starts from -
+ *   sfm/sfm_data_triangulation.cpp:166-222  SfM_Data_Structure_Computation_Blind::triangulate
+ *   sfm/sfm_data_triangulation.cpp:319-434  SfM_Data_Structure_Computation_Robust::robust_triangulation
+ * as the global, stellar and sequential-v2 engines, structure_estimator.cpp:317 and main_ComputeStructureFromKnownPoses.cpp:287 call them.
+ * Track t owns the observations [track_start[t], track_start[t + 1]) in the order of the reference's Observations map (ascending view
+ * id); poses / intrinsics / intr_model have the layout of mvgx_ba_problem, all six MVGX_CAM_* models are accepted; obs_defined[o] == 0
+ * marks an observation whose view has no pose or no intrinsic (IsPoseAndIntrinsicDefined, its obs_pose / obs_intr are not read).
+ * MVGX_TRI_BLIND: track_triangulation (:45-101; more than two views TriangulateNViewAlgebraic, two views the inverse-depth-weighted
+ * midpoint), kept iff it succeeds and every observation passes CheiralityTest. MVGX_TRI_ROBUST: 2 n iterations of UniformSample(
+ * min_sample_index, n) on a fresh std::mt19937 per track, the sample triangulated (two-view samples by `method`, ETriangulationMethod
+ * of multiview/triangulation_method.hpp:15-22) and checked, every observation scored, the smallest error with at least
+ * min_required_inliers inliers wins (the earliest among equals); n == min_required_inliers == min_sample_index: one hypothesis from all
+ * observations. min_sample_index other than 2 or 3: MVGX_ERR_UNSUPPORTED; indices out of range, a track_start that decreases:
+ * MVGX_ERR_ARG. Parity: decisions and sample sequence as the reference's, points to rounding ("Triangulation"). */
+#define MVGX_TRI_BLIND 0
+#define MVGX_TRI_ROBUST 1
+typedef struct mvgx_triangulate_options {
+  int32_t mode;                     /* MVGX_TRI_*                                              */
+  int32_t method;                   /* ETriangulationMethod 0..3, two-view samples (robust)    */
+  double  max_reprojection_error;   /* pixels; 4.0                                             */
+  uint32_t min_required_inliers;    /* 3                                                       */
+  uint32_t min_sample_index;        /* 2 or 3                                                  */
+} mvgx_triangulate_options;
+typedef struct mvgx_triangulate_stats {
+  uint64_t n_tracks, n_kept, n_inlier_obs, n_hypotheses;
+  double kernel_ms, total_ms;
+} mvgx_triangulate_stats;
+void mvgx_triangulate_default_options(mvgx_triangulate_options*);
+int mvgx_triangulate_tracks(int device,
+    const double* poses /* n_poses x 6, layout of mvgx_ba_problem */, uint32_t n_poses,
+    const double* intrinsics /* n_intrinsics x MVGX_BA_MAX_INTR_PARAMS */, const int32_t* intr_model, uint32_t n_intrinsics,
+    const uint64_t* track_start /* n_tracks + 1 */, uint32_t n_tracks,
+    const uint32_t* obs_pose, const uint32_t* obs_intr, const double* obs_xy,
+    const uint8_t* obs_defined /* NULL = all; 0 = view without pose or intrinsic */,
+    const mvgx_triangulate_options* opt,
+    double* X /* n_tracks x 3; rejected tracks: zeros */, uint8_t* track_ok /* n_tracks */,
+    uint8_t* obs_inlier /* n_obs: blind = every observation of a kept track, robust = the inlier set */,
+    mvgx_triangulate_stats* stats /* may be NULL */);
 
 #ifdef __cplusplus
 }

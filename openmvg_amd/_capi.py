@@ -133,6 +133,19 @@ class GuidedStats(C.Structure):
                 ("n_descriptor_stages", C.c_uint64), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+MVGX_TRI_BLIND, MVGX_TRI_ROBUST = 0, 1
+
+
+class TriangulateOptions(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("method", C.c_int32), ("max_reprojection_error", C.c_double), ("min_required_inliers", C.c_uint32),
+                ("min_sample_index", C.c_uint32)]
+
+
+class TriangulateStats(C.Structure):
+    _fields_ = [("n_tracks", C.c_uint64), ("n_kept", C.c_uint64), ("n_inlier_obs", C.c_uint64), ("n_hypotheses", C.c_uint64),
+                ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 PROTOTYPES = {
     "mvgx_last_error": (C.c_char_p, []),
     "mvgx_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -223,6 +236,10 @@ PROTOTYPES = {
     "mvgx_guided_match": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_uint64, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(GuidedStats)]),
     "mvgx_host_free": (None, [C.c_void_p]),
+    "mvgx_triangulate_default_options": (None, [C.POINTER(TriangulateOptions)]),
+    "mvgx_triangulate_tracks": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(TriangulateStats)]),
 }
 
 _lib = None

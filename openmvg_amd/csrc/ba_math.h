@@ -230,6 +230,47 @@ MVGX_HD void eval_observation(int model, const double* intr, const double* pose,
   eval_observation_t<kJac>(model, intr, pose, trig, X, obs, r, Ji, Jc, Jp, off);
 }
 
+// The residual of eval_observation_t<false> for a point p that is ALREADY in the camera frame (the triangulation keeps R | t per pose and
+// scores one point against many observations): the same expressions in the same order, without the pose and the derivatives.
+MVGX_HD void project_residual(int model, const double* intr, const double p[3], const double* obs, double r[2]) {
+  if (model == kCamSpherical) {
+    const double w = intr[0], h = intr[1];
+    const double size = w > h ? w : h;
+    const double k = size / (2.0 * 3.14159265358979323846);
+    const double rho = sqrt(p[0] * p[0] + p[2] * p[2]);
+    r[0] = atan2(p[0], p[2]) * k + w / 2.0 - obs[0];
+    r[1] = -atan2(-p[1], rho) * k + h / 2.0 - obs[1];
+    return;
+  }
+  const double iz = 1.0 / p[2];
+  const double u = p[0] * iz, v = p[1] * iz;
+  const double f = intr[0];
+  const double r2 = u * u + v * v;
+  double xd = u, yd = v;
+  if (model == kCamRadial1 || model == kCamRadial3 || model == kCamBrown) {
+    const double k1 = intr[3], k2 = model == kCamRadial1 ? 0.0 : intr[4], k3 = model == kCamRadial1 ? 0.0 : intr[5];
+    const double r4 = r2 * r2, r6 = r4 * r2;
+    const double coeff = 1.0 + k1 * r2 + k2 * r4 + k3 * r6;
+    xd = u * coeff; yd = v * coeff;
+    if (model == kCamBrown) {
+      const double t1 = intr[6], t2 = intr[7];
+      xd += t2 * (r2 + 2.0 * u * u) + 2.0 * t1 * u * v;
+      yd += t1 * (r2 + 2.0 * v * v) + 2.0 * t2 * u * v;
+    }
+  } else if (model == kCamFisheye) {
+    const double rr = sqrt(r2);
+    if (rr > 1e-8) {
+      const double th = atan(rr);
+      const double th2 = th * th, th3 = th2 * th, th5 = th3 * th2, th7 = th5 * th2, th9 = th7 * th2;
+      const double thd = th + intr[3] * th3 + intr[4] * th5 + intr[5] * th7 + intr[6] * th9;
+      const double cdist = thd * (1.0 / rr);
+      xd = u * cdist; yd = v * cdist;
+    }
+  }
+  r[0] = intr[1] + xd * f - obs[0];
+  r[1] = intr[2] + yd * f - obs[1];
+}
+
 // PoseCenterConstraintCostFunction (sfm_data_BA_ceres.cpp:44-80): r = weight o (C(pose) - prior), C = -R(-aa) t.
 // When kJac: Jc (3 x 6, row-major) = [d r / d aa | d r / d t].
 // Unit ray of an image observation in world coordinates: R^T * bearing(get_ud_pixel(x)), normalised — the two vectors
@@ -254,7 +295,9 @@ MVGX_HD double radial_disto_r2(int model, const double* intr, double r2) {
   return r2 * (c * c);
 }
 
-MVGX_HD void observation_ray(int model, const double* intr, const double* pose, const double* obs, double ray[3]) {
+// The camera-frame part: the unit bearing cam(get_ud_pixel(x)) of an image position or, with undistort == false, cam(x) of the
+// position as given (IntrinsicBase::operator(), what CheiralityTest of Camera_Intrinsics.hpp:293-301 is handed by the triangulation).
+MVGX_HD void camera_bearing(int model, const double* intr, const double* obs, bool undistort, double b[3]) {
   double b0, b1, b2;
   if (model == kCamSpherical) {
     const double w = intr[0], h = intr[1];
@@ -265,7 +308,8 @@ MVGX_HD void observation_ray(int model, const double* intr, const double* pose, 
   } else {
     const double f = intr[0], cx = intr[1], cy = intr[2];
     double px = (obs[0] - cx) / f, py = (obs[1] - cy) / f;   // ima2cam
-    if (model == kCamRadial1 || model == kCamRadial3) {
+    if (!undistort) {   // cam(x): no distortion removed
+    } else if (model == kCamRadial1 || model == kCamRadial3) {
       const double r2 = px * px + py * py;
       double radius = 1.0;
       if (r2 != 0.0) {
@@ -312,6 +356,13 @@ MVGX_HD void observation_ray(int model, const double* intr, const double* pose, 
     const double n = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
     b0 /= n; b1 /= n; b2 /= n;
   }
+  b[0] = b0; b[1] = b1; b[2] = b2;
+}
+
+MVGX_HD void observation_ray(int model, const double* intr, const double* pose, const double* obs, double ray[3]) {
+  double b[3];
+  camera_bearing(model, intr, obs, true, b);
+  const double b0 = b[0], b1 = b[1], b2 = b[2];
   double p[3], R[9], A[9];
   const double zero[3] = {0.0, 0.0, 0.0};
   transform_point<true>(pose, zero, p, R, A);   // R row-major

@@ -5912,3 +5912,5 @@ int mvgx_ba_evaluate(mvgx_ba_ctx* c, double* cost, double* rmse) {
 }
 
 }  // extern "C"
+
+#include "mvgx_triangulate.h"   // mvgx_triangulate_tracks: the step between tracks + poses and the points BA adjusts

@@ -1,0 +1,485 @@
+"""Float64 restatement of the reference's track triangulation - the yardstick of the triangulation tests (TEST INFRASTRUCTURE).
+
+What is restated (paths under src/openMVG of the reference):
+  sfm/sfm_data_triangulation.cpp:45-101, :107-164, :166-222, :300-434   track_triangulation, the predicates, the blind and robust loops
+  multiview/triangulation.cpp:16-248                                     the four two-view solvers, Triangulate2View
+  multiview/triangulation_nview.cpp:39-61                                TriangulateNViewAlgebraic (numpy.linalg.eigh)
+  robust_estimation/rand_sampling.hpp:36-58                              UniformSample on std::mt19937(5489) with libstdc++ 11's bounded draw
+  cameras/Camera_Intrinsics.hpp:293-301                                  CheiralityTest
+Scalars are Python floats (IEEE double, one rounding per operation, sums in the reference's order); the 4 x 4 eigen / singular vectors
+come from LAPACK. The camera parts (bearing with and without undistortion, residual) restate openmvg_amd/csrc/ba_math.h and are pinned
+to the oracle's port_ba_eval_obs / port_ba_track_angles by tests/test_triangulation_ref_cpu.py.
+"""
+import functools
+import math
+
+import numpy as np
+
+PINHOLE, RADIAL1, RADIAL3, BROWN, FISHEYE, SPHERICAL = 1, 2, 3, 4, 5, 7
+MODELS = (PINHOLE, RADIAL1, RADIAL3, BROWN, FISHEYE, SPHERICAL)
+DLT, L1_ANGULAR, LINF_ANGULAR, IDW_MIDPOINT = 0, 1, 2, 3
+
+
+# ---- poses ----
+def rotation(aa):
+    """R of an angle-axis vector as the BA kernels form it: c I + s [w]x + (1 - c) w w^T; first order for theta^2 <= DBL_EPSILON"""
+    a0, a1, a2 = (float(v) for v in aa)
+    th2 = a0 * a0 + a1 * a1 + a2 * a2
+    if th2 > 2.220446049250313e-16:
+        th = math.sqrt(th2)
+        c, s = math.cos(th), math.sin(th)
+        k = 1.0 - c
+        w0, w1, w2 = a0 / th, a1 / th, a2 / th
+        return ((c + k * w0 * w0, -s * w2 + k * w0 * w1, s * w1 + k * w0 * w2),
+                (s * w2 + k * w1 * w0, c + k * w1 * w1, -s * w0 + k * w1 * w2),
+                (-s * w1 + k * w2 * w0, s * w0 + k * w2 * w1, c + k * w2 * w2))
+    return ((1.0, -a2, a1), (a2, 1.0, -a0), (-a1, a0, 1.0))
+
+
+def to_camera(R, t, X):
+    return tuple(R[i][0] * X[0] + R[i][1] * X[1] + R[i][2] * X[2] + t[i] for i in range(3))
+
+
+# ---- cameras ----
+def _radial_r2(model, intr, r2):
+    if model == RADIAL1:
+        c = 1.0 + r2 * intr[3]
+    else:
+        c = 1.0 + r2 * (intr[3] + r2 * (intr[4] + r2 * intr[5]))
+    return r2 * (c * c)
+
+
+def bearing(model, intr, xy, undistort):
+    """cam(get_ud_pixel(x)) (undistort) or cam(x): unit vector"""
+    intr = [float(v) for v in intr]
+    x, y = float(xy[0]), float(xy[1])
+    if model == SPHERICAL:
+        w, h = intr[0], intr[1]
+        size = max(w, h)
+        lon = (x - w / 2.0) / size * 2 * math.pi
+        lat = -((y - h / 2.0) / size) * 2 * math.pi
+        return (math.cos(lat) * math.sin(lon), -math.sin(lat), math.cos(lat) * math.cos(lon))
+    f, cx, cy = intr[0], intr[1], intr[2]
+    px, py = (x - cx) / f, (y - cy) / f
+    if undistort and model in (RADIAL1, RADIAL3):
+        r2 = px * px + py * py
+        radius = 1.0
+        if r2 != 0.0:
+            lo = up = r2
+            while _radial_r2(model, intr, lo) > r2:
+                lo /= 1.05
+            while _radial_r2(model, intr, up) < r2:
+                up *= 1.05
+            while 1e-10 < up - lo:
+                mid = .5 * (lo + up)
+                if _radial_r2(model, intr, mid) > r2:
+                    up = mid
+                else:
+                    lo = mid
+            radius = math.sqrt(.5 * (lo + up) / r2)
+        px, py = px * radius, py * radius
+    elif undistort and model == BROWN:
+        k1, k2, k3, t1, t2 = intr[3:8]
+        ux, uy = px, py
+        while True:
+            r2 = ux * ux + uy * uy
+            r4 = r2 * r2
+            r6 = r4 * r2
+            kd = k1 * r2 + k2 * r4 + k3 * r6
+            dx = ux * kd + (t2 * (r2 + 2 * ux * ux) + 2 * t1 * ux * uy)
+            dy = uy * kd + (t1 * (r2 + 2 * uy * uy) + 2 * t2 * ux * uy)
+            if not (abs(ux + dx - px) + abs(uy + dy - py) > 1e-10):
+                break
+            ux, uy = px - dx, py - dy
+        px, py = ux, uy
+    elif undistort and model == FISHEYE:
+        td = math.hypot(px, py)
+        scale = 1.0
+        if td > 1e-8:
+            th = td
+            for _ in range(10):
+                t2 = th * th
+                t4 = t2 * t2
+                t6 = t4 * t2
+                t8 = t6 * t2
+                th = td / (1 + intr[3] * t2 + intr[4] * t4 + intr[5] * t6 + intr[6] * t8)
+            scale = math.tan(th) / td
+        px, py = px * scale, py * scale
+    xu, yu = f * px + cx, f * py + cy
+    b0, b1 = (xu - cx) / f, (yu - cy) / f
+    n = math.sqrt(b0 * b0 + b1 * b1 + 1.0)
+    return (b0 / n, b1 / n, 1.0 / n)
+
+
+def residual(model, intr, p, xy):
+    """projection of the camera-frame point p minus the observation (the functors of sfm_data_BA_ceres_camera_functor.hpp)"""
+    if model == SPHERICAL:
+        w, h = intr[0], intr[1]
+        k = max(w, h) / (2.0 * math.pi)
+        rho = math.sqrt(p[0] * p[0] + p[2] * p[2])
+        return (math.atan2(p[0], p[2]) * k + w / 2.0 - xy[0], -math.atan2(-p[1], rho) * k + h / 2.0 - xy[1])
+    if p[2] == 0.0:
+        return (math.nan, math.nan)
+    iz = 1.0 / p[2]
+    u, v = p[0] * iz, p[1] * iz
+    f = intr[0]
+    r2 = u * u + v * v
+    xd, yd = u, v
+    if model in (RADIAL1, RADIAL3, BROWN):
+        k1 = intr[3]
+        k2, k3 = (0.0, 0.0) if model == RADIAL1 else (intr[4], intr[5])
+        r4 = r2 * r2
+        r6 = r4 * r2
+        coeff = 1.0 + k1 * r2 + k2 * r4 + k3 * r6
+        xd, yd = u * coeff, v * coeff
+        if model == BROWN:
+            t1, t2 = intr[6], intr[7]
+            xd += t2 * (r2 + 2.0 * u * u) + 2.0 * t1 * u * v
+            yd += t1 * (r2 + 2.0 * v * v) + 2.0 * t2 * u * v
+    elif model == FISHEYE:
+        rr = math.sqrt(r2)
+        if rr > 1e-8:
+            th = math.atan(rr)
+            th2 = th * th
+            th3 = th2 * th
+            th5 = th3 * th2
+            th7 = th5 * th2
+            th9 = th7 * th2
+            thd = th + intr[3] * th3 + intr[4] * th5 + intr[5] * th7 + intr[6] * th9
+            cdist = thd * (1.0 / rr)
+            xd, yd = u * cdist, v * cdist
+    return (intr[1] + xd * f - xy[0], intr[2] + yd * f - xy[1])
+
+
+# ---- vectors ----
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _dot(a, b):
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+
+
+def _normalized(a):
+    s = _dot(a, a)
+    n = math.sqrt(s) if s > 0.0 else 1.0
+    return (a[0] / n, a[1] / n, a[2] / n)
+
+
+def _to_world(R, t, x):
+    d = (x[0] - t[0], x[1] - t[1], x[2] - t[2])
+    return tuple(R[0][j] * d[0] + R[1][j] * d[1] + R[2][j] * d[2] for j in range(3))
+
+
+def _hnormalized(v):
+    with np.errstate(all="ignore"):
+        return tuple(float(x) for x in np.asarray(v[:3], np.float64) / np.float64(v[3]))
+
+
+# ---- two views (triangulation.cpp) ----
+def _point_from_rays(m0, m1, t, R1, t1):
+    z = _cross(m1, m0)
+    z2 = _dot(z, z)
+    if z2 == 0.0:
+        return False, (math.nan,) * 3
+    l0 = _dot(z, _cross(t, m1)) / z2
+    l1 = _dot(z, _cross(t, m0)) / z2
+    xp = tuple(t[i] + l0 * m0[i] for i in range(3))
+    return (l0 > 0.0 and l1 > 0.0), _to_world(R1, t1, xp)
+
+
+def two_view(method, R0, t0, x0, R1, t1, x1):
+    """Triangulate2View -> (ok, X)"""
+    if method == DLT:
+        P0 = np.hstack([np.asarray(R0), np.asarray(t0)[:, None]])
+        P1 = np.hstack([np.asarray(R1), np.asarray(t1)[:, None]])
+        D = np.stack([x0[0] * P0[2] - x0[2] * P0[0], x0[1] * P0[2] - x0[2] * P0[1], x1[0] * P1[2] - x1[2] * P1[0], x1[1] * P1[2] - x1[2] * P1[1]])
+        X = _hnormalized(np.linalg.svd(D)[2][3])
+        return (to_camera(R0, t0, X)[2] > 0.0 and to_camera(R1, t1, X)[2] > 0.0), X
+    R = [[sum(R1[i][k] * R0[j][k] for k in range(3)) for j in range(3)] for i in range(3)]
+    t = tuple(t1[i] - (R[i][0] * t0[0] + R[i][1] * t0[1] + R[i][2] * t0[2]) for i in range(3))
+    Rx0 = tuple(R[i][0] * x0[0] + R[i][1] * x0[1] + R[i][2] * x0[2] for i in range(3))
+    if method == L1_ANGULAR:
+        ca, cb = _cross(_normalized(Rx0), t), _cross(_normalized(x1), t)
+        if _dot(ca, ca) <= _dot(cb, cb):
+            n1 = _normalized(_cross(x1, t))
+            s = _dot(Rx0, n1)
+            return _point_from_rays(tuple(Rx0[i] - s * n1[i] for i in range(3)), x1, t, R1, t1)
+        n0 = _normalized(_cross(Rx0, t))
+        s = _dot(x1, n0)
+        return _point_from_rays(Rx0, tuple(x1[i] - s * n0[i] for i in range(3)), t, R1, t1)
+    if method == LINF_ANGULAR:
+        rn, xn = _normalized(Rx0), _normalized(x1)
+        na = _cross(tuple(rn[i] + xn[i] for i in range(3)), t)
+        nb = _cross(tuple(rn[i] - xn[i] for i in range(3)), t)
+        npr = _normalized(na) if _dot(na, na) >= _dot(nb, nb) else _normalized(nb)
+        s0, s1 = _dot(Rx0, npr), _dot(x1, npr)
+        return _point_from_rays(tuple(Rx0[i] - s0 * npr[i] for i in range(3)), tuple(x1[i] - s1 * npr[i] for i in range(3)), t, R1, t1)
+    assert method == IDW_MIDPOINT
+    cp, cq, cr = _cross(Rx0, x1), _cross(Rx0, t), _cross(x1, t)
+    pn, qn, rn = math.sqrt(_dot(cp, cp)), math.sqrt(_dot(cq, cq)), math.sqrt(_dot(cr, cr))
+    if pn == 0.0 or qn + rn == 0.0:
+        return False, (math.nan,) * 3
+    w, rp, qp = qn / (qn + rn), rn / pn, qn / pn
+    xp = tuple(w * (t[i] + rp * (Rx0[i] + x1[i])) for i in range(3))
+    X = _to_world(R1, t1, xp)
+    l0 = tuple(rp * Rx0[i] for i in range(3))
+    l1 = tuple(qp * x1[i] for i in range(3))
+
+    def sq(s0, s1):
+        e = tuple(t[i] + s0 * l0[i] + s1 * l1[i] for i in range(3))
+        return _dot(e, e)
+    return sq(1, -1) < min(min(sq(1, 1), sq(-1, -1)), sq(-1, 1)), X
+
+
+# ---- N views (triangulation_nview.cpp:39-61) ----
+def nview_cost(R, t, b):
+    """cost^T cost of one view, cost = P - b b^T P with b = bearing.normalized()"""
+    P = np.hstack([np.asarray(R, np.float64), np.asarray(t, np.float64)[:, None]])
+    bn = np.asarray(_normalized(b))
+    cost = P - np.outer(bn, bn) @ P
+    return cost.T @ cost
+
+
+def nview_algebraic(costs):
+    AtA = np.zeros((4, 4))
+    for c in costs:
+        AtA = AtA + c
+    return _hnormalized(np.linalg.eigh(AtA)[1][:, 0])
+
+
+# ---- the sample sequence (rand_sampling.hpp:36-58 on std::mt19937(default_seed)) ----
+def _mt19937():
+    bg = np.random.MT19937()
+    bg._legacy_seeding(5489)   # init_genrand(5489): the state of std::mt19937(std::mt19937::default_seed)
+    return bg
+
+
+def _below(bg, rng):
+    """std::uniform_int_distribution<uint32_t>(0, rng - 1) of libstdc++ 11 on a 32-bit engine (bits/uniform_int_dist.h, _S_nd)"""
+    product = int(bg.random_raw()) * rng
+    low = product & 0xffffffff
+    if low < rng:
+        threshold = ((1 << 32) - rng) % rng
+        while low < threshold:
+            product = int(bg.random_raw()) * rng
+            low = product & 0xffffffff
+    return product >> 32
+
+
+@functools.lru_cache(maxsize=None)
+def sample_table(k, n):
+    """the 2 n samples of a track of n observations, each ordered by observation position (ObservationsSampler inserts into a map)"""
+    bg = _mt19937()
+    out = []
+    for _ in range(2 * n):
+        s = []
+        while len(s) < k:
+            v = _below(bg, n)
+            if v not in s:
+                s.append(v)
+        out.append(tuple(sorted(s)))
+    return tuple(out)
+
+
+# ---- the loops ----
+class Result:
+    def __init__(self, n_tracks, n_obs):
+        self.X = np.zeros((n_tracks, 3))
+        self.ok = np.zeros(n_tracks, bool)
+        self.inl = np.zeros(n_obs, bool)
+        self.n_hypotheses = 0
+        self.margin = math.inf   # smallest decision margin: |residual^2 - bound| / bound, |cheirality dot|
+        self.gap = math.inf      # smallest relative gap between a hypothesis error and the distinct best error it is compared with (:416)
+
+
+class _Obs:
+    __slots__ = ("defined", "R", "t", "bu", "br", "xy", "model", "intr", "cost")
+
+
+def _observations(poses, intrinsics, intr_model, obs_pose, obs_intr, obs_xy, obs_defined, lo, hi, cache):
+    out = []
+    for o in range(lo, hi):
+        ob = _Obs()
+        ob.defined = obs_defined is None or bool(obs_defined[o])
+        if ob.defined:
+            ip, ii = int(obs_pose[o]), int(obs_intr[o])
+            if ip not in cache:
+                cache[ip] = (rotation(poses[ip][:3]), tuple(float(v) for v in poses[ip][3:6]))
+            ob.R, ob.t = cache[ip]
+            ob.model, ob.intr = int(intr_model[ii]), [float(v) for v in intrinsics[ii]]
+            ob.xy = (float(obs_xy[o][0]), float(obs_xy[o][1]))
+            ob.bu = bearing(ob.model, ob.intr, ob.xy, True)
+            ob.br = bearing(ob.model, ob.intr, ob.xy, False)
+            ob.cost = nview_cost(ob.R, ob.t, ob.bu)
+        out.append(ob)
+    return out
+
+
+def _track_triangulation(obs, method):
+    """track_triangulation (:45-101) -> (ok, X)"""
+    if len(obs) < 2 or not all(o.defined for o in obs):
+        return False, None
+    if len(obs) > 2:
+        return True, nview_algebraic([o.cost for o in obs])
+    return two_view(method, obs[0].R, obs[0].t, obs[0].bu, obs[1].R, obs[1].t, obs[1].bu)
+
+
+def _score(res, ob, X, bound2):
+    """0: not counted, 1: inlier, 2: outlier; + residual^2. Records the decision margins."""
+    if not ob.defined:
+        return 0, 0.0
+    p = to_camera(ob.R, ob.t, X)
+    dot = _dot(ob.br, p)
+    if not math.isnan(dot):
+        res.margin = min(res.margin, abs(dot))
+    if not dot > 0.0:
+        return 0, 0.0
+    r = residual(ob.model, ob.intr, p, ob.xy)
+    r2 = r[0] * r[0] + r[1] * r[1]
+    if not math.isnan(r2):
+        res.margin = min(res.margin, abs(r2 - bound2) / bound2)
+    return (1 if r2 < bound2 else 2), r2
+
+
+def triangulate(poses, intrinsics, intr_model, track_start, obs_pose, obs_intr, obs_xy, mode="robust", method=IDW_MIDPOINT,
+                max_reprojection_error=4.0, min_required_inliers=3, min_sample_index=3, obs_defined=None):
+    poses = np.asarray(poses, np.float64).reshape(-1, 6)
+    intrinsics = np.asarray(intrinsics, np.float64).reshape(-1, 8)
+    obs_xy = np.asarray(obs_xy, np.float64).reshape(-1, 2)
+    track_start = [int(v) for v in track_start]
+    n_tracks = len(track_start) - 1
+    res = Result(n_tracks, track_start[-1])
+    bound2 = float(max_reprojection_error) * float(max_reprojection_error)
+    cache = {}
+    for t in range(n_tracks):
+        lo, hi = track_start[t], track_start[t + 1]
+        obs = _observations(poses, intrinsics, intr_model, obs_pose, obs_intr, obs_xy, obs_defined, lo, hi, cache)
+        n = hi - lo
+        if mode == "blind":   # :193-206
+            ok, X = _track_triangulation(obs, IDW_MIDPOINT)
+            if ok:
+                seen = False
+                for ob in obs:
+                    if not ob.defined:
+                        continue
+                    seen = True
+                    if _score(res, ob, X, math.inf)[0] == 0:
+                        ok = False
+                        break
+                ok = ok and seen
+            if ok:
+                res.X[t] = X; res.ok[t] = True; res.inl[lo:hi] = True
+            continue
+        k, need = int(min_sample_index), int(min_required_inliers)
+        if n < need or n < k:   # :327-330
+            continue
+        if need == k and n == need:   # :344-357
+            ok, X = _track_triangulation(obs, method)
+            if ok:
+                seen = False
+                for ob in obs:
+                    if not ob.defined:
+                        continue
+                    seen = True
+                    if _score(res, ob, X, bound2)[0] != 1:
+                        ok = False
+                        break
+                ok = ok and seen
+            if ok:
+                res.X[t] = X; res.ok[t] = True; res.inl[lo:hi] = True
+            continue
+        best_err, best_X, best_in = 1.7976931348623157e308, None, None
+        res.n_hypotheses += 2 * n
+        for sample in sample_table(k, n):
+            sub = [obs[j] for j in sample]
+            ok, X = _track_triangulation(sub, method)
+            if not ok:
+                continue
+            if not all(_score(res, ob, X, bound2)[0] == 1 for ob in sub):
+                continue
+            err, inliers = 0.0, []
+            for j, ob in enumerate(obs):
+                s, r2 = _score(res, ob, X, bound2)
+                if s == 1:
+                    inliers.append(j); err += r2
+                elif s == 2:
+                    err += bound2
+            if best_in is not None and err != best_err:   # the comparison of :416 between two distinct errors
+                res.gap = min(res.gap, abs(err - best_err) / max(err, best_err))
+            if err < best_err and len(inliers) >= need:
+                best_err, best_X, best_in = err, X, inliers
+        if best_in:
+            res.X[t] = best_X; res.ok[t] = True
+            res.inl[[lo + j for j in best_in]] = True
+    return res
+
+
+# ---- the scene family of the tests ----
+def ring_cameras(n_cams, rng):
+    """cameras on a ring of radius 5 looking at the origin: angle jitter sigma 0.05 rad, height sigma 0.3 -> poses (n, 6)"""
+    from scipy.spatial.transform import Rotation
+    ang = 2 * np.pi * np.arange(n_cams) / n_cams + 0.05 * rng.standard_normal(n_cams)
+    Cc = np.stack([5 * np.cos(ang), 0.3 * rng.standard_normal(n_cams), 5 * np.sin(ang)], axis=1)
+    z = -Cc / np.linalg.norm(Cc, axis=1, keepdims=True)
+    x = np.cross(np.array([0.0, 1.0, 0.0])[None], z); x /= np.linalg.norm(x, axis=1, keepdims=True)
+    y = np.cross(z, x)
+    R = np.stack([x, y, z], axis=1)
+    return np.concatenate([Rotation.from_matrix(R).as_rotvec(), -np.einsum("nij,nj->ni", R, Cc)], axis=1)
+
+
+def model_intrinsics(model, rng):
+    """f = 1000, principal point (500, 500), small distortion (k1 ~ +-0.05, Brown t ~ 1e-3); spherical: a 4000 x 2000 panorama"""
+    row = np.zeros(8)
+    if model == SPHERICAL:
+        row[:2] = (4000.0, 2000.0)
+        return row
+    row[:3] = (1000.0, 500.0, 500.0)
+    sign = 1.0 if rng.random() < 0.5 else -1.0
+    if model in (RADIAL1, RADIAL3, BROWN):
+        row[3] = sign * 0.05
+    if model in (RADIAL3, BROWN):
+        row[4:6] = (0.01, -0.002)
+    if model == BROWN:
+        row[6:8] = (1e-3, -1e-3)
+    if model == FISHEYE:
+        row[3:7] = (sign * 0.05, 0.01, -0.002, 0.0005)
+    return row
+
+
+def scene(n_cams, track_lens, model=PINHOLE, seed=0, noise=0.5, displaced=True, n_displaced=None):
+    """dict of the arrays mvgx_triangulate_tracks takes (+ "points": the true positions). Points uniform in [-1, 1]^3, pixel noise sigma
+    `noise`; in a track of five or more observations at most one (exactly n_displaced if given) is displaced by +-[50, 300] px per axis."""
+    from openmvg_amd import synth
+    rng = np.random.default_rng(seed)
+    poses = ring_cameras(n_cams, rng)
+    intr = model_intrinsics(model, rng)[None]
+    pts = rng.uniform(-1, 1, (len(track_lens), 3))
+    obs_pose, obs_pt = [], []
+    for t, n in enumerate(track_lens):
+        n = int(n)
+        if n <= n_cams:
+            cams = np.sort(rng.choice(n_cams, size=n, replace=False))
+        else:   # more views than poses: some views share a pose (a rig, View::id_pose), never more than two
+            cams = np.sort(np.concatenate([np.arange(n_cams), rng.choice(n_cams, size=n - n_cams, replace=False)]))
+        obs_pose += list(cams); obs_pt += [t] * int(n)
+    obs_pose, obs_pt = np.array(obs_pose, np.uint32), np.array(obs_pt, np.int64)
+    xy = synth.project(model, np.repeat(intr, len(obs_pose), 0), poses[obs_pose], pts[obs_pt]) + noise * rng.standard_normal((len(obs_pose), 2))
+    start = np.concatenate([[0], np.cumsum(track_lens)]).astype(np.uint64)
+    moved = np.zeros(len(obs_pose), bool)
+    for t, n in enumerate(track_lens):
+        m = (1 if rng.random() < 0.5 else 0) if n_displaced is None else n_displaced
+        if not displaced or n < 5 or not m:
+            continue
+        for j in rng.choice(int(n), size=m, replace=False):
+            xy[int(start[t]) + int(j)] += rng.choice([-1.0, 1.0], 2) * rng.uniform(50, 300, 2)
+            moved[int(start[t]) + int(j)] = True
+    return dict(poses=poses, intrinsics=intr, intr_model=np.array([model], np.int32), track_start=start, obs_pose=obs_pose,
+                obs_intr=np.zeros(len(obs_pose), np.uint32), obs_xy=xy, points=pts, displaced=moved)
+
+
+ARGS = ("poses", "intrinsics", "intr_model", "track_start", "obs_pose", "obs_intr", "obs_xy")
+
+
+def args_of(sc):
+    return [sc[k] for k in ARGS]

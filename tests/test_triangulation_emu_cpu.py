@@ -1,0 +1,176 @@
+"""CPU: mvgx_triangulate_tracks - the device code of openmvg_amd/csrc/mvgx_triangulate.h under the HIP emulation (tests/_emu.py) against
+the float64 restatement of the reference (tests/_triangulation_ref.py): decisions equal, points within the tolerance of
+tests/_triangulation_cases.py. The -m gpu twin of this file is tests/test_triangulation_gpu.py."""
+import numpy as np
+import pytest
+
+from openmvg_amd import _capi, synth, triangulation
+from tests import _emu
+from tests import _triangulation_cases as cases
+from tests import _triangulation_ref as ref
+
+ROBUST_FORMS = [(2, 2), (3, 2), (3, 3)]   # (min_required_inliers, min_sample_index) of the reference's callers
+# group boundaries of the robust kernel: 16-lane groups up to 8 observations, LDS records and the inlier mask up to 64, rounds of 64 hypotheses above 32
+BOUNDARY_LENGTHS = [2, 3, 8, 9, 32, 33, 63, 64, 65]
+
+
+@pytest.fixture(autouse=True)
+def _emulated():
+    with _emu.emulated():
+        yield
+
+
+def _with_undefined(sc, tracks, seed=5):
+    """one observation of each named track becomes a view without pose or intrinsic; its indices are made unusable on purpose"""
+    sc = dict(sc)
+    rng = np.random.default_rng(seed)
+    sc["obs_defined"] = np.ones(len(sc["obs_pose"]), np.uint8)
+    sc["obs_pose"] = sc["obs_pose"].copy(); sc["obs_intr"] = sc["obs_intr"].copy()
+    for t in tracks:
+        lo, hi = int(sc["track_start"][t]), int(sc["track_start"][t + 1])
+        o = int(rng.integers(lo, hi))
+        sc["obs_defined"][o] = 0
+        sc["obs_pose"][o] = 0xFFFFFFFF; sc["obs_intr"][o] = 0xFFFFFFFF
+    return sc
+
+
+def _behind_track(model):
+    """three adjacent cameras of the ring and a point BEHIND them (off the middle camera's axis): the lines meet there, the rays of a
+    perspective camera do not. A spherical camera sees it like any other point."""
+    sc = ref.scene(8, [3], model=model, seed=77, noise=0.0)
+    sc["obs_pose"] = np.array([0, 1, 2], np.uint32)
+    R = synth._rodrigues(sc["poses"][1, :3])[0]
+    centre = -R.T @ sc["poses"][1, 3:6]
+    sc["points"] = (1.5 * centre + (0.3, 0.2, 0.1))[None]
+    sc["obs_xy"] = synth.project(model, np.repeat(sc["intrinsics"], 3, 0), sc["poses"][:3], np.repeat(sc["points"], 3, 0))
+    return sc
+
+
+def test_reference_unit_test_statements():
+    """sfm_data_triangulation_test.cpp:25-111 on a noise-free 6-view, 32-point pinhole scene"""
+    sc = ref.scene(6, [6] * 32, seed=1, noise=0.0, displaced=False)
+    for mode in ("blind", "robust"):
+        X, ok, inl, stats = cases.run_device(sc, mode=mode)
+        assert ok.all() and inl.all() and stats.n_kept == 32
+        assert np.abs(X - sc["points"]).max() < 1e-8
+    # a landmark without observations is removed
+    empty = dict(sc)
+    empty["track_start"] = np.concatenate([[0], sc["track_start"]]).astype(np.uint64)
+    for mode in ("blind", "robust"):
+        X, ok, inl, _ = cases.run_device(empty, mode=mode)
+        assert not ok[0] and ok[1:].all() and np.all(X[0] == 0.0)
+    # a landmark with two grossly displaced observations out of six is still there
+    one = ref.scene(6, [6], seed=1, noise=0.0, displaced=False)
+    one["obs_xy"][0] += (-10.0, -10000.0)
+    one["obs_xy"][1] += (-10000.0, -10000.0)
+    X, ok, inl, _ = cases.run_device(one, mode="robust")
+    assert ok[0] and list(inl) == [False, False, True, True, True, True]
+    assert np.abs(X - one["points"]).max() < 1e-8
+
+
+@pytest.mark.parametrize("model", ref.MODELS)
+def test_blind_matches_the_restatement(model):
+    short = ref.scene(8, [2, 3, 4] * 12, model=model, seed=20 + model)
+    (_, ok, _, _), _, dev_short = cases.compare(f"blind-short-{model}", short, mode="blind")
+    long_ = ref.scene(72, [9, 40] * 4, model=model, seed=40 + model)
+    (_, ok2, _, _), _, dev_long = cases.compare(f"blind-long-{model}", long_, mode="blind")
+    assert ok.sum() + ok2.sum() >= 40   # the family triangulates: the comparison is not one of rejections
+    print(f"model {model}: largest |dX| {max(dev_short, dev_long):.3g}")
+
+
+@pytest.mark.parametrize("model", ref.MODELS)
+def test_blind_rejections(model):
+    sc = _with_undefined(ref.scene(8, [2, 3, 6, 6], model=model, seed=60 + model), [1, 2])
+    (_, ok, _, _), _, _ = cases.compare(f"blind-undefined-{model}", sc, mode="blind")
+    assert list(ok[[1, 2]]) == [False, False] and ok[3]
+    (_, ok, _, _), _, _ = cases.compare(f"blind-behind-{model}", _behind_track(model), mode="blind")
+    assert ok[0] == (model == ref.SPHERICAL)
+
+
+def _robust_methods(k):
+    return [ref.DLT, ref.L1_ANGULAR, ref.LINF_ANGULAR, ref.IDW_MIDPOINT] if k == 2 else [ref.IDW_MIDPOINT]
+
+
+@pytest.mark.parametrize("need,k", ROBUST_FORMS)
+def test_robust_group_boundaries(need, k):
+    """every length at which the kernel changes form, the all-observations case (n == need == k, the first tracks) and views without pose"""
+    sc = ref.scene(72, BOUNDARY_LENGTHS * 2, seed=300 + 10 * need + k)
+    sc = _with_undefined(sc, [12, 13, 15, 17])   # tracks of 9, 32, 63 and 65 observations
+    for method in _robust_methods(k):
+        (_, ok, inl, _), want, _ = cases.compare(f"robust-boundaries-{need}-{k}", sc, method=method, min_required_inliers=need, min_sample_index=k)
+        assert ok.sum() >= 14
+        assert not inl[sc["displaced"]].any()   # no displaced observation ends up an inlier
+
+
+@pytest.mark.parametrize("need,k", ROBUST_FORMS)
+def test_robust_mixed_lengths(need, k):
+    """ragged 16-lane groups (four tracks per wave), whole-wave groups and the all-observations case in one call"""
+    sc = ref.scene(72, cases.mixed_lengths(150, 2, 12, seed=7), seed=450 + 10 * need + k)
+    for method in _robust_methods(k):
+        (_, ok, _, stats), _, _ = cases.compare(f"robust-mixed-{need}-{k}", sc, method=method, min_required_inliers=need, min_sample_index=k)
+        assert ok.sum() >= 100
+        n = np.diff(sc["track_start"].astype(np.int64))
+        loop = (n >= need) & (n >= k) & ~((need == k) & (n == need))
+        assert stats.n_hypotheses == 2 * n[loop].sum()
+
+
+@pytest.mark.parametrize("model", ref.MODELS)
+def test_robust_camera_models(model):
+    sc = ref.scene(8, cases.mixed_lengths(60, 2, 8, seed=9), model=model, seed=500 + model)
+    (_, ok, _, _), _, _ = cases.compare(f"robust-models-{model}", sc)
+    assert ok.sum() >= 30
+    (_, ok, _, _), _, _ = cases.compare(f"robust-behind-{model}", _behind_track(model))
+    assert ok[0] == (model == ref.SPHERICAL)
+
+
+def test_track_order_does_not_matter():
+    sc = ref.scene(72, cases.mixed_lengths(60, 2, 40, seed=3), seed=600)
+    X, ok, inl, _ = cases.run_device(sc)
+    perm = np.random.default_rng(0).permutation(60)
+    n = np.diff(sc["track_start"].astype(np.int64))
+    order = np.concatenate([np.arange(sc["track_start"][t], sc["track_start"][t + 1]) for t in perm]).astype(np.int64)
+    sp = dict(sc, track_start=np.concatenate([[0], np.cumsum(n[perm])]).astype(np.uint64), obs_pose=sc["obs_pose"][order],
+              obs_intr=sc["obs_intr"][order], obs_xy=sc["obs_xy"][order])
+    Xp, okp, inlp, _ = cases.run_device(sp)
+    assert np.array_equal(Xp, X[perm]) and np.array_equal(okp, ok[perm]) and np.array_equal(inlp, inl[order])
+
+
+def test_argument_errors():
+    sc = ref.scene(8, [4, 5], seed=1)
+    lib = _capi.lib()
+
+    def call(sc, **kw):
+        try:
+            cases.run_device(sc, **kw)
+        except _capi.MvgxError as e:
+            return e.code
+        return _capi.MVGX_OK
+
+    assert call(sc) == _capi.MVGX_OK
+    assert call(dict(sc, obs_pose=np.full(9, 8, np.uint32))) == _capi.MVGX_ERR_ARG
+    assert call(dict(sc, obs_intr=np.full(9, 1, np.uint32))) == _capi.MVGX_ERR_ARG
+    assert call(dict(sc, track_start=np.array([0, 5, 4], np.uint64))) == _capi.MVGX_ERR_ARG
+    assert call(sc, min_sample_index=4, min_required_inliers=4) == _capi.MVGX_ERR_UNSUPPORTED
+    assert call(sc, mode=7) == _capi.MVGX_ERR_ARG
+    assert call(sc, method=4) == _capi.MVGX_ERR_ARG
+    assert call(dict(sc, intr_model=np.array([6], np.int32))) == _capi.MVGX_ERR_UNSUPPORTED
+    o = triangulation.default_options()
+    assert (o.mode, o.method, o.max_reprojection_error, o.min_required_inliers, o.min_sample_index) == (_capi.MVGX_TRI_ROBUST, 3, 4.0, 3, 3)
+    assert lib.mvgx_abi_version() == 12
+
+
+def test_scene_helper_feeds_bundle_adjustment_arrays():
+    """triangulate_scene drops rejected tracks and non-inlier observations and renumbers: the arrays are those of a BA scene"""
+    t = ref.scene(8, [2, 6, 6, 7, 1], seed=12)
+    n = np.diff(t["track_start"].astype(np.int64))
+    scene = dict(poses=t["poses"], intrinsics=t["intrinsics"], intr_model=t["intr_model"], points=np.zeros((5, 3)), obs_pose=t["obs_pose"],
+                 obs_intr=t["obs_intr"], obs_point=np.repeat(np.arange(5, dtype=np.uint32), n), obs_xy=t["obs_xy"], n_poses=8, n_intrinsics=1,
+                 n_points=5, n_obs=len(t["obs_pose"]))
+    by_view = np.argsort(scene["obs_pose"], kind="stable")   # the helper groups the observations by point itself, keeping the order inside a track
+    shuffled = dict(scene, **{k: np.ascontiguousarray(scene[k][by_view]) for k in ("obs_pose", "obs_intr", "obs_point", "obs_xy")})
+    out, ok, stats = triangulation.triangulate_scene(scene)
+    assert list(ok) == [False, True, True, True, False]   # robust (3, 3): tracks of 2 and 1 observations are rejected
+    assert out["n_points"] == 3 and out["points"].shape == (3, 3) and out["n_obs"] == len(out["obs_pose"]) == stats.n_inlier_obs
+    assert out["obs_point"].max() == 2 and np.abs(out["points"] - t["points"][1:4]).max() < 0.05
+    out2, ok2, _ = triangulation.triangulate_scene(shuffled)
+    assert np.array_equal(ok2, ok) and out2["n_obs"] == out["n_obs"]
