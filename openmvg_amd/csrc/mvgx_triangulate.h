@@ -17,8 +17,9 @@
 // Exact: the sample sequence (a fresh std::mt19937(default_seed) per track, :371, so the samples of a track depend on (min_sample_index, n)
 // alone: a host-built table per (k, n), no generator on the device), the order of every sum over observations, every decision rule.
 // To rounding: the points (the eigenvector of AtA comes from a cyclic Jacobi iteration instead of Eigen's tridiagonal QL; the DLT's null
-// vector from the same iteration on D^T D instead of a JacobiSVD of D; fused multiply-adds), R | t = the BA kernels' rotation terms
-// instead of Pose3's matrix, pose(X) = R X + t instead of R (X - C).
+// vector from a one-sided (Hestenes) Jacobi iteration on the columns of D instead of a two-sided JacobiSVD of D - never from D^T D, whose
+// error grows with the SQUARED condition number of D; fused multiply-adds), R | t = the BA kernels' rotation terms instead of Pose3's
+// matrix, pose(X) = R X + t instead of R (X - C).
 #pragma once
 
 #include <map>
@@ -146,10 +147,64 @@ __device__ __forceinline__ bool tri_point_from_rays(const double m0[3], const do
   tri_to_world(Rt1, xp, X);
   return l0 > 0.0 && l1 > 0.0;
 }
-// TriangulateDLT (triangulation.cpp:16-70) in two halves around the eigen-solver, so that a kernel holds ONE copy of that solver for the
-// DLT and the N-view form: the point is the right singular vector of the smallest singular value of the 4 x 4 design matrix D, i.e. the
-// eigenvector of D^T D. One view's rows x[0] P.row(2) - x[2] P.row(0) and x[1] P.row(2) - x[2] P.row(1) (:29-32):
-__device__ __forceinline__ void tri_dlt_add(const double* Rt, const double x[3], double a[10]) {
+// TriangulateDLT (triangulation.cpp:16-70): the point is the right singular vector of the smallest singular value of the 4 x 4 design
+// matrix D, rows x[0] P.row(2) - x[2] P.row(0) and x[1] P.row(2) - x[2] P.row(1) per view (:29-32). One-sided (Hestenes) Jacobi: plane
+// rotations from the right make the columns of D orthogonal, V collects them, D V = U S; the column of the smallest norm names the null
+// vector. Its error grows with the condition number of D (as that of the reference's JacobiSVD), not with its square (as that of an
+// eigenvector of D^T D: three orders worse at half a degree of parallax). Every entry a named scalar, as in tri_smallest_eigenvector.
+__device__ __forceinline__ void tri_dlt_row(const double* Rt, double xa, double xc, int r, double& d0, double& d1, double& d2, double& d3) {
+  d0 = xa * Rt[6] - xc * Rt[3 * r]; d1 = xa * Rt[7] - xc * Rt[3 * r + 1]; d2 = xa * Rt[8] - xc * Rt[3 * r + 2]; d3 = xa * Rt[11] - xc * Rt[9 + r];
+}
+// columns p and q of D (four rows each) and of V; returns whether it rotated
+__device__ __forceinline__ bool tri_hestenes_rot(double& d0p, double& d0q, double& d1p, double& d1q, double& d2p, double& d2q, double& d3p, double& d3q,
+                                                 double& v0p, double& v0q, double& v1p, double& v1q, double& v2p, double& v2q, double& v3p, double& v3q) {
+  const double app = d0p * d0p + d1p * d1p + d2p * d2p + d3p * d3p, aqq = d0q * d0q + d1q * d1q + d2q * d2q + d3q * d3q;
+  const double apq = d0p * d0q + d1p * d1q + d2p * d2q + d3p * d3q;
+  if (fabs(apq) <= 2.220446049250313e-16 * sqrt(app * aqq)) return false;   // orthogonal at this precision (a zero column included)
+  const double th = (aqq - app) / (2.0 * apq);
+  const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));   // th^2 = inf -> t = 0
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  double x, y;
+  x = d0p; y = d0q; d0p = c * x - s * y; d0q = s * x + c * y;
+  x = d1p; y = d1q; d1p = c * x - s * y; d1q = s * x + c * y;
+  x = d2p; y = d2q; d2p = c * x - s * y; d2q = s * x + c * y;
+  x = d3p; y = d3q; d3p = c * x - s * y; d3q = s * x + c * y;
+  x = v0p; y = v0q; v0p = c * x - s * y; v0q = s * x + c * y;
+  x = v1p; y = v1q; v1p = c * x - s * y; v1q = s * x + c * y;
+  x = v2p; y = v2q; v2p = c * x - s * y; v2q = s * x + c * y;
+  x = v3p; y = v3q; v3p = c * x - s * y; v3q = s * x + c * y;
+  return true;
+}
+__device__ __forceinline__ void tri_dlt_point(const double* Rt0, const double x0[3], const double* Rt1, const double x1[3], double X[3]) {
+  double d00, d01, d02, d03, d10, d11, d12, d13, d20, d21, d22, d23, d30, d31, d32, d33;   // d_rc: row r, column c
+  tri_dlt_row(Rt0, x0[0], x0[2], 0, d00, d01, d02, d03);
+  tri_dlt_row(Rt0, x0[1], x0[2], 1, d10, d11, d12, d13);
+  tri_dlt_row(Rt1, x1[0], x1[2], 0, d20, d21, d22, d23);
+  tri_dlt_row(Rt1, x1[1], x1[2], 1, d30, d31, d32, d33);
+  double v00 = 1, v01 = 0, v02 = 0, v03 = 0, v10 = 0, v11 = 1, v12 = 0, v13 = 0, v20 = 0, v21 = 0, v22 = 1, v23 = 0, v30 = 0, v31 = 0, v32 = 0, v33 = 1;
+#pragma unroll 1
+  for (int sweep = 0; sweep < kTriJacobiSweeps; ++sweep) {
+    bool any = tri_hestenes_rot(d00, d01, d10, d11, d20, d21, d30, d31, v00, v01, v10, v11, v20, v21, v30, v31);   // (0, 1)
+    any = tri_hestenes_rot(d00, d02, d10, d12, d20, d22, d30, d32, v00, v02, v10, v12, v20, v22, v30, v32) || any;  // (0, 2)
+    any = tri_hestenes_rot(d00, d03, d10, d13, d20, d23, d30, d33, v00, v03, v10, v13, v20, v23, v30, v33) || any;  // (0, 3)
+    any = tri_hestenes_rot(d01, d02, d11, d12, d21, d22, d31, d32, v01, v02, v11, v12, v21, v22, v31, v32) || any;  // (1, 2)
+    any = tri_hestenes_rot(d01, d03, d11, d13, d21, d23, d31, d33, v01, v03, v11, v13, v21, v23, v31, v33) || any;  // (1, 3)
+    any = tri_hestenes_rot(d02, d03, d12, d13, d22, d23, d32, d33, v02, v03, v12, v13, v22, v23, v32, v33) || any;  // (2, 3)
+    if (!any) break;
+  }
+  // the column of the smallest norm (the first among equals), picked pairwise as in tri_smallest_eigenvector
+  const double n0 = d00 * d00 + d10 * d10 + d20 * d20 + d30 * d30, n1 = d01 * d01 + d11 * d11 + d21 * d21 + d31 * d31;
+  const double n2 = d02 * d02 + d12 * d12 + d22 * d22 + d32 * d32, n3 = d03 * d03 + d13 * d13 + d23 * d23 + d33 * d33;
+  const bool lo1 = n1 < n0, hi1 = n3 < n2;
+  const double elo = lo1 ? n1 : n0, ehi = hi1 ? n3 : n2;
+  const double l0 = lo1 ? v01 : v00, l1 = lo1 ? v11 : v10, l2 = lo1 ? v21 : v20, l3 = lo1 ? v31 : v30;
+  const double h0 = hi1 ? v03 : v02, h1 = hi1 ? v13 : v12, h2 = hi1 ? v23 : v22, h3 = hi1 ? v33 : v32;
+  const bool hi = ehi < elo;
+  const double x3 = hi ? h3 : l3;
+  X[0] = (hi ? h0 : l0) / x3; X[1] = (hi ? h1 : l1) / x3; X[2] = (hi ? h2 : l2) / x3;
+}
+// D^T D += the two rows of one view (the form the DLT had before the one-sided iteration; see tri_robust_kernel for why it is still here)
+__device__ __forceinline__ void tri_dtd_add(const double* Rt, const double x[3], double a[10]) {
   tri_add_row(x[0] * Rt[6] - x[2] * Rt[0], x[0] * Rt[7] - x[2] * Rt[1], x[0] * Rt[8] - x[2] * Rt[2], x[0] * Rt[11] - x[2] * Rt[9], a);
   tri_add_row(x[1] * Rt[6] - x[2] * Rt[3], x[1] * Rt[7] - x[2] * Rt[4], x[1] * Rt[8] - x[2] * Rt[5], x[1] * Rt[11] - x[2] * Rt[10], a);
 }
@@ -311,6 +366,8 @@ __global__ __launch_bounds__(256) void tri_bearing_kernel(TriDev d, double* __re
 // robust == 0: SfM_Data_Structure_Computation_Blind::triangulate (:193-206; the default method, cheirality of every observation).
 // robust == 1: the all-observations case of robust_triangulation (:344-357; the caller's method, cheirality and residual).
 // perm lists the tracks in order of length, so the lanes of a wave run similar trip counts.
+// kDlt: the caller's method is the DLT (robust only): the form with the one-sided Jacobi, kept out of the code the other methods run.
+template <bool kDlt>
 __global__ __launch_bounds__(256) void tri_track_kernel(TriDev d, const uint32_t* __restrict__ perm, uint32_t count, int robust) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
@@ -321,23 +378,27 @@ __global__ __launch_bounds__(256) void tri_track_kernel(TriDev d, const uint32_t
   for (uint32_t j = 0; j < n && ok; ++j) ok = tri_obs_model<false>(d, nullptr, o0 + j, j) >= 0;   // :63-64
   double X[3] = {0.0, 0.0, 0.0};
   if (ok) {
-    const int method = robust ? d.method : 3;
-    if (n == 2 && method != 0) {
+    const int method = robust ? d.method : 3;   // (kDlt: not read)
+    if (n == 2) {
       double b0[3], b1[3];
       tri_obs_bearing<false>(d, nullptr, o0, 0, 0, b0);
       tri_obs_bearing<false>(d, nullptr, o0 + 1, 1, 0, b1);
-      ok = tri_two_view_closed(method, tri_obs_Rt<false>(d, nullptr, o0, 0), b0, tri_obs_Rt<false>(d, nullptr, o0 + 1, 1), b1, X);
+      const double *Rt0 = tri_obs_Rt<false>(d, nullptr, o0, 0), *Rt1 = tri_obs_Rt<false>(d, nullptr, o0 + 1, 1);
+      if constexpr (kDlt) {
+        tri_dlt_point(Rt0, b0, Rt1, b1, X);
+        ok = tri_dlt_in_front(Rt0, Rt1, X);
+      } else {
+        ok = tri_two_view_closed(method, Rt0, b0, Rt1, b1, X);
+      }
     } else {
       double a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 1
       for (uint32_t j = 0; j < n; ++j) {
         double b[3];
         tri_obs_bearing<false>(d, nullptr, o0 + j, j, 0, b);
-        if (n == 2) tri_dlt_add(tri_obs_Rt<false>(d, nullptr, o0 + j, j), b, a);
-        else tri_nview_add(tri_obs_Rt<false>(d, nullptr, o0 + j, j), b, a);
+        tri_nview_add(tri_obs_Rt<false>(d, nullptr, o0 + j, j), b, a);
       }
       tri_smallest_eigenvector(a, X);
-      if (n == 2) ok = tri_dlt_in_front(tri_obs_Rt<false>(d, nullptr, o0, 0), tri_obs_Rt<false>(d, nullptr, o0 + 1, 1), X);
     }
   }
 #pragma unroll 1
@@ -358,7 +419,9 @@ __global__ __launch_bounds__(256) void tri_track_kernel(TriDev d, const uint32_t
 // reference's `current_error < best_error` would have ended with. G = 16: four tracks of at most 8 observations per wave; G = 64: one.
 // kLds: the track's records are staged in LDS once (tracks up to kTriLdsObs observations; above, every lane reads the scene arrays).
 // Tracks up to 64 observations carry their inlier set as a mask; longer ones are scored once more with the winning point.
-template <int G, bool kLds>
+// kDlt: two-view samples by the DLT (min_sample_index == 2, method 0) - a form of its own, so that the one-sided Jacobi costs the forms of
+// the other methods no register; a kernel holds ONE of the two iterations.
+template <int G, bool kLds, bool kDlt>
 __global__ __launch_bounds__(64) void tri_robust_kernel(TriDev d, const uint32_t* __restrict__ perm, uint32_t count) {
   constexpr int kGroups = 64 / G;
   constexpr int kCap = G == 16 ? kTriSmallObs : kTriLdsObs;
@@ -402,13 +465,17 @@ __global__ __launch_bounds__(64) void tri_robust_kernel(TriDev d, const uint32_t
       tri_obs_bearing<kLds>(d, rec, o0 + s0, s0, 0, b0);
       tri_obs_bearing<kLds>(d, rec, o0 + s1, s1, 0, b1);
       const double *Rt0 = tri_obs_Rt<kLds>(d, rec, o0 + s0, s0), *Rt1 = tri_obs_Rt<kLds>(d, rec, o0 + s1, s1);
-      if (k == 2 && d.method != 0) {
+      if constexpr (kDlt) {
+        tri_dlt_point(Rt0, b0, Rt1, b1, X);
+        if (!tri_dlt_in_front(Rt0, Rt1, X)) continue;
+      } else if (k == 2 && d.method != 0) {
         if (!tri_two_view_closed(d.method, Rt0, b0, Rt1, b1, X)) continue;
       } else {
         double a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (k == 2) {
-          tri_dlt_add(Rt0, b0, a);
-          tri_dlt_add(Rt1, b1, a);
+        if (k == 2) {   // (never taken: the host launches the kDlt form for two-view samples by the DLT. The branch is what this form had
+                        // when it served the DLT too, through D^T D; with it the form compiles to the code it had - measured, not argued)
+          tri_dtd_add(Rt0, b0, a);
+          tri_dtd_add(Rt1, b1, a);
         } else {
           double b2[3];
           tri_obs_bearing<kLds>(d, rec, o0 + s2, s2, 0, b2);
@@ -694,24 +761,30 @@ int mvgx_triangulate_tracks(int device, const double* poses, uint32_t n_poses, c
   const auto blocks = [](uint32_t count, uint32_t per_block) { return dim3((count + per_block - 1) / per_block); };
   const uint32_t n_all = (uint32_t)pl.all.size(), n_whole = (uint32_t)pl.whole.size(), n_small = (uint32_t)pl.small.size();
   const uint32_t n_wave = (uint32_t)pl.wave.size(), n_global = (uint32_t)pl.global.size();
+  // the DLT forms: only where a two-view solve by the caller's method 0 can happen (the robust lists are empty in blind mode)
+  const bool dlt_whole = opt->method == 0, dlt_samples = opt->method == 0 && opt->min_sample_index == 2;
   if (n_all) {
-    hipLaunchKernelGGL(tri_track_kernel, blocks(n_all, 256), dim3(256), 0, stream, d, lists + at_all, n_all, 0);
+    hipLaunchKernelGGL(tri_track_kernel<false>, blocks(n_all, 256), dim3(256), 0, stream, d, lists + at_all, n_all, 0);
     BA_LAUNCH_CHECK();
   }
   if (n_whole) {
-    hipLaunchKernelGGL(tri_track_kernel, blocks(n_whole, 256), dim3(256), 0, stream, d, lists + at_whole, n_whole, 1);
+    if (dlt_whole) hipLaunchKernelGGL(tri_track_kernel<true>, blocks(n_whole, 256), dim3(256), 0, stream, d, lists + at_whole, n_whole, 1);
+    else hipLaunchKernelGGL(tri_track_kernel<false>, blocks(n_whole, 256), dim3(256), 0, stream, d, lists + at_whole, n_whole, 1);
     BA_LAUNCH_CHECK();
   }
   if (n_small) {
-    hipLaunchKernelGGL((tri_robust_kernel<16, true>), blocks(n_small, 4), dim3(64), 0, stream, d, lists + at_small, n_small);
+    if (dlt_samples) hipLaunchKernelGGL((tri_robust_kernel<16, true, true>), blocks(n_small, 4), dim3(64), 0, stream, d, lists + at_small, n_small);
+    else hipLaunchKernelGGL((tri_robust_kernel<16, true, false>), blocks(n_small, 4), dim3(64), 0, stream, d, lists + at_small, n_small);
     BA_LAUNCH_CHECK();
   }
   if (n_wave) {
-    hipLaunchKernelGGL((tri_robust_kernel<64, true>), blocks(n_wave, 1), dim3(64), 0, stream, d, lists + at_wave, n_wave);
+    if (dlt_samples) hipLaunchKernelGGL((tri_robust_kernel<64, true, true>), blocks(n_wave, 1), dim3(64), 0, stream, d, lists + at_wave, n_wave);
+    else hipLaunchKernelGGL((tri_robust_kernel<64, true, false>), blocks(n_wave, 1), dim3(64), 0, stream, d, lists + at_wave, n_wave);
     BA_LAUNCH_CHECK();
   }
   if (n_global) {
-    hipLaunchKernelGGL((tri_robust_kernel<64, false>), blocks(n_global, 1), dim3(64), 0, stream, d, lists + at_global, n_global);
+    if (dlt_samples) hipLaunchKernelGGL((tri_robust_kernel<64, false, true>), blocks(n_global, 1), dim3(64), 0, stream, d, lists + at_global, n_global);
+    else hipLaunchKernelGGL((tri_robust_kernel<64, false, false>), blocks(n_global, 1), dim3(64), 0, stream, d, lists + at_global, n_global);
     BA_LAUNCH_CHECK();
   }
   MVGX_HIP(hipEventRecord(e1, stream));

@@ -6,8 +6,9 @@ What is restated (paths under src/openMVG of the reference):
   multiview/triangulation_nview.cpp:39-61                                TriangulateNViewAlgebraic (numpy.linalg.eigh)
   robust_estimation/rand_sampling.hpp:36-58                              UniformSample on std::mt19937(5489) with libstdc++ 11's bounded draw
   cameras/Camera_Intrinsics.hpp:293-301                                  CheiralityTest
-Scalars are Python floats (IEEE double, one rounding per operation, sums in the reference's order); the 4 x 4 eigen / singular vectors
-come from LAPACK. The camera parts (bearing with and without undistortion, residual) restate openmvg_amd/csrc/ba_math.h and are pinned
+Scalars are Python floats (IEEE double, one rounding per operation, sums in the reference's order); the 4 x 4 eigenvectors come from
+LAPACK, the DLT's null vector from a two-sided Jacobi iteration as in Eigen::JacobiSVD (LAPACK's SVD is up to three orders MORE accurate
+than the reference on scenes away from the origin - no restatement of it there; tests/test_triangulation_ref_cpu.py). The camera parts (bearing with and without undistortion, residual) restate openmvg_amd/csrc/ba_math.h and are pinned
 to the oracle's port_ba_eval_obs / port_ba_track_angles by tests/test_triangulation_ref_cpu.py.
 """
 import functools
@@ -188,13 +189,61 @@ def _point_from_rays(m0, m1, t, R1, t1):
     return (l0 > 0.0 and l1 > 0.0), _to_world(R1, t1, xp)
 
 
+def two_sided_jacobi_null_vector(D):
+    """The right singular vector of the smallest singular value of a square matrix by the two-sided Jacobi iteration, the method of the
+    reference's Eigen::JacobiSVD (TriangulateDLT, triangulation.cpp:34): the matrix is scaled by its largest entry; sweeps over the
+    pairs (p, q < p); a pair is rotated while an off-diagonal entry of its 2 x 2 block exceeds 2 epsilon x the largest diagonal entry
+    met so far - a bound relative to the LARGEST singular value, which is where the small singular vector of a badly scaled D (a
+    translation column of 1e3 .. 1e5 beside a rotation block of order 1) loses what LAPACK's SVD keeps; a block is made symmetric by
+    a rotation from the left, then diagonal by a Jacobi rotation from both sides; V collects the rotations from the right."""
+    W = np.array(D, np.float64)
+    n = len(W)
+    scale = float(np.abs(W).max())
+    W = W / (scale if scale > 0.0 and math.isfinite(scale) else 1.0)
+    V = np.eye(n)
+    tiny, precision = 2.2250738585072014e-308, 2.0 * 2.220446049250313e-16
+    largest = float(np.abs(np.diag(W)).max())
+    rotated, sweeps = bool(np.isfinite(W).all()), 0
+    while rotated and sweeps < 64:   # (it converges quadratically: a handful of sweeps; the bound only keeps a NaN from looping)
+        rotated, sweeps = False, sweeps + 1
+        for p in range(1, n):
+            for q in range(p):
+                threshold = max(tiny, precision * largest)
+                if not (abs(W[p, q]) > threshold or abs(W[q, p]) > threshold):
+                    continue
+                rotated = True
+                a, b, c, d = W[p, p], W[p, q], W[q, p], W[q, q]
+                # G = [[cg, sg], [-sg, cg]] from the left makes the block symmetric
+                cg, sg = 1.0, 0.0
+                if abs(c - b) >= tiny:
+                    u = (a + d) / (c - b)
+                    h = math.sqrt(1.0 + u * u)
+                    cg, sg = u / h, 1.0 / h
+                x, y, z = cg * a + sg * c, cg * b + sg * d, -sg * b + cg * d
+                # J = [[cj, sj], [-sj, cj]]: J^T S J is diagonal
+                cj, sj = 1.0, 0.0
+                if 2.0 * abs(y) >= tiny:
+                    tau = (z - x) / (2.0 * y)
+                    t = (1.0 if tau >= 0.0 else -1.0) / (abs(tau) + math.sqrt(tau * tau + 1.0))
+                    cj = 1.0 / math.sqrt(t * t + 1.0)
+                    sj = t * cj
+                cl, sl = cj * cg + sj * sg, cj * sg - sj * cg   # J^T G = [[cl, sl], [-sl, cl]]
+                rp, rq = W[p].copy(), W[q].copy()
+                W[p], W[q] = cl * rp + sl * rq, -sl * rp + cl * rq
+                for M in (W, V):
+                    cp, cq = M[:, p].copy(), M[:, q].copy()
+                    M[:, p], M[:, q] = cj * cp - sj * cq, sj * cp + cj * cq
+                largest = max(largest, abs(W[p, p]), abs(W[q, q]))
+    return V[:, int(np.argmin(np.abs(np.diag(W))))]
+
+
 def two_view(method, R0, t0, x0, R1, t1, x1):
     """Triangulate2View -> (ok, X)"""
     if method == DLT:
         P0 = np.hstack([np.asarray(R0), np.asarray(t0)[:, None]])
         P1 = np.hstack([np.asarray(R1), np.asarray(t1)[:, None]])
         D = np.stack([x0[0] * P0[2] - x0[2] * P0[0], x0[1] * P0[2] - x0[2] * P0[1], x1[0] * P1[2] - x1[2] * P1[0], x1[1] * P1[2] - x1[2] * P1[1]])
-        X = _hnormalized(np.linalg.svd(D)[2][3])
+        X = _hnormalized(two_sided_jacobi_null_vector(D))
         return (to_camera(R0, t0, X)[2] > 0.0 and to_camera(R1, t1, X)[2] > 0.0), X
     R = [[sum(R1[i][k] * R0[j][k] for k in range(3)) for j in range(3)] for i in range(3)]
     t = tuple(t1[i] - (R[i][0] * t0[0] + R[i][1] * t0[1] + R[i][2] * t0[2]) for i in range(3))
@@ -447,13 +496,26 @@ def model_intrinsics(model, rng):
     return row
 
 
-def scene(n_cams, track_lens, model=PINHOLE, seed=0, noise=0.5, displaced=True, n_displaced=None):
+def mixed_intrinsics(n_cams, seed):
+    """eight intrinsic rows - one per camera model, and two more pinhole rows of other focal lengths and principal points - and the row
+    of every pose (pose i has row i mod 8): the views of a track then differ in model and in intrinsic row"""
+    rng = np.random.default_rng([seed, 8])
+    rows = [model_intrinsics(m, rng) for m in MODELS] + [np.array([800.0, 480.0, 520.0, 0, 0, 0, 0, 0]), np.array([1300.0, 510.0, 490.0, 0, 0, 0, 0, 0])]
+    return np.stack(rows), np.array(list(MODELS) + [PINHOLE, PINHOLE], np.int32), (np.arange(n_cams) % 8).astype(np.uint32)
+
+
+def scene(n_cams, track_lens, model=PINHOLE, seed=0, noise=0.5, displaced=True, n_displaced=None, mixed=False):
     """dict of the arrays mvgx_triangulate_tracks takes (+ "points": the true positions). Points uniform in [-1, 1]^3, pixel noise sigma
-    `noise`; in a track of five or more observations at most one (exactly n_displaced if given) is displaced by +-[50, 300] px per axis."""
+    `noise`; in a track of five or more observations at most one (exactly n_displaced if given) is displaced by +-[50, 300] px per axis.
+    mixed: the cameras of mixed_intrinsics instead of one intrinsic row of `model` (drawn from a generator of their own: the scene's
+    stream of random numbers is the same with and without)."""
     from openmvg_amd import synth
     rng = np.random.default_rng(seed)
     poses = ring_cameras(n_cams, rng)
     intr = model_intrinsics(model, rng)[None]
+    models, intr_of_pose = np.array([model], np.int32), np.zeros(n_cams, np.uint32)
+    if mixed:
+        intr, models, intr_of_pose = mixed_intrinsics(n_cams, seed)
     pts = rng.uniform(-1, 1, (len(track_lens), 3))
     obs_pose, obs_pt = [], []
     for t, n in enumerate(track_lens):
@@ -464,7 +526,12 @@ def scene(n_cams, track_lens, model=PINHOLE, seed=0, noise=0.5, displaced=True, 
             cams = np.sort(np.concatenate([np.arange(n_cams), rng.choice(n_cams, size=n - n_cams, replace=False)]))
         obs_pose += list(cams); obs_pt += [t] * int(n)
     obs_pose, obs_pt = np.array(obs_pose, np.uint32), np.array(obs_pt, np.int64)
-    xy = synth.project(model, np.repeat(intr, len(obs_pose), 0), poses[obs_pose], pts[obs_pt]) + noise * rng.standard_normal((len(obs_pose), 2))
+    obs_intr = intr_of_pose[obs_pose]
+    xy = np.zeros((len(obs_pose), 2))
+    for m in sorted(set(int(v) for v in models)):
+        sel = models[obs_intr] == m
+        xy[sel] = synth.project(m, intr[obs_intr[sel]], poses[obs_pose[sel]], pts[obs_pt[sel]])
+    xy = xy + noise * rng.standard_normal((len(obs_pose), 2))
     start = np.concatenate([[0], np.cumsum(track_lens)]).astype(np.uint64)
     moved = np.zeros(len(obs_pose), bool)
     for t, n in enumerate(track_lens):
@@ -474,8 +541,8 @@ def scene(n_cams, track_lens, model=PINHOLE, seed=0, noise=0.5, displaced=True, 
         for j in rng.choice(int(n), size=m, replace=False):
             xy[int(start[t]) + int(j)] += rng.choice([-1.0, 1.0], 2) * rng.uniform(50, 300, 2)
             moved[int(start[t]) + int(j)] = True
-    return dict(poses=poses, intrinsics=intr, intr_model=np.array([model], np.int32), track_start=start, obs_pose=obs_pose,
-                obs_intr=np.zeros(len(obs_pose), np.uint32), obs_xy=xy, points=pts, displaced=moved)
+    return dict(poses=poses, intrinsics=intr, intr_model=models, track_start=start, obs_pose=obs_pose,
+                obs_intr=obs_intr.astype(np.uint32), obs_xy=xy, points=pts, displaced=moved)
 
 
 ARGS = ("poses", "intrinsics", "intr_model", "track_start", "obs_pose", "obs_intr", "obs_xy")

@@ -4,14 +4,13 @@ tests/_triangulation_cases.py. The -m gpu twin of this file is tests/test_triang
 import numpy as np
 import pytest
 
-from openmvg_amd import _capi, synth, triangulation
+from openmvg_amd import _capi, triangulation
 from tests import _emu
 from tests import _triangulation_cases as cases
 from tests import _triangulation_ref as ref
 
-ROBUST_FORMS = [(2, 2), (3, 2), (3, 3)]   # (min_required_inliers, min_sample_index) of the reference's callers
-# group boundaries of the robust kernel: 16-lane groups up to 8 observations, LDS records and the inlier mask up to 64, rounds of 64 hypotheses above 32
-BOUNDARY_LENGTHS = [2, 3, 8, 9, 32, 33, 63, 64, 65]
+ROBUST_FORMS = cases.ROBUST_FORMS
+BOUNDARY_LENGTHS = cases.BOUNDARY_LENGTHS
 
 
 @pytest.fixture(autouse=True)
@@ -22,28 +21,10 @@ def _emulated():
 
 def _with_undefined(sc, tracks, seed=5):
     """one observation of each named track becomes a view without pose or intrinsic; its indices are made unusable on purpose"""
-    sc = dict(sc)
-    rng = np.random.default_rng(seed)
-    sc["obs_defined"] = np.ones(len(sc["obs_pose"]), np.uint8)
-    sc["obs_pose"] = sc["obs_pose"].copy(); sc["obs_intr"] = sc["obs_intr"].copy()
-    for t in tracks:
-        lo, hi = int(sc["track_start"][t]), int(sc["track_start"][t + 1])
-        o = int(rng.integers(lo, hi))
-        sc["obs_defined"][o] = 0
-        sc["obs_pose"][o] = 0xFFFFFFFF; sc["obs_intr"][o] = 0xFFFFFFFF
-    return sc
+    return cases.with_undefined(sc, tracks, seed=seed, poison=False)
 
 
-def _behind_track(model):
-    """three adjacent cameras of the ring and a point BEHIND them (off the middle camera's axis): the lines meet there, the rays of a
-    perspective camera do not. A spherical camera sees it like any other point."""
-    sc = ref.scene(8, [3], model=model, seed=77, noise=0.0)
-    sc["obs_pose"] = np.array([0, 1, 2], np.uint32)
-    R = synth._rodrigues(sc["poses"][1, :3])[0]
-    centre = -R.T @ sc["poses"][1, 3:6]
-    sc["points"] = (1.5 * centre + (0.3, 0.2, 0.1))[None]
-    sc["obs_xy"] = synth.project(model, np.repeat(sc["intrinsics"], 3, 0), sc["poses"][:3], np.repeat(sc["points"], 3, 0))
-    return sc
+_behind_track = cases.behind_track
 
 
 def test_reference_unit_test_statements():
@@ -174,3 +155,34 @@ def test_scene_helper_feeds_bundle_adjustment_arrays():
     assert out["obs_point"].max() == 2 and np.abs(out["points"] - t["points"][1:4]).max() < 0.05
     out2, ok2, _ = triangulation.triangulate_scene(shuffled)
     assert np.array_equal(ok2, ok) and out2["n_obs"] == out["n_obs"]
+
+
+# ---- form edges (the bodies are in tests/_triangulation_cases.py; the -m gpu twins run the same) ----
+def test_views_without_pose():
+    cases.check_views_without_pose(poison=False)
+
+
+def test_mixed_cameras():
+    cases.check_mixed_cameras()
+
+
+def test_ragged_groups():
+    cases.check_ragged_groups()
+
+
+@pytest.mark.parametrize("need,k", cases.OTHER_FORMS)
+def test_other_caller_forms(need, k):
+    cases.check_other_caller_form(need, k)
+
+
+def test_offset_observation_arrays():
+    cases.check_offset_observation_arrays()
+
+
+def test_degenerate_two_view_input():
+    cases.check_degenerate_pairs()
+
+
+@pytest.mark.parametrize("need,k", [(2, 2), (3, 2)])
+def test_two_view_samples_sharing_a_pose(need, k):
+    cases.check_samples_sharing_a_pose(need, k)

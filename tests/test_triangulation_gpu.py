@@ -71,6 +71,55 @@ def test_repeatable_and_order_independent(built_lib):
     assert ok.sum() >= 400
 
 
+# ---- form edges: the bodies are in tests/_triangulation_cases.py and run under the emulation too. What only real waves decide: shuffles
+# across lanes that left the hypothesis loop early, the one barrier after the LDS staging, the 64-bit inlier mask, the lanes of a 16-lane
+# group without a track. A view without pose names an extra pose row and an extra intrinsic row of NaNs here - every index the device
+# can read is in range, and an unguarded read shows as a wrong decision. ----
+@pytest.mark.parametrize("need,k", cases.ROBUST_FORMS)
+def test_robust_group_boundaries(built_lib, need, k):
+    cases.check_group_boundaries(need, k, poison=True)
+
+
+@pytest.mark.parametrize("model", ref.MODELS)
+def test_blind_rejections(built_lib, model):
+    cases.check_blind_rejections(model, poison=True)
+
+
+@pytest.mark.parametrize("model", ref.MODELS)
+def test_robust_behind_the_camera(built_lib, model):
+    cases.check_robust_behind(model)
+
+
+def test_views_without_pose(built_lib):
+    cases.check_views_without_pose(poison=True)
+
+
+def test_mixed_cameras(built_lib):
+    cases.check_mixed_cameras()
+
+
+def test_ragged_groups(built_lib):
+    cases.check_ragged_groups()
+
+
+@pytest.mark.parametrize("need,k", cases.OTHER_FORMS)
+def test_other_caller_forms(built_lib, need, k):
+    cases.check_other_caller_form(need, k)
+
+
+def test_offset_observation_arrays(built_lib):
+    cases.check_offset_observation_arrays()
+
+
+def test_degenerate_two_view_input(built_lib):
+    cases.check_degenerate_pairs()
+
+
+@pytest.mark.parametrize("need,k", [(2, 2), (3, 2)])
+def test_two_view_samples_sharing_a_pose(built_lib, need, k):
+    cases.check_samples_sharing_a_pose(need, k)
+
+
 def test_output_feeds_bundle_adjustment(built_lib):
     """tracks + true poses -> triangulate_scene -> ba.BaContext: the solve starts from a finite cost near the noise level"""
     scene = synth.ba_scene(16, 400, track_len=5, seed=5)

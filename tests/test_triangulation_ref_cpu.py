@@ -94,23 +94,59 @@ def _camera_pairs(n_pairs, seed=2024):
     return out[:n_pairs]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libref_geofilter.so (the compiled reference) is not built")
-def test_two_view_solvers_match_the_compiled_reference():
-    """All four methods on 2 000 camera pairs: equal decisions; the largest |dX| per method is printed (recorded in DESIGN.md)."""
+def compiled_two_view():
+    """openMVG::Triangulate2View of the compiled reference as f(method, R0, t0, b0, R1, t1, b1) -> (ok, X)"""
     fn = getattr(C.CDLL(REF_SO), TRIANGULATE2VIEW)
     fn.restype = C.c_bool
     fn.argtypes = [C.c_void_p] * 7 + [C.c_ubyte]
     col = lambda R: np.ascontiguousarray(np.asarray(R, np.float64).T).reshape(-1)   # Mat3: 9 doubles, column-major
     vec = lambda v: np.ascontiguousarray(v, np.float64)
+
+    def call(method, R0, t0, b0, R1, t1, b1):
+        a = [col(R0), vec(t0), vec(b0), col(R1), vec(t1), vec(b1), np.zeros(3)]
+        ok = bool(fn(*[x.ctypes.data for x in a], method))
+        return ok, a[6]
+    return call
+
+
+needs_compiled_reference = pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libref_geofilter.so (the compiled reference) is not built")
+
+
+@needs_compiled_reference
+def test_two_view_solvers_match_the_compiled_reference():
+    """All four methods on 2 000 camera pairs: equal decisions; the largest |dX| per method is printed (recorded in DESIGN.md)."""
+    fn = compiled_two_view()
     pairs = _camera_pairs(2000)
     for method in (ref.DLT, ref.L1_ANGULAR, ref.LINF_ANGULAR, ref.IDW_MIDPOINT):
         worst, mismatches = 0.0, 0
         for (R0, t0, b0), (R1, t1, b1) in pairs:
-            a = [col(R0), vec(t0), vec(b0), col(R1), vec(t1), vec(b1), np.zeros(3)]
-            want_ok = bool(fn(*[x.ctypes.data for x in a], method))
+            want_ok, want_X = fn(method, R0, t0, b0, R1, t1, b1)
             ok, X = ref.two_view(method, R0, t0, b0, R1, t1, b1)
             mismatches += ok != want_ok
-            worst = max(worst, float(np.abs(np.asarray(X) - a[6]).max()))
+            worst = max(worst, float(np.abs(np.asarray(X) - want_X).max()))
         print(f"method {method}: largest |dX| restatement vs compiled reference {worst:.3g}, decision mismatches {mismatches}")
         assert mismatches == 0
         assert worst < 1e-12   # coordinates of order 1: the two are the same formulas, a few ulp apart (see DESIGN.md for the figures)
+
+
+@needs_compiled_reference
+@pytest.mark.parametrize("family", range(5))
+def test_two_view_solvers_against_50_digits(family):
+    """The compiled Triangulate2View on the two-view families of tests/golden/triangulation_truth.npz (scenes away from the origin, small
+    parallax) against the 50-digit points: its error within 10 x the restatement's and the restatement's within 10 x its own - the two are
+    one yardstick on the hard geometry too, where they are no longer equal to 1e-12."""
+    from tests import _triangulation_accuracy_cases as acc
+    from tests import _triangulation_truth as truth
+    gen, fx, fn = acc.generator(), acc.fixture(), compiled_two_view()
+    key = f"f{family}_v2_"
+    for solver in gen.SOLVERS_OF[2]:
+        got = []
+        for poses, xy in zip(fx[key + "poses"], fx[key + "xy"]):
+            ok, X = gen.compiled_reference(fn, solver, poses, xy)
+            assert ok
+            got.append(X)
+        hi, lo = fx[key + solver + "_hi"], fx[key + solver + "_lo"]
+        e_compiled = float(truth.error(np.array(got), hi, lo).max())
+        e_ref = float(truth.error(fx[key + solver + "_ref"], hi, lo).max())
+        print(f"family {tuple(fx['families'][family])} {solver}: compiled reference vs 50 digits {e_compiled:.3g}, restatement {e_ref:.3g}")
+        assert e_compiled <= 10.0 * e_ref and e_ref <= 10.0 * e_compiled
