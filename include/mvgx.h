@@ -641,6 +641,45 @@ int mvgx_triangulate_tracks(int device,
     uint8_t* obs_inlier /* n_obs: blind = every observation of a kept track, robust = the inlier set */,
     mvgx_triangulate_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Robust camera resection (no ABI bump: detect it by the symbol): the step that starts every round of the sequential pipeline -
+ *   sfm/pipelines/localization/SfM_Localizer.cpp:109-343   SfM_Localizer::Localize with error_max = infinity
+ *   robust_estimation/robust_estimator_ACRansac.hpp:257-304, :326-489   the exhaustive NFA and the a-contrario loop
+ *   multiview/solver_resection_p3p_ding.cpp, solver_resection_p3p_nordberg.cpp   the minimal solvers
+ * A batch of independent problems, each run from start to end on the device. Problem p owns the correspondences [start[p], start[p + 1])
+ * of x2d (2 doubles each: pixels with the distortion ALREADY removed, as sequential_SfM.cpp:925-928 passes them) and X3d (3 doubles);
+ * intr_model[p] is a MVGX_CAM_* value and intrinsics + 8 p its row, laid out as in mvgx_ba_problem (spherical: {w, h}). The residual is
+ * the reprojection without distortion (the spherical camera: its own projection) scaled by imagePlane_toCameraPlaneError(1).
+ * Outputs per problem: out_ok = more than 2.5 * 3 inliers; then out_pose + 15 p = R | t (row-major 3 x 4) of KRt_From_P(P) followed by
+ * the centre C = -R^T t, and out_P + 12 p = the winning [R | t] of the solver (row-major). out_error_max: the a-contrario threshold in
+ * pixels (infinity if no model was found), out_min_nfa: the NFA reached. out_inliers: the inlier lists one after the other, the list
+ * of p at [out_inlier_start[p], out_inlier_start[p + 1]), indices within the problem in the reference's order (ascending residual);
+ * room for start[n_problems] - start[0] entries. A problem of three or fewer correspondences: not ok, zeros, nothing else written.
+ * MVGX_ERR_UNSUPPORTED: a solver other than the two P3P ones below, a finite error_max (the quantified NFA with the max-consensus early
+ * exit), an unknown camera model. MVGX_ERR_ARG: NULL arrays, a start that decreases, more than 65 536 correspondences in one problem.
+ * Parity: decisions, sample sequence and inlier order as the reference's, numbers to rounding ("Resection"); a model with a
+ * non-finite entry is skipped. */
+#define MVGX_RESECTION_P3P_NORDBERG 3   /* resection::SolverType::P3P_NORDBERG_ECCV18 */
+#define MVGX_RESECTION_P3P_DING 4       /* resection::SolverType::P3P_DING_CVPR23 (DEFAULT) */
+typedef struct mvgx_resection_options {
+  int32_t solver;           /* resection::SolverType 0..5; 3 and 4 have a device path                                   */
+  uint32_t max_iteration;   /* 4096                                                                                      */
+  double error_max;         /* infinity                                                                                  */
+  uint32_t waves_ahead;     /* test hook: iterations evaluated ahead, 0 = as built, else 1 .. the build's (8)            */
+  uint32_t global_above;    /* test hook: problems above this many correspondences use global scratch, 0 = as built      */
+} mvgx_resection_options;
+typedef struct mvgx_resection_stats {
+  uint64_t n_problems, n_iterations, n_models;   /* a-contrario iterations run, models evaluated (all problems) */
+  double kernel_ms, total_ms;
+} mvgx_resection_stats;
+void mvgx_resection_default_options(mvgx_resection_options*);
+int mvgx_resection_localize(int device, uint32_t n_problems, const uint64_t* start /* n_problems + 1 */, const double* x2d, const double* X3d,
+                            const int32_t* intr_model /* n_problems */, const double* intrinsics /* n_problems x MVGX_BA_MAX_INTR_PARAMS */,
+                            const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose /* n_problems x 15 */,
+                            double* out_P /* n_problems x 12 */, double* out_error_max, double* out_min_nfa,
+                            uint64_t* out_inlier_start /* n_problems + 1 */, uint32_t* out_inliers,
+                            mvgx_resection_stats* stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

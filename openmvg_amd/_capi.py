@@ -146,6 +146,16 @@ class TriangulateStats(C.Structure):
                 ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class ResectionOptions(C.Structure):
+    _fields_ = [("solver", C.c_int32), ("max_iteration", C.c_uint32), ("error_max", C.c_double), ("waves_ahead", C.c_uint32),
+                ("global_above", C.c_uint32)]
+
+
+class ResectionStats(C.Structure):
+    _fields_ = [("n_problems", C.c_uint64), ("n_iterations", C.c_uint64), ("n_models", C.c_uint64), ("kernel_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
 PROTOTYPES = {
     "mvgx_last_error": (C.c_char_p, []),
     "mvgx_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -240,6 +250,10 @@ PROTOTYPES = {
     "mvgx_triangulate_tracks": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(TriangulateStats)]),
+    "mvgx_resection_default_options": (None, [C.POINTER(ResectionOptions)]),
+    "mvgx_resection_localize": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ResectionOptions),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(ResectionStats)]),
 }
 
 _lib = None

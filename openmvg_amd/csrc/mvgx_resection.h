@@ -1,0 +1,981 @@
+// mvgx_resection.h - robust camera resection on the device: AC-RANSAC with the exhaustive NFA over a P3P solver, a batch of independent
+// problems per call (mvgx_resection_localize). Included at the end of mvgx_geofilter.hip: it uses that unit's std::mt19937, bounded draw,
+// logcombi and un-contracted mul_rn / add_rn, and ba_math.h for the camera models. What is restated (paths under src/openMVG of the reference):
+//   sfm/pipelines/localization/SfM_Localizer.cpp:31-343          ACKernelAdaptorResection_Intrinsics, SfM_Localizer::Localize
+//   robust_estimation/robust_estimator_ACRansac.hpp:257-304      the exhaustive NFA of one model
+//   robust_estimation/robust_estimator_ACRansac.hpp:326-489      the a-contrario loop
+//   robust_estimation/rand_sampling.hpp:71-100                   UniformSample on the pool (three Fisher-Yates swaps at its head)
+//   multiview/solver_resection_p3p_ding.cpp:33-325               P3PSolver_Ding
+//   multiview/solver_resection_p3p_nordberg.cpp:31-454           P3PSolver_Nordberg
+//   multiview/projection.cpp:40-132                              KRt_From_P (host)
+// Mapping ("Resection"): one workgroup runs one problem from start to end; each of its kResWaves waves evaluates one
+// iteration of a block of consecutive iterations ahead, under the pool and minNFA the block started with; the verdicts are read in
+// iteration order, the first event is applied and what was drawn after it is drawn again. No workgroup waits for another.
+#pragma once
+#include "ba_math.h"
+
+// The reference's build has no fused multiply-add. The solvers are ill-conditioned on some samples (a sample of the fixture moves by
+// 7e-11 under contraction, 20 times the distance between reference and restatement there), and the order of near-equal residuals
+// follows the last bits: everything in this file is compiled as separate products and sums. (Division and square root of doubles round
+// correctly on the device; cbrt, acos, cos and log10 are OCML's, within an ulp or two of glibc's.)
+// (A file-scope pragma holds to the end of the translation unit: this header is the last thing mvgx_geofilter.hip includes. In the
+// emulation's single unit the files included after it are compiled for a host without fused multiply-add, where it changes nothing.)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kResWaves = 8;                  // W: waves (= iterations evaluated ahead) per workgroup
+constexpr uint32_t kResLdsMaxN = 1024;        // largest n whose sort slices and tables live in LDS (DESIGN.md derives it)
+constexpr uint32_t kResMaxN = 65536;          // largest supported n
+constexpr int kResVerdict = 18;               // doubles per wave: better | nfa | k | error | P[12] | models evaluated | unused
+constexpr int kResSolverNordberg = 3, kResSolverDing = 4;   // resection::SolverType (multiview/solver_resection.hpp:15-24)
+constexpr double kResFltEps = 1.1920928955078125e-07;       // std::numeric_limits<float>::epsilon()
+constexpr int kResTraceRecord = 10;           // words of a trace record (test hook): iteration | k | the first 8 sorted indices
+__host__ __device__ constexpr uint32_t res_trace_words(uint32_t events) { return 1 + kResTraceRecord * events; }   // per problem: count | records
+// Test hook (mvgx_resection_debug_trace): where the next call leaves, per problem, the iterations that found a better model
+uint32_t* g_res_trace = nullptr;
+uint32_t g_res_trace_events = 0;
+
+struct ResProblem {       // per problem, prepared on the host (glibc's log10: the reference's value)
+  uint64_t start;         // first correspondence, counted from the first problem's
+  uint64_t scratch;       // global form: byte offset of the problem's scratch
+  uint32_t n, model;
+  double intr[8];
+  double n1, loge0;       // imagePlane_toCameraPlaneError(1), log10(MAX_MODELS (n - 3))
+};
+struct ResResult {
+  double P[12];           // best model [R | t], row-major; valid if n_inliers > 0
+  double error_max, min_nfa;   // normalised squared residual at the chosen k; minNFA
+  uint32_t n_inliers, n_iterations, n_models, pad_;
+};
+
+struct ResV3 { double x, y, z; };
+__device__ __forceinline__ ResV3 res_sub(ResV3 a, ResV3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ ResV3 res_neg(ResV3 a) { return {-a.x, -a.y, -a.z}; }
+__device__ __forceinline__ ResV3 res_scale(ResV3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ double res_dot(ResV3 a, ResV3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ ResV3 res_cross(ResV3 a, ResV3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ ResV3 res_load(const double* p) { return {p[0], p[1], p[2]}; }
+
+// P3PSolver_Nordberg::root2real (solver_resection_p3p_nordberg.hpp:22-38)
+__device__ __forceinline__ bool res_root2real(double b, double c, double& r1, double& r2) {
+  const double v = b * b - 4.0 * c;
+  if (v <= 0.0) {
+    r1 = r2 = -0.5 * b;
+    return v >= 0.0;
+  }
+  const double y = sqrt(v);
+  if (b < 0.0) {
+    r1 = 0.5 * (-b + y);
+    r2 = 0.5 * (-b - y);
+  } else {
+    r1 = 2.0 * c / (-b + y);
+    r2 = 2.0 * c / (-b - y);
+  }
+  return true;
+}
+
+// What both solvers end with: R = [v1 v2 v1 x v2] [c0 c1 c0 x c1]^-1 (the inverse by cofactors, rows i0 i1 i2), t = base - R X0; the model
+// is stored as the row-major 3 x 4 matrix [R | t]
+struct ResFrame { ResV3 i0, i1, i2, X0; };
+__device__ __forceinline__ ResFrame res_frame(ResV3 c0, ResV3 c1, ResV3 X0) {
+  const ResV3 c2 = res_cross(c0, c1);
+  const ResV3 r0 = res_cross(c1, c2), r1 = res_cross(c2, c0), r2 = res_cross(c0, c1);
+  const double inv_det = 1.0 / res_dot(c0, r0);
+  return {res_scale(r0, inv_det), res_scale(r1, inv_det), res_scale(r2, inv_det), X0};
+}
+__device__ __forceinline__ void res_emit(const ResFrame& f, ResV3 v1, ResV3 v2, ResV3 base, double* __restrict__ Rt) {
+  const ResV3 v3 = res_cross(v1, v2);
+  const double r00 = v1.x * f.i0.x + v2.x * f.i1.x + v3.x * f.i2.x, r01 = v1.x * f.i0.y + v2.x * f.i1.y + v3.x * f.i2.y, r02 = v1.x * f.i0.z + v2.x * f.i1.z + v3.x * f.i2.z;
+  const double r10 = v1.y * f.i0.x + v2.y * f.i1.x + v3.y * f.i2.x, r11 = v1.y * f.i0.y + v2.y * f.i1.y + v3.y * f.i2.y, r12 = v1.y * f.i0.z + v2.y * f.i1.z + v3.y * f.i2.z;
+  const double r20 = v1.z * f.i0.x + v2.z * f.i1.x + v3.z * f.i2.x, r21 = v1.z * f.i0.y + v2.z * f.i1.y + v3.z * f.i2.y, r22 = v1.z * f.i0.z + v2.z * f.i1.z + v3.z * f.i2.z;
+  Rt[0] = r00; Rt[1] = r01; Rt[2] = r02; Rt[3] = base.x - (r00 * f.X0.x + r01 * f.X0.y + r02 * f.X0.z);
+  Rt[4] = r10; Rt[5] = r11; Rt[6] = r12; Rt[7] = base.y - (r10 * f.X0.x + r11 * f.X0.y + r12 * f.X0.z);
+  Rt[8] = r20; Rt[9] = r21; Rt[10] = r22; Rt[11] = base.z - (r20 * f.X0.x + r21 * f.X0.y + r22 * f.X0.z);
+}
+
+// ---- P3PSolver_Ding (solver_resection_p3p_ding.cpp) ----
+__device__ __forceinline__ void ding_refine(double& l1, double& l2, double& l3, double a12, double a13, double a23, double b12, double b13, double b23) {
+  for (int it = 0; it < 5; ++it) {
+    const double r1 = (l1 * l1 - 2.0 * l1 * l2 * b12 + l2 * l2 - a12);
+    const double r2 = (l1 * l1 - 2.0 * l1 * l3 * b13 + l3 * l3 - a13);
+    const double r3 = (l2 * l2 - 2.0 * l2 * l3 * b23 + l3 * l3 - a23);
+    if (fabs(r1) + fabs(r2) + fabs(r3) < 1e-10) return;
+    const double x11 = l1 - l2 * b12, x12 = l2 - l1 * b12, x21 = l1 - l3 * b13, x23 = l3 - l1 * b13, x32 = l2 - l3 * b23, x33 = l3 - l2 * b23;
+    const double detJ = 0.5 / (x11 * x23 * x32 + x12 * x21 * x33);
+    const double n1 = l1 + (-x23 * x32 * r1 - x12 * x33 * r2 + x12 * x23 * r3) * detJ;
+    const double n2 = l2 + (-x21 * x33 * r1 + x11 * x33 * r2 - x11 * x23 * r3) * detJ;
+    const double n3 = l3 + (x21 * x32 * r1 - x11 * x32 * r2 - x12 * x21 * r3) * detJ;
+    l1 = n1; l2 = n2; l3 = n3;
+  }
+}
+__device__ __forceinline__ bool ding_cubic_single_real(double c2, double c1, double c0, double& root) {
+  const double a = c1 - c2 * c2 / 3.0;
+  double b = (2.0 * c2 * c2 * c2 - 9.0 * c2 * c1) / 27.0 + c0;
+  double c = b * b / 4.0 + a * a * a / 27.0;
+  if (c != 0) {
+    if (c > 0) {
+      c = sqrt(c);
+      b *= -0.5;
+      root = cbrt(b + c) + cbrt(b - c) - c2 / 3.0;
+      return true;
+    }
+    c = 3.0 * b / (2.0 * a) * sqrt(-3.0 / a);
+    root = 2.0 * sqrt(-a / 3.0) * cos(acos(c) / 3.0) - c2 / 3.0;
+  } else {
+    root = -c2 / 3.0 + (a != 0 ? (3.0 * b / a) : 0);
+  }
+  return false;
+}
+struct DingCtx {
+  double a, b, a01, a02, a12, m01, m02, m12;
+  ResV3 x0, x1, x2;
+  ResFrame f;
+};
+// one positive tau of one line: depths, the refinement, the pose
+__device__ __forceinline__ void ding_tau(const DingCtx& c, bool switch_12, double tau, double w0, double w1, double* __restrict__ Rt, int& n_sols) {
+  if (tau <= 0) return;
+  double d0, d1, d2;
+  if (switch_12) {
+    d2 = sqrt(c.a12 / (tau * (tau - 2.0 * c.m12) + 1.0));
+    d1 = tau * d2;
+    d0 = (w0 * d2 + w1 * d1);
+    if (d0 < 0) return;
+  } else {
+    d0 = sqrt(c.a01 / (tau * (tau - 2.0 * c.m01) + 1.0));
+    d1 = tau * d0;
+    d2 = w0 * d0 + w1 * d1;
+    if (d2 < 0) return;
+  }
+  ding_refine(d0, d1, d2, c.a01, c.a02, c.a12, c.m01, c.m02, c.m12);
+  const ResV3 base = res_scale(c.x0, d0);
+  res_emit(c.f, res_sub(base, res_scale(c.x1, d1)), res_sub(base, res_scale(c.x2, d2)), base, Rt + 12 * n_sols);
+  ++n_sols;
+}
+__device__ __forceinline__ void ding_line(const DingCtx& c, double p0, double p1, double p2, double* __restrict__ Rt, int& n_sols) {
+  const bool switch_12 = fabs(p0) <= fabs(p1);
+  double w0, w1, cb, cc, tau0, tau1;
+  if (switch_12) {
+    w0 = -p0 / p1;
+    w1 = -p2 / p1;
+    const double ca = 1.0 / (w1 * w1 - c.b);
+    cb = 2.0 * (c.b * c.m12 - c.m02 * w1 + w0 * w1) * ca;
+    cc = (w0 * w0 - 2 * c.m02 * w0 - c.b + 1.0) * ca;
+  } else {
+    w0 = -p1 / p0;
+    w1 = -p2 / p0;
+    const double ca = 1.0 / (-c.a * w1 * w1 + 2 * c.a * c.m12 * w1 - c.a + 1);
+    cb = 2 * (c.a * c.m12 * w0 - c.m01 - c.a * w0 * w1) * ca;
+    cc = (1 - c.a * w0 * w0) * ca;
+  }
+  if (!res_root2real(cb, cc, tau0, tau1)) return;
+  ding_tau(c, switch_12, tau0, w0, w1, Rt, n_sols);
+  ding_tau(c, switch_12, tau1, w0, w1, Rt, n_sols);
+}
+// bear, X: three vectors each (3 x 3 doubles, one vector after the other); Rt: up to four [R | t]; returns their number
+__device__ __forceinline__ int p3p_ding(const double* __restrict__ bear, const double* __restrict__ X, double* __restrict__ Rt) {
+  ResV3 X0 = res_load(X), X1 = res_load(X + 3), X2 = res_load(X + 6);
+  ResV3 X01 = res_sub(X0, X1), X02 = res_sub(X0, X2);
+  const ResV3 X12 = res_sub(X1, X2);
+  double a01 = res_dot(X01, X01), a02 = res_dot(X02, X02), a12 = res_dot(X12, X12);
+  ResV3 x0 = res_load(bear), x1 = res_load(bear + 3), x2 = res_load(bear + 6);
+  // the columns are switched so that |X1 - X2| is the largest of the three distances
+  if (a01 > a02) {
+    if (a01 > a12) {
+      ResV3 t = X0; X0 = X2; X2 = t;
+      t = x0; x0 = x2; x2 = t;
+      const double s = a01; a01 = a12; a12 = s;
+      X01 = res_neg(X12);
+      X02 = res_neg(X02);
+    }
+  } else if (a02 > a12) {
+    ResV3 t = X0; X0 = X1; X1 = t;
+    t = x0; x0 = x1; x1 = t;
+    const double s = a02; a02 = a12; a12 = s;
+    X01 = res_neg(X01);
+    X02 = X12;
+  }
+  const double a12d = 1.0 / a12;
+  const double a = a01 * a12d, b = a02 * a12d;
+  const double m01 = res_dot(x0, x1), m02 = res_dot(x0, x2), m12 = res_dot(x1, x2);
+  const double m12sq = -m12 * m12 + 1.0, m02sq = -1.0 + m02 * m02, m01sq = -1.0 + m01 * m01;
+  const double ab = a * b, bsq = b * b, asq = a * a;
+  const double m013 = -2.0 + 2.0 * m01 * m02 * m12;
+  const double bsqm12sq = bsq * m12sq, asqm12sq = asq * m12sq, abm12sq = 2.0 * ab * m12sq;
+  const double k3_inv = 1.0 / (bsqm12sq + b * m02sq);
+  const double k2 = k3_inv * ((-1.0 + a) * m02sq + abm12sq + bsqm12sq + b * m013);
+  const double k1 = k3_inv * (asqm12sq + abm12sq + a * m013 + (-1.0 + b) * m01sq);
+  const double k0 = k3_inv * (asqm12sq + a * m01sq);
+  double s;
+  const bool G = ding_cubic_single_real(k2, k1, k0, s);
+  // the degenerate conic C = C1 + s C2 (symmetric) and its split into two lines (compute_pq)
+  const double C00 = -a + s * (1 - b), C01 = -m02 * s, C02 = a * m12 + b * m12 * s, C11 = s + 1, C12 = -m01, C22 = -a - b * s + 1;
+  const double A00 = C12 * C12 - C11 * C22, A11 = C02 * C02 - C00 * C22, A22 = C01 * C01 - C00 * C11;
+  const double A01 = C01 * C22 - C02 * C12, A02 = C02 * C11 - C01 * C12, A12 = C00 * C12 - C02 * C01;
+  double v0, v1, v2;
+  if (A00 > A11) {
+    if (A00 > A22) { const double q = sqrt(A00); v0 = A00 / q; v1 = A01 / q; v2 = A02 / q; }
+    else { const double q = sqrt(A22); v0 = A02 / q; v1 = A12 / q; v2 = A22 / q; }
+  } else if (A11 > A22) {
+    const double q = sqrt(A11); v0 = A01 / q; v1 = A11 / q; v2 = A12 / q;
+  } else {
+    const double q = sqrt(A22); v0 = A02 / q; v1 = A12 / q; v2 = A22 / q;
+  }
+  (void)v0;   // (v(0) only moves C(1,2) / C(2,1), which neither line reads)
+  DingCtx c{a, b, a01, a02, a12, m01, m02, m12, x0, x1, x2, res_frame(X01, X02, X0)};
+  int n_sols = 0;
+  ding_line(c, C00, C01 + v2, C02 - v1, Rt, n_sols);   // pq[0] = C.col(0)
+  if (n_sols > 0 && G) return n_sols;                  // only one line of the pair meets the conic
+  ding_line(c, C00, C01 - v2, C02 + v1, Rt, n_sols);   // pq[1] = C.row(0)
+  return n_sols;
+}
+
+// ---- P3PSolver_Nordberg (solver_resection_p3p_nordberg.cpp) ----
+__device__ __forceinline__ void nordberg_refine(double& L1, double& L2, double& L3, double a12, double a13, double a23, double b12, double b13, double b23) {
+  for (int i = 0; i < 5; ++i) {
+    const double l1 = L1, l2 = L2, l3 = L3;
+    const double r1 = l1 * l1 + l2 * l2 + b12 * l1 * l2 - a12;
+    const double r2 = l1 * l1 + l3 * l3 + b13 * l1 * l3 - a13;
+    const double r3 = l2 * l2 + l3 * l3 + b23 * l2 * l3 - a23;
+    if (fabs(r1) + fabs(r2) + fabs(r3) < 1e-10) break;
+    const double v0 = 2.0 * l1 + b12 * l2, v1 = 2.0 * l2 + b12 * l1, v3 = 2.0 * l1 + b13 * l3, v5 = 2.0 * l3 + b13 * l1;
+    const double v7 = 2.0 * l2 + b23 * l3, v8 = 2.0 * l3 + b23 * l2;
+    const double det = 1.0 / (-v0 * v5 * v7 - v1 * v3 * v8);
+    const double n1 = l1 - det * (-v5 * v7 * r1 + -v1 * v8 * r2 + v1 * v5 * r3);
+    const double n2 = l2 - det * (-v3 * v8 * r1 + v0 * v8 * r2 + -v0 * v5 * r3);
+    const double n3 = l3 - det * (v3 * v7 * r1 + -v0 * v7 * r2 + -v1 * v3 * r3);
+    const double r11 = n1 * n1 + n2 * n2 + b12 * n1 * n2 - a12;
+    const double r12 = n1 * n1 + n3 * n3 + b13 * n1 * n3 - a13;
+    const double r13 = n2 * n2 + n3 * n3 + b23 * n2 * n3 - a23;
+    if (fabs(r11) + fabs(r12) + fabs(r13) > fabs(r1) + fabs(r2) + fabs(r3)) break;
+    L1 = n1; L2 = n2; L3 = n3;
+  }
+}
+__device__ __forceinline__ double nordberg_cubick(double b, double c, double d) {
+  double r0;
+  if (b * b >= 3.0 * c) {
+    const double v = sqrt(b * b - 3.0 * c);
+    const double t1 = (-b - v) / (3.0);
+    double k = ((t1 + b) * t1 + c) * t1 + d;
+    if (k > 0.0) {
+      r0 = t1 - sqrt(-k / (3.0 * t1 + b));
+    } else {
+      const double t2 = (-b + v) / 3.0;
+      k = ((t2 + b) * t2 + c) * t2 + d;
+      r0 = t2 + sqrt(-k / (3.0 * t2 + b));
+    }
+  } else {
+    r0 = -b / 3.0;
+    if (fabs(((3.0 * r0 + 2.0 * b) * r0 + c)) < 1e-4) r0 += 1;
+  }
+  for (unsigned int cnt = 0; cnt < 50; ++cnt) {
+    const double fx = (((r0 + b) * r0 + c) * r0 + d);
+    if ((cnt < 7 || fabs(fx) > 1e-13)) {
+      const double fpx = ((3.0 * r0 + 2.0 * b) * r0 + c);
+      r0 -= fx / fpx;
+    } else {
+      break;
+    }
+  }
+  return r0;
+}
+struct NordbergCtx {
+  double a12, a13, a23, b12, b13, b23;
+  ResV3 f1, f2, f3;
+  ResFrame f;
+};
+__device__ __forceinline__ void nordberg_pose(const NordbergCtx& c, double l1, double l2, double l3, double* __restrict__ Rt, int& valid) {
+  nordberg_refine(l1, l2, l3, c.a12, c.a13, c.a23, c.b12, c.b13, c.b23);
+  const ResV3 ry1 = res_scale(c.f1, l1), ry2 = res_scale(c.f2, l2), ry3 = res_scale(c.f3, l3);
+  res_emit(c.f, res_sub(ry1, ry2), res_sub(ry1, ry3), ry1, Rt + 12 * valid);
+  ++valid;
+}
+__device__ __forceinline__ void nordberg_sign(const NordbergCtx& c, ResV3 U, double* __restrict__ Rt, int& valid) {
+  const double u1 = U.x, u2 = U.y, u3 = U.z;
+  const double a12 = c.a12, a13 = c.a13, a23 = c.a23, b12 = c.b12, b13 = c.b13, b23 = c.b23;
+  double tau0, tau1;
+  if (fabs(u1) < fabs(u2)) {   // solve for l2
+    const double a = (a23 - a12) * u3 * u3 - a12 * u2 * u2 + a12 * b23 * u2 * u3;
+    const double b = (2. * a23 * u1 * u3 - 2. * a12 * u1 * u3 + a12 * b23 * u1 * u2 - a23 * b12 * u2 * u3) / a;
+    const double cq = (a23 * u1 * u1 - a12 * u1 * u1 + a23 * u2 * u2 - a23 * b12 * u1 * u2) / a;
+    if (!res_root2real(b, cq, tau0, tau1)) return;
+    for (int r = 0; r < 2; ++r) {
+      const double tau = r == 0 ? tau0 : tau1;
+      if (tau <= 0) continue;
+      const double l1 = sqrt(a13 / (tau * (tau + b13) + 1.));
+      const double l3 = tau * l1;
+      const double l2 = -(u1 * l1 + u3 * l3) / u2;
+      if (l2 <= 0.) continue;
+      nordberg_pose(c, l1, l2, l3, Rt, valid);
+    }
+  } else {   // solve for l1
+    const double w2 = 1. / (-u1);
+    const double w0 = u2 * w2, w1 = u3 * w2;
+    const double a = 1.0 / ((a13 - a12) * w1 * w1 - a12 * b13 * w1 - a12);
+    const double b = (a13 * b12 * w1 - a12 * b13 * w0 - 2. * w0 * w1 * (a12 - a13)) * a;
+    const double cq = ((a13 - a12) * w0 * w0 + a13 * b12 * w0 + a13) * a;
+    if (!res_root2real(b, cq, tau0, tau1)) return;
+    for (int r = 0; r < 2; ++r) {
+      const double tau = r == 0 ? tau0 : tau1;
+      if (tau <= 0.) continue;
+      const double d = a23 / (tau * (b23 + tau) + 1.0);
+      const double l2 = sqrt(d);
+      const double l3 = tau * l2;
+      const double l1 = w0 * l2 + w1 * l3;
+      if (l1 <= 0.) continue;
+      nordberg_pose(c, l1, l2, l3, Rt, valid);
+    }
+  }
+}
+// (The reference collects the up to four depth triples, refines them all, then forms the poses: each triple's refinement and pose depend
+// on that triple alone, so they are formed here as the triples are found - the same models in the same order.)
+__device__ __forceinline__ int p3p_nordberg(const double* __restrict__ bear, const double* __restrict__ X, double* __restrict__ Rt) {
+  const ResV3 P1 = res_load(X), P2 = res_load(X + 3), P3 = res_load(X + 6);
+  const ResV3 f1 = res_load(bear), f2 = res_load(bear + 3), f3 = res_load(bear + 6);
+  const double b12 = -2.0 * (res_dot(f1, f2)), b13 = -2.0 * (res_dot(f1, f3)), b23 = -2.0 * (res_dot(f2, f3));
+  const ResV3 d12 = res_sub(P1, P2), d13 = res_sub(P1, P3), d23 = res_sub(P2, P3);
+  const double a12 = res_dot(d12, d12), a13 = res_dot(d13, d13), a23 = res_dot(d23, d23);
+  const double c31 = -0.5 * b13, c23 = -0.5 * b23, c12 = -0.5 * b12;
+  const double blob = (c12 * c23 * c31 - 1.0);
+  const double s31_squared = 1.0 - c31 * c31, s23_squared = 1.0 - c23 * c23, s12_squared = 1.0 - c12 * c12;
+  double p3 = a13 * (a23 * s31_squared - a13 * s23_squared);
+  double p2 = 2.0 * blob * a23 * a13 + a13 * (2.0 * a12 + a13) * s23_squared + a23 * (a23 - a12) * s31_squared;
+  double p1 = a23 * (a13 - a23) * s12_squared - a12 * a12 * s23_squared - 2.0 * a12 * (blob * a23 + a13 * s23_squared);
+  double p0 = a12 * (a12 * s23_squared - a23 * s12_squared);
+  p3 = 1.0 / p3;
+  p2 *= p3; p1 *= p3; p0 *= p3;
+  const double g = nordberg_cubick(p2, p1, p0);
+  const double A00 = a23 * (1.0 - g), A01 = (a23 * b12) * 0.5, A02 = (a23 * b13 * g) * (-0.5);
+  const double A11 = a23 - a12 + a13 * g, A12 = b23 * (a13 * g - a12) * 0.5, A22 = g * (a13 - a23) - a12;
+  // eigwithknown0: A has a zero eigenvalue; the other two from the characteristic quadratic, the larger in magnitude first, and their
+  // vectors (the vector of the zero eigenvalue is computed by the reference and never read: left out)
+  const double x01_squared = A01 * A01;
+  const double qb = -A00 - A11 - A22;
+  const double qc = -x01_squared - A02 * A02 - A12 * A12 + A00 * (A11 + A22) + A11 * A22;
+  double e1, e2;
+  (void)res_root2real(qb, qc, e1, e2);
+  if (fabs(e1) < fabs(e2)) { const double t = e1; e1 = e2; e2 = t; }
+  const double mx0011 = -A00 * A11;
+  const double prec_0 = A01 * A12 - A02 * A11, prec_1 = A01 * A02 - A00 * A12;
+  const double tmp = 1.0 / (e1 * (A00 + A11) + mx0011 - e1 * e1 + x01_squared);
+  double a1 = -(e1 * A02 + prec_0) * tmp, a2 = -(e1 * A12 + prec_1) * tmp;
+  const double rnorm = 1.0 / sqrt(a1 * a1 + a2 * a2 + 1.0);
+  a1 *= rnorm; a2 *= rnorm;
+  const double tmp2 = 1.0 / (e2 * (A00 + A11) + mx0011 - e2 * e2 + x01_squared);
+  double a21 = -(e2 * A02 + prec_0) * tmp2, a22 = -(e2 * A12 + prec_1) * tmp2;
+  const double rnorm2 = 1.0 / sqrt(a21 * a21 + a22 * a22 + 1.0);
+  a21 *= rnorm2; a22 *= rnorm2;
+  const double q = -e2 / e1;
+  const double v = sqrt(0.0 < q ? q : 0.0);   // std::max(0.0, q): 0 for a NaN
+  NordbergCtx c{a12, a13, a23, b12, b13, b23, f1, f2, f3, res_frame(d12, d13, P1)};
+  int valid = 0;
+  nordberg_sign(c, ResV3{a1 - v * a21, a2 - v * a22, rnorm - v * rnorm2}, Rt, valid);
+  nordberg_sign(c, ResV3{a1 - (-v) * a21, a2 - (-v) * a22, rnorm - (-v) * rnorm2}, Rt, valid);
+  return valid;
+}
+
+__device__ __forceinline__ int res_solve(int solver, const double* __restrict__ bear, const double* __restrict__ X, double* __restrict__ Rt) {
+  return solver == kResSolverNordberg ? p3p_nordberg(bear, X, Rt) : p3p_ding(bear, X, Rt);
+}
+
+// Test hook: one lane per sample
+__global__ __launch_bounds__(64) void resection_p3p_debug_kernel(int solver, const double* __restrict__ bear, const double* __restrict__ X, uint32_t n_samples,
+                                                                 double* __restrict__ Rt_out, int* __restrict__ n_out) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n_samples) return;
+  n_out[i] = res_solve(solver, bear + 9 * (size_t)i, X + 9 * (size_t)i, Rt_out + 48 * (size_t)i);
+}
+
+// ---- prepare pass: the bearing of every correspondence, once per problem ----
+__global__ __launch_bounds__(256) void resection_bearing_kernel(const ResProblem* __restrict__ problems, uint32_t n_problems, uint64_t n_total,
+                                                                const double* __restrict__ x2d, double* __restrict__ bear) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_total) return;
+  uint32_t lo = 0, hi = n_problems - 1;   // the last problem that starts at or before i and is not empty there
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) / 2;
+    if (problems[mid].start <= i) lo = mid; else hi = mid - 1;
+  }
+  const ResProblem& P = problems[lo];
+  double b[3];
+  mvgx_ba::camera_bearing((int)P.model, P.intr, x2d + 2 * i, /*undistort=*/false, b);
+  bear[3 * i] = b[0]; bear[3 * i + 1] = b[1]; bear[3 * i + 2] = b[2];
+}
+
+// ---- the loop ----
+// words of LDS a workgroup needs: generator | its copy | verdicts | models | samples, swaps, counts | best model | (LDS form) pool, inliers, logc_n, logc_k, slices
+__host__ __device__ constexpr uint32_t res_fixed_words() { return 2 * kMtN + 2 * kResWaves * kResVerdict + 2 * kResWaves * 48 + 8 * kResWaves + 24; }
+__host__ __device__ constexpr uint32_t res_table_words(uint32_t n) { return 4 * (n + 1); }    // pool, inliers, logc_n, logc_k (n + 1 each)
+__host__ __device__ constexpr uint32_t res_slice_words(uint32_t p2) { return 3 * p2; }         // keys (64 bit) | indices
+__host__ __device__ inline uint32_t res_pow2(uint32_t n) { uint32_t p = 64; while (p < n) p <<= 1; return p; }   // the sort's length: n padded with +inf
+inline size_t res_scratch_bytes(uint32_t n) { return ((size_t)4 * (res_table_words(n) + kResWaves * res_slice_words(res_pow2(n))) + 255) / 256 * 256; }
+inline uint32_t res_lds_bytes(uint32_t n_lds_max) { return 4 * (res_fixed_words() + (n_lds_max ? res_table_words(n_lds_max) + kResWaves * res_slice_words(res_pow2(n_lds_max)) : 0)); }
+
+struct ResKeyIdx { uint64_t key; uint32_t idx; };
+// (residual bits, index) ascending: residuals are non-negative or +inf, so the bit patterns order as the values do
+__device__ __forceinline__ bool res_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
+  return ka < kb || (ka == kb && ia < ib);
+}
+
+// bitonic sort of p2 (a power of two >= 64) records by one wave; every stage ends with the wave's writes visible to its lanes. In the
+// global form the slice is global memory: wave_sync's wavefront-scope fence covers every address space (the compiler waits for the
+// stores), and a CU's vector memory path serves one wave's accesses to an address in order, so the next stage's loads see them.
+__device__ __forceinline__ void res_sort(uint64_t* keys, uint32_t* idx, uint32_t p2, int lane) {
+  for (uint32_t k = 2; k <= p2; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = lane; t < p2 / 2; t += 64) {
+        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const uint64_t ki = keys[i], kl = keys[l];
+        const uint32_t ii = idx[i], il = idx[l];
+        const bool up = (i & k) == 0;
+        if (res_less(kl, il, ki, ii) == up) { keys[i] = kl; keys[l] = ki; idx[i] = il; idx[l] = ii; }
+      }
+      wave_sync();
+    }
+  }
+}
+
+template <bool kGlobal>
+__global__ __launch_bounds__(64 * kResWaves) void resection_acransac_kernel(const ResProblem* __restrict__ problems, const uint32_t* __restrict__ order, uint32_t n_work,
+                                                                            const double* __restrict__ x2d, const double* __restrict__ X3d, const double* __restrict__ bear,
+                                                                            const float* __restrict__ l10, const uint32_t* __restrict__ mt_init, uint32_t max_iteration,
+                                                                            int solver, uint32_t waves_ahead, uint32_t n_lds_max, unsigned char* __restrict__ scratch,
+                                                                            ResResult* __restrict__ results, uint32_t* __restrict__ inliers_out, uint32_t* __restrict__ trace, uint32_t trace_events) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_u32[];
+  if (blockIdx.x >= n_work) return;
+  const uint32_t pi = order[blockIdx.x];
+  const ResProblem& P = problems[pi];
+  const uint32_t n = P.n, p2 = res_pow2(n);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n_threads = 64 * kResWaves;
+
+  uint32_t* const mt = lds_u32;
+  uint32_t* const mt_saved = mt + kMtN;
+  double* const verdicts = reinterpret_cast<double*>(mt_saved + kMtN);
+  double* const models = verdicts + kResWaves * kResVerdict;        // 48 doubles per wave
+  uint32_t* const samples = reinterpret_cast<uint32_t*>(models + kResWaves * 48);   // 3 per wave | swap partners, 3 per wave | models per wave
+  uint32_t* const swaps = samples + 3 * kResWaves;
+  uint32_t* const n_mod = swaps + 3 * kResWaves;
+  double* const best_model = reinterpret_cast<double*>(samples + 8 * kResWaves);   // the winning [R | t] (thread 0 writes and reads it)
+  uint32_t* const tables = kGlobal ? reinterpret_cast<uint32_t*>(scratch + P.scratch) : lds_u32 + res_fixed_words();
+  const uint32_t n1 = n + 1;
+  uint32_t* const pool = tables;
+  uint32_t* const inliers = pool + n1;
+  float* const logc_n = reinterpret_cast<float*>(inliers + n1);
+  float* const logc_k = logc_n + n1;
+  uint32_t* const slices = tables + res_table_words(kGlobal ? n : n_lds_max);
+  const uint32_t slice_words = res_slice_words(kGlobal ? p2 : res_pow2(n_lds_max));   // LDS form: every wave's slice is sized for the launch's largest problem
+  uint64_t* const my_keys = reinterpret_cast<uint64_t*>(slices + (size_t)wave * slice_words);
+  uint32_t* const my_idx = reinterpret_cast<uint32_t*>(my_keys + p2);
+
+  const double2* const px = reinterpret_cast<const double2*>(x2d) + P.start;
+  const double* const pX = X3d + 3 * P.start;
+  const double* const pb = bear + 3 * P.start;
+  const double n1norm = P.n1, loge0 = P.loge0;
+  const double logalpha0 = 0.49714987269413385;   // log10(M_PI)
+  const int res_model = P.model == (uint32_t)mvgx_ba::kCamSpherical ? mvgx_ba::kCamSpherical : mvgx_ba::kCamPinhole;   // ignore_distortion
+
+  // tables and generator
+  for (uint32_t k = tid; k <= n; k += n_threads) {
+    pool[k] = k;
+    logc_k[k] = logcombi(3, k, l10);
+  }
+  // logc_n[k] = logcombi(k, n) is the running float sum of min(k, n - k) terms that do not depend on k: one pass of n / 2 dependent
+  // additions by one thread (the sum's order is the reference's; n calls of logcombi would be n^2 / 4 additions), then the mirror
+  if (tid == 0) {
+    float r = 0.f;
+    logc_n[0] = 0.f;
+    for (uint32_t i = 1; i <= n / 2; ++i) { r += l10[n - i + 1] - l10[i]; logc_n[i] = r; }
+  }
+  __syncthreads();
+  for (uint32_t k = n / 2 + 1 + tid; k <= n; k += n_threads) logc_n[k] = k >= n ? 0.f : logc_n[n - k];
+  for (int i = tid; i < kMtN; i += n_threads) mt[i] = mt_init[i];
+  int mt_idx = kMtN, mt_idx_saved = kMtN;   // (tracked by wave 0 alone)
+  __syncthreads();
+
+  const uint32_t Wa = waves_ahead ? waves_ahead : (uint32_t)kResWaves;
+  double minNFA = INFINITY, errorMax = INFINITY;
+  if (tid == 0)
+    for (int e = 0; e < 12; ++e) best_model[e] = 0.0;
+  uint32_t n_inl = 0, pool_n = n;
+  int nIterReserve = (int)(max_iteration / 10);
+  uint32_t nIter = max_iteration - (uint32_t)nIterReserve;
+  uint32_t iter = 0, n_models_total = 0;
+
+  while (iter < nIter && iter < max_iteration) {
+    const uint32_t nb = min(Wa, min(nIter - iter, max_iteration - iter));
+    // ---- the samples of the block, drawn in iteration order from the one generator (wave 0) ----
+    if (wave == 0) {
+      for (int i = lane; i < kMtN; i += 64) mt_saved[i] = mt[i];   // (a twist cannot be taken back: the state before the block is kept)
+      wave_sync();
+      mt_idx_saved = mt_idx;
+      for (uint32_t j = 0; j < nb; ++j) {
+        for (uint32_t i = 0; i < 3; ++i) {
+          const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
+          if (lane == 0) {   // (lane 0 alone reads and writes the pool here)
+            const uint32_t a = pool[i], b = pool[r];
+            pool[i] = b; pool[r] = a;
+            swaps[3 * j + i] = r;
+          }
+        }
+        if (lane == 0) { samples[3 * j] = pool[0]; samples[3 * j + 1] = pool[1]; samples[3 * j + 2] = pool[2]; }
+      }
+    }
+    __syncthreads();
+
+    // ---- one wave, one iteration ----
+    if ((uint32_t)wave < nb) {
+      double* const my_models = models + 48 * wave;
+      // the sample's vectors in the wave's verdict slot (18 doubles), read by lane 0's solve before the verdict is written
+      double* const my_verdict = verdicts + kResVerdict * wave;
+      if (lane < 3) {
+        const uint32_t s = samples[3 * wave + lane];
+        my_verdict[3 * lane] = pb[3 * s]; my_verdict[3 * lane + 1] = pb[3 * s + 1]; my_verdict[3 * lane + 2] = pb[3 * s + 2];
+        my_verdict[9 + 3 * lane] = pX[3 * s]; my_verdict[9 + 3 * lane + 1] = pX[3 * s + 1]; my_verdict[9 + 3 * lane + 2] = pX[3 * s + 2];
+      }
+      wave_sync();
+      if (lane == 0) n_mod[wave] = (uint32_t)res_solve(solver, my_verdict, my_verdict + 9, my_models);
+      wave_sync();
+      const int nm = (int)n_mod[wave];
+      double run_min = minNFA, win_err = 0.0;
+      int winner = -1, sorted = -1;
+      uint32_t win_k = 0, evaluated = 0;
+      for (int m = 0; m <= nm; ++m) {
+        // m == nm: the winner's order once more, if a later model of the iteration was sorted over it
+        const int mm = m < nm ? m : winner;
+        if (m == nm && (winner < 0 || winner == sorted)) break;
+        const double* const M = my_models + 12 * mm;
+        const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5], m6 = M[6], m7 = M[7], m8 = M[8], m9 = M[9], m10 = M[10], m11 = M[11];
+        // a model with a non-finite entry is skipped (the reference would sort NaNs: undefined)
+        const double probe = m0 + m1 + m2 + m3 + m4 + m5 + m6 + m7 + m8 + m9 + m10 + m11;
+        if (!(fabs(probe) < INFINITY)) continue;
+        for (uint32_t i = lane; i < p2; i += 64) {
+          double e = INFINITY;
+          if (i < n) {
+            const double X = pX[3 * i], Y = pX[3 * i + 1], Z = pX[3 * i + 2];
+            const double pc[3] = {m0 * X + m1 * Y + m2 * Z + m3, m4 * X + m5 * Y + m6 * Z + m7, m8 * X + m9 * Y + m10 * Z + m11};
+            const double2 obs = px[i];
+            const double ob[2] = {obs.x, obs.y};
+            double r[2];
+            mvgx_ba::project_residual(res_model, P.intr, pc, ob, r);
+            const double rx = mul_rn(r[0], n1norm), ry = mul_rn(r[1], n1norm);
+            e = add_rn(mul_rn(rx, rx), mul_rn(ry, ry));
+            if (!(e < INFINITY)) e = INFINITY;   // NaN too
+          }
+          my_keys[i] = (uint64_t)__double_as_longlong(e);
+          my_idx[i] = i;
+        }
+        wave_sync();
+        res_sort(my_keys, my_idx, p2, lane);
+        sorted = mm;
+        if (m == nm) break;
+        ++evaluated;
+        // NFA(k) for every k in [4, n]: the smallest, the lowest k among equals
+        double best = INFINITY;
+        uint32_t best_k = 3;
+        for (uint32_t k = 4 + lane; k <= n; k += 64) {
+          const double r = __longlong_as_double((long long)my_keys[k - 1]);
+          const double logalpha = add_rn(logalpha0, log10(add_rn(r, kResFltEps)));
+          const double nfa = add_rn(add_rn(add_rn(loge0, mul_rn(logalpha, (double)(k - 3))), (double)logc_n[k]), (double)logc_k[k]);
+          if (nfa < best) { best = nfa; best_k = k; }
+        }
+        for (int d = 32; d > 0; d >>= 1) {
+          const double o = __shfl_xor(best, d);
+          const uint32_t ok = (uint32_t)__shfl_xor((int)best_k, d);
+          if (o < best || (o == best && ok < best_k)) { best = o; best_k = ok; }
+        }
+        if (best < run_min) {
+          run_min = best; winner = mm; win_k = best_k;
+          win_err = __longlong_as_double((long long)my_keys[best_k - 1]);
+        }
+      }
+      wave_sync();   // every lane has read the sample's vectors and the keys before the verdict overwrites the slot
+      if (lane == 0) {
+        my_verdict[0] = winner >= 0 ? 1.0 : 0.0;
+        my_verdict[1] = run_min; my_verdict[2] = (double)win_k; my_verdict[3] = win_err;
+        const double* const M = my_models + 12 * (winner >= 0 ? winner : 0);
+        for (int e = 0; e < 12; ++e) my_verdict[4 + e] = M[e];
+        my_verdict[16] = (double)evaluated;
+      }
+    }
+    __syncthreads();
+
+    // ---- the verdicts in iteration order: the first event is applied, what follows it is void ----
+    uint32_t done = nb;
+    bool event = false;
+    for (uint32_t j = 0; j < nb && !event; ++j) {
+      const double* const v = verdicts + kResVerdict * j;
+      n_models_total += (uint32_t)v[16];
+      const bool better = v[0] != 0.0;   // (evaluated under the block's minNFA, which no earlier verdict of the block has changed)
+      if (better) {
+        minNFA = v[1]; errorMax = v[3]; n_inl = (uint32_t)v[2];
+        if (tid == 0)
+          for (int e = 0; e < 12; ++e) best_model[e] = v[4 + e];
+        const uint32_t* const src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint64_t*>(slices + (size_t)j * slice_words) + p2);
+        for (uint32_t i = tid; i < n_inl; i += n_threads) inliers[i] = src[i];
+        if (trace && tid == 0) {   // test hook: iteration | k | the head of the sorted list, one record per iteration that found a better model
+          uint32_t* const T = trace + (size_t)pi * res_trace_words(trace_events);
+          const uint32_t at = T[0];
+          if (at < trace_events) {
+            uint32_t* const rec = T + 1 + (size_t)kResTraceRecord * at;
+            rec[0] = iter + j; rec[1] = n_inl;
+            for (uint32_t i = 0; i < (uint32_t)kResTraceRecord - 2; ++i) rec[2 + i] = i < n_inl ? src[i] : 0xffffffffu;
+          }
+          T[0] = at + 1;
+        }
+      }
+      const bool branch = (better && minNFA < 0) || ((iter + j + 1) == nIter && nIterReserve > 0);
+      bool take_pool = false;
+      if (branch) {
+        if (n_inl == 0) { ++nIter; --nIterReserve; }
+        else {
+          take_pool = true;
+          if (nIterReserve) { nIter = iter + j + 1 + (uint32_t)nIterReserve; nIterReserve = 0; }
+        }
+      }
+      if (better || branch) {
+        event = true;
+        done = j + 1;
+        __syncthreads();   // the inlier list is complete; wave 0 may touch the pool
+        if (done < nb && wave == 0) {
+          // the generator and the pool as they stood after iteration j: undo the block's swaps, restore the state, draw j + 1 again
+          if (lane == 0)
+            for (int s = 3 * (int)nb - 1; s >= 0; --s) {
+              const uint32_t i = (uint32_t)s % 3, r = swaps[s];
+              const uint32_t a = pool[i], b = pool[r];
+              pool[i] = b; pool[r] = a;
+            }
+          for (int i = lane; i < kMtN; i += 64) mt[i] = mt_saved[i];
+          wave_sync();
+          mt_idx = mt_idx_saved;
+          for (uint32_t jj = 0; jj < done; ++jj)
+            for (uint32_t i = 0; i < 3; ++i) {
+              const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
+              if (lane == 0) { const uint32_t a = pool[i], b = pool[r]; pool[i] = b; pool[r] = a; }
+            }
+        }
+        __syncthreads();
+        if (take_pool) {   // vec_index = vec_inliers: in sorted order
+          for (uint32_t i = tid; i < n_inl; i += n_threads) pool[i] = inliers[i];
+          pool_n = n_inl;
+        }
+      }
+    }
+    iter += done;
+    __syncthreads();
+  }
+
+  if (minNFA >= 0) n_inl = 0;   // no meaningful model
+  for (uint32_t i = tid; i < n_inl; i += n_threads) inliers_out[P.start + i] = inliers[i];
+  if (tid == 0) {
+    ResResult& R = results[pi];
+    for (int e = 0; e < 12; ++e) R.P[e] = best_model[e];
+    R.error_max = errorMax; R.min_nfa = minNFA; R.n_inliers = n_inl; R.n_iterations = iter; R.n_models = n_models_total; R.pad_ = 0;
+  }
+}
+
+// ---- host ----
+// KRt_From_P (multiview/projection.cpp:40-132) of P = [R | t]: RQ of the left block by three Givens rotations, the signs fixed, t = K^-1 p4
+inline void res_mul3(const double* A, const double* B, double* C) {
+  double T[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) T[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+  memcpy(C, T, sizeof(T));
+}
+inline void res_krt_from_p(const double* P, double* K, double* R, double* t) {
+  double Q[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) K[3 * i + j] = P[4 * i + j];
+  const auto rotate = [&](const double* Qr) {
+    double Qt[9];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) Qt[3 * i + j] = Qr[3 * j + i];
+    res_mul3(K, Qr, K);
+    res_mul3(Qt, Q, Q);
+  };
+  if (K[7] != 0) {
+    double c = -K[8], s = K[7];
+    const double l = std::hypot(c, s);
+    c /= l; s /= l;
+    const double Qx[9] = {1, 0, 0, 0, c, -s, 0, s, c};
+    rotate(Qx);
+  }
+  if (K[6] != 0) {
+    double c = K[8], s = K[6];
+    const double l = std::hypot(c, s);
+    c /= l; s /= l;
+    const double Qy[9] = {c, 0, s, 0, 1, 0, -s, 0, c};
+    rotate(Qy);
+  }
+  if (K[3] != 0) {
+    double c = -K[4], s = K[3];
+    const double l = std::hypot(c, s);
+    c /= l; s /= l;
+    const double Qz[9] = {c, -s, 0, s, c, 0, 0, 0, 1};
+    rotate(Qz);
+  }
+  memcpy(R, Q, sizeof(Q));
+  if (K[8] < 0)
+    for (int e = 0; e < 9; ++e) { K[e] = -K[e]; R[e] = -R[e]; }
+  if (K[4] < 0) {
+    const double S[9] = {1, 0, 0, 0, -1, 0, 0, 0, 1};
+    res_mul3(K, S, K);
+    res_mul3(S, R, R);
+  }
+  if (K[0] < 0) {
+    const double S[9] = {-1, 0, 0, 0, 1, 0, 0, 0, 1};
+    res_mul3(K, S, K);
+    res_mul3(S, R, R);
+  }
+  // t = K^-1 p4 by elimination with partial pivoting (Eigen::PartialPivLU)
+  double A[12];
+  for (int i = 0; i < 3; ++i) { A[4 * i] = K[3 * i]; A[4 * i + 1] = K[3 * i + 1]; A[4 * i + 2] = K[3 * i + 2]; A[4 * i + 3] = P[4 * i + 3]; }
+  for (int c = 0; c < 3; ++c) {
+    int piv = c;
+    for (int r = c + 1; r < 3; ++r)
+      if (std::fabs(A[4 * r + c]) > std::fabs(A[4 * piv + c])) piv = r;
+    if (piv != c)
+      for (int e = 0; e < 4; ++e) std::swap(A[4 * c + e], A[4 * piv + e]);
+    for (int r = c + 1; r < 3; ++r) {
+      const double f = A[4 * r + c] / A[4 * c + c];
+      for (int e = c; e < 4; ++e) A[4 * r + e] -= f * A[4 * c + e];
+    }
+  }
+  t[2] = A[11] / A[10];
+  t[1] = (A[7] - A[6] * t[2]) / A[5];
+  t[0] = (A[3] - A[1] * t[1] - A[2] * t[2]) / A[0];
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  if (det < 0) {
+    for (int e = 0; e < 9; ++e) R[e] = -R[e];
+    for (int e = 0; e < 3; ++e) t[e] = -t[e];
+  }
+  const double k22 = K[8];
+  for (int e = 0; e < 9; ++e) K[e] /= k22;
+}
+
+template <bool kGlobal>
+int res_launch(uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, const ResProblem* problems, const uint32_t* order, const double* x2d, const double* X3d,
+               const double* bear, const float* l10, const uint32_t* mt_init, uint32_t max_iteration, int solver, uint32_t waves_ahead, uint32_t n_lds_max,
+               unsigned char* scratch, ResResult* results, uint32_t* inliers_out, uint32_t* trace, uint32_t trace_events) {
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resection_acransac_kernel<kGlobal>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL((resection_acransac_kernel<kGlobal>), dim3(n_work), dim3(64 * kResWaves), lds_bytes, stream, problems, order, n_work, x2d, X3d, bear, l10,
+                     mt_init, max_iteration, solver, waves_ahead, n_lds_max, scratch, results, inliers_out, trace, trace_events);
+  MVGX_HIP(hipGetLastError());
+  return MVGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void mvgx_resection_default_options(mvgx_resection_options* o) {
+  if (!o) return;
+  // Image_Localizer_Match_Data's defaults (SfM_Localizer.hpp:28-37) and resection::SolverType::DEFAULT
+  o->solver = MVGX_RESECTION_P3P_DING; o->max_iteration = 4096; o->error_max = std::numeric_limits<double>::infinity();
+  o->waves_ahead = 0; o->global_above = 0;
+}
+
+int mvgx_resection_localize(int device, uint32_t n_problems, const uint64_t* start, const double* x2d, const double* X3d, const int32_t* intr_model,
+                            const double* intrinsics, const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose, double* out_P,
+                            double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats) {
+  using clock = std::chrono::steady_clock;
+  const auto t_begin = clock::now();
+  MVGX_REQUIRE(opt && start && out_ok && out_pose && out_P && out_error_max && out_min_nfa && out_inlier_start, MVGX_ERR_ARG, "%s: NULL argument", __func__);
+  MVGX_REQUIRE(n_problems == 0 || (intr_model && intrinsics), MVGX_ERR_ARG, "%s: NULL camera arrays", __func__);
+  MVGX_REQUIRE(opt->solver >= 0 && opt->solver <= 5, MVGX_ERR_ARG, "%s: solver %d is no resection::SolverType", __func__, opt->solver);
+  MVGX_REQUIRE(opt->solver == MVGX_RESECTION_P3P_DING || opt->solver == MVGX_RESECTION_P3P_NORDBERG, MVGX_ERR_UNSUPPORTED,
+               "%s: solver %d has no device path (P3P_DING_CVPR23 = 4 and P3P_NORDBERG_ECCV18 = 3 have)", __func__, opt->solver);
+  MVGX_REQUIRE(std::isinf(opt->error_max) && opt->error_max > 0, MVGX_ERR_UNSUPPORTED,
+               "%s: a finite error_max selects the quantified NFA with the max-consensus early exit, which has no device path yet", __func__);
+  MVGX_REQUIRE(opt->waves_ahead <= (uint32_t)kResWaves, MVGX_ERR_ARG, "%s: waves_ahead %u exceeds the build's %d", __func__, opt->waves_ahead, kResWaves);
+  uint32_t n_max = 0;
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    MVGX_REQUIRE(start[p + 1] >= start[p], MVGX_ERR_ARG, "%s: start decreases at problem %u", __func__, p);
+    const uint64_t n = start[p + 1] - start[p];
+    MVGX_REQUIRE(n <= kResMaxN, MVGX_ERR_ARG, "%s: problem %u has %llu correspondences, the supported maximum is %u", __func__, p, (unsigned long long)n, kResMaxN);
+    const int m = intr_model[p];
+    MVGX_REQUIRE(mvgx_ba::intr_param_count(m) >= 0, MVGX_ERR_UNSUPPORTED, "%s: problem %u: camera model %d is not supported", __func__, p, m);
+    n_max = std::max(n_max, (uint32_t)n);
+  }
+  if (stats) memset(stats, 0, sizeof(*stats));
+  for (uint32_t p = 0; p < n_problems; ++p) { out_ok[p] = 0; out_error_max[p] = 0.0; out_min_nfa[p] = 0.0; }
+  for (uint32_t p = 0; p <= n_problems; ++p) out_inlier_start[p] = 0;
+  if (!n_problems) return MVGX_OK;
+  const uint64_t base = start[0], n_total = start[n_problems] - base;
+  MVGX_REQUIRE(n_total == 0 || (x2d && X3d && out_inliers), MVGX_ERR_ARG, "%s: NULL correspondence arrays", __func__);
+
+  // problems that reach the loop (n > 3), the largest first; the two storage forms
+  const uint32_t lds_bound = opt->global_above ? std::min(opt->global_above, kResLdsMaxN) : kResLdsMaxN;
+  std::vector<uint32_t> in_lds, in_global;
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    const uint64_t n = start[p + 1] - start[p];
+    if (n > 3) (n <= lds_bound ? in_lds : in_global).push_back(p);
+  }
+  const auto by_n = [&](uint32_t a, uint32_t b) { const uint64_t na = start[a + 1] - start[a], nb = start[b + 1] - start[b]; return na != nb ? na > nb : a < b; };
+  std::sort(in_lds.begin(), in_lds.end(), by_n);
+  std::sort(in_global.begin(), in_global.end(), by_n);
+  int rc;
+  if (in_lds.empty() && in_global.empty()) return MVGX_OK;
+  if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
+
+  // one page-locked staging buffer: problems | launch lists | log10 table | generator state
+  const size_t n_lists = in_lds.size() + in_global.size();
+  const size_t prob_words = (size_t)n_problems * sizeof(ResProblem) / 4, l10_n = (size_t)n_max + 2;
+  mvgx::PinnedBuf<uint64_t> stage;
+  const size_t stage_words = prob_words + n_lists + l10_n + kMtN;
+  if ((rc = stage.ensure((stage_words + 1) / 2))) return rc;
+  ResProblem* const hp = reinterpret_cast<ResProblem*>(stage.p);
+  uint32_t* const h_lists = reinterpret_cast<uint32_t*>(stage.p) + prob_words;
+  float* const h_l10 = reinterpret_cast<float*>(h_lists + n_lists);
+  uint32_t* const h_mt = reinterpret_cast<uint32_t*>(h_l10 + l10_n);
+  size_t scratch_bytes = 0;
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    ResProblem& g = hp[p];
+    const uint32_t n = (uint32_t)(start[p + 1] - start[p]);
+    g.start = start[p] - base; g.n = n; g.model = (uint32_t)intr_model[p]; g.scratch = 0;
+    memcpy(g.intr, intrinsics + 8 * (size_t)p, sizeof(g.intr));
+    // imagePlane_toCameraPlaneError(1): 1 / focal (pinhole family), 1 / max(w, h) (spherical)
+    g.n1 = intr_model[p] == mvgx_ba::kCamSpherical ? 1.0 / std::max(g.intr[0], g.intr[1]) : 1.0 / g.intr[0];
+    g.loge0 = n > 3 ? std::log10(4.0 * (double)(n - 3)) : 0.0;   // MAX_MODELS = 4, MINIMUM_SAMPLES = 3
+  }
+  for (uint32_t p : in_global) { hp[p].scratch = scratch_bytes; scratch_bytes += res_scratch_bytes(hp[p].n); }
+  if (!in_lds.empty()) memcpy(h_lists, in_lds.data(), in_lds.size() * 4);
+  if (!in_global.empty()) memcpy(h_lists + in_lds.size(), in_global.data(), in_global.size() * 4);
+  for (size_t i = 0; i < l10_n; ++i) h_l10[i] = (float)::log10((double)static_cast<float>(i));
+  h_mt[0] = 5489u;   // std::mt19937::default_seed
+  for (int i = 1; i < kMtN; ++i) h_mt[i] = 1812433253u * (h_mt[i - 1] ^ (h_mt[i - 1] >> 30)) + (uint32_t)i;
+
+  mvgx::DevBuf<uint64_t> d_stage;   // (before the stream guard: drained first, freed after)
+  mvgx::DevBuf<double> d_x2d, d_X, d_bear;
+  mvgx::DevBuf<unsigned char> d_scratch;
+  mvgx::DevBuf<ResResult> d_res;
+  mvgx::DevBuf<uint32_t> d_inl, d_trace;
+  mvgx::PinnedBuf<ResResult> h_res;
+  hipStream_t stream = nullptr;
+  if ((rc = mvgx::acquire_stream(&stream))) return rc;
+  int stream_device = 0;
+  MVGX_HIP(hipGetDevice(&stream_device));
+  mvgx::StreamGuard sg{stream_device, stream};
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  MVGX_HIP(hipEventCreate(&e0));
+  MVGX_HIP(hipEventCreate(&e1));
+  mvgx::EventGuard eg{e0, e1};
+  if ((rc = d_stage.ensure((stage_words + 1) / 2)) || (rc = d_x2d.ensure(2 * n_total)) || (rc = d_X.ensure(3 * n_total)) || (rc = d_bear.ensure(3 * n_total)) ||
+      (rc = d_scratch.ensure(std::max<size_t>(scratch_bytes, 1))) || (rc = d_res.ensure(n_problems)) || (rc = d_inl.ensure(n_total)) || (rc = h_res.ensure(n_problems)))
+    return rc;
+  MVGX_HIP(hipMemcpyAsync(d_stage.p, stage.p, (stage_words + 1) / 2 * 8, hipMemcpyHostToDevice, stream));
+  MVGX_HIP(hipMemcpyAsync(d_x2d.p, x2d + 2 * base, 2 * n_total * sizeof(double), hipMemcpyHostToDevice, stream));
+  MVGX_HIP(hipMemcpyAsync(d_X.p, X3d + 3 * base, 3 * n_total * sizeof(double), hipMemcpyHostToDevice, stream));
+  MVGX_HIP(hipMemsetAsync(d_res.p, 0, (size_t)n_problems * sizeof(ResResult), stream));
+  uint32_t* const host_trace = g_res_trace;   // (one call only)
+  const uint32_t trace_events = host_trace ? g_res_trace_events : 0;
+  g_res_trace = nullptr;
+  const size_t trace_words = (size_t)n_problems * res_trace_words(trace_events);
+  if (host_trace) {
+    if ((rc = d_trace.ensure(trace_words))) return rc;
+    MVGX_HIP(hipMemsetAsync(d_trace.p, 0, trace_words * sizeof(uint32_t), stream));
+  }
+  uint32_t* const p_trace = host_trace ? d_trace.p : nullptr;
+
+  // (launch arguments are plain pointers and counts: the test-suite's emulation captures them by value)
+  const ResProblem* const p_prob = reinterpret_cast<const ResProblem*>(d_stage.p);
+  const uint32_t* const p_lists = reinterpret_cast<const uint32_t*>(d_stage.p) + prob_words;
+  const float* const p_l10 = reinterpret_cast<const float*>(p_lists + n_lists);
+  const uint32_t* const p_mt = reinterpret_cast<const uint32_t*>(p_l10 + l10_n);
+  const double *p_x2d = d_x2d.p, *p_X = d_X.p;
+  double* const p_bear = d_bear.p;
+  MVGX_HIP(hipEventRecord(e0, stream));
+  hipLaunchKernelGGL(resection_bearing_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, stream, p_prob, n_problems, n_total, p_x2d, p_bear);
+  MVGX_HIP(hipGetLastError());
+  if (!in_lds.empty()) {
+    const uint32_t n_lds_max = hp[in_lds[0]].n;
+    if ((rc = res_launch<false>((uint32_t)in_lds.size(), res_lds_bytes(n_lds_max), stream, p_prob, p_lists, p_x2d, p_X, p_bear, p_l10, p_mt, opt->max_iteration,
+                                opt->solver, opt->waves_ahead, n_lds_max, d_scratch.p, d_res.p, d_inl.p, p_trace, trace_events)))
+      return rc;
+  }
+  if (!in_global.empty()) {
+    if ((rc = res_launch<true>((uint32_t)in_global.size(), res_lds_bytes(0), stream, p_prob, p_lists + in_lds.size(), p_x2d, p_X, p_bear, p_l10, p_mt,
+                               opt->max_iteration, opt->solver, opt->waves_ahead, 0, d_scratch.p, d_res.p, d_inl.p, p_trace, trace_events)))
+      return rc;
+  }
+  MVGX_HIP(hipEventRecord(e1, stream));
+  MVGX_HIP(hipMemcpyAsync(h_res.p, d_res.p, (size_t)n_problems * sizeof(ResResult), hipMemcpyDeviceToHost, stream));
+  // the inlier lists come back in place (one list per problem at its start), then are packed
+  std::vector<uint32_t> inl(n_total);
+  MVGX_HIP(hipMemcpyAsync(inl.data(), d_inl.p, n_total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  if (host_trace) MVGX_HIP(hipMemcpyAsync(host_trace, d_trace.p, trace_words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  MVGX_HIP(hipStreamSynchronize(stream));
+
+  uint64_t at = 0, iterations = 0, n_models = 0;
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    out_inlier_start[p] = at;
+    const ResResult& r = h_res.p[p];
+    if (hp[p].n <= 3) continue;   // ACRANSAC's early return of (0, 0): nothing else is written
+    iterations += r.n_iterations; n_models += r.n_models;
+    out_min_nfa[p] = r.min_nfa;
+    const double n1 = hp[p].n1;
+    out_error_max[p] = r.n_inliers ? std::sqrt(r.error_max) / n1 : r.error_max;   // unormalizeError
+    if (r.n_inliers) memcpy(out_inliers + at, inl.data() + hp[p].start, (size_t)r.n_inliers * sizeof(uint32_t));
+    at += r.n_inliers;
+    if ((double)r.n_inliers > 2.5 * 3) {
+      double K[9], R[9], t[3];
+      res_krt_from_p(r.P, K, R, t);
+      double* const pose = out_pose + 15 * (size_t)p;
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) pose[4 * i + j] = R[3 * i + j];
+        pose[4 * i + 3] = t[i];
+        pose[12 + i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);   // C = -R^T t
+      }
+      memcpy(out_P + 12 * (size_t)p, r.P, 12 * sizeof(double));
+      out_ok[p] = 1;
+    }
+  }
+  out_inlier_start[n_problems] = at;
+  if (stats) {
+    float kernel_ms = 0.f;
+    (void)hipEventElapsedTime(&kernel_ms, e0, e1);
+    stats->n_problems = n_problems; stats->n_iterations = iterations; stats->n_models = n_models; stats->kernel_ms = kernel_ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(clock::now() - t_begin).count();
+  }
+  return MVGX_OK;
+}
+
+// Test hook (not declared in include/mvgx.h): the NEXT mvgx_resection_localize call of this process leaves in `out`, per problem,
+// 1 + 10 * events words: the number of iterations that found a better model, then per such iteration (the first `events` of them)
+// iteration | k | the first 8 indices of its sorted list (0xffffffff beyond k). The order of a sample's own three points at the head of
+// that list is rounding noise ("Resection"); with it the tests' restatement follows the device's sample sequence.
+int mvgx_resection_debug_trace(uint32_t* out, uint32_t events) {
+  g_res_trace = out;
+  g_res_trace_events = out ? events : 0;
+  return MVGX_OK;
+}
+
+// Test hook (not declared in include/mvgx.h): the minimal solvers alone, one lane per sample. bearings, X: n_samples x 3 x 3 doubles (three
+// vectors per sample); Rt_out: n_samples x 4 x 12 ([R | t] row-major, zeros beyond n_out[i]); n_out: n_samples
+int mvgx_resection_debug_p3p(int solver, const double* bearings, const double* X, uint32_t n_samples, double* Rt_out, int* n_out) {
+  MVGX_REQUIRE(bearings && X && Rt_out && n_out, MVGX_ERR_ARG, "%s: NULL argument", __func__);
+  MVGX_REQUIRE(solver == kResSolverDing || solver == kResSolverNordberg, MVGX_ERR_UNSUPPORTED, "%s: solver %d has no device path", __func__, solver);
+  if (!n_samples) return MVGX_OK;
+  int rc = mvgx::select_device(-1);
+  if (rc) return rc;
+  mvgx::DevBuf<double> db, dX, dR;
+  mvgx::DevBuf<int> dn;
+  if ((rc = db.ensure(9 * (size_t)n_samples)) || (rc = dX.ensure(9 * (size_t)n_samples)) || (rc = dR.ensure(48 * (size_t)n_samples)) || (rc = dn.ensure(n_samples))) return rc;
+  MVGX_HIP(hipMemcpy(db.p, bearings, 9 * (size_t)n_samples * sizeof(double), hipMemcpyHostToDevice));
+  MVGX_HIP(hipMemcpy(dX.p, X, 9 * (size_t)n_samples * sizeof(double), hipMemcpyHostToDevice));
+  MVGX_HIP(hipMemset(dR.p, 0, 48 * (size_t)n_samples * sizeof(double)));
+  MVGX_HIP(hipMemset(dn.p, 0, (size_t)n_samples * sizeof(int)));
+  {
+    const double *pb = db.p, *pX = dX.p;
+    double* const pR = dR.p;
+    int* const pn = dn.p;
+    hipLaunchKernelGGL(resection_p3p_debug_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, nullptr, solver, pb, pX, n_samples, pR, pn);
+  }
+  MVGX_HIP(hipGetLastError());
+  MVGX_HIP(hipStreamSynchronize(nullptr));
+  MVGX_HIP(hipMemcpy(Rt_out, dR.p, 48 * (size_t)n_samples * sizeof(double), hipMemcpyDeviceToHost));
+  MVGX_HIP(hipMemcpy(n_out, dn.p, (size_t)n_samples * sizeof(int), hipMemcpyDeviceToHost));
+  return MVGX_OK;
+}
+
+}  // extern "C"
