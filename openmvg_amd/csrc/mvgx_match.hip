@@ -31,8 +31,9 @@
 //            database role needs); qtnorm: |a'|^2 per slot of it. A query slot of that kernel's best[] / cd[] is the original row.
 //
 // What ships (option "variant" 4, the default): a FILTER launch and a VERIFY launch per batch of image pairs.
-//   l2_filter16_kernel   one workgroup = 4 waves, each wave 128 queries (4 dense query tiles, register-resident MFMA B operands) of any
-//                        pair whose database image I the workgroup streams through a double-buffered 33 KiB LDS window. On
+//   l2_filter16_kernel   one workgroup = 4 waves, each wave 8 blocks of 16 queries (register-resident MFMA B operands): consecutive blocks of
+//                        the dense query tiles of the pairs whose database image I the workgroup streams through a double-buffered
+//                        33 KiB LDS window, running on from one query image into the next (mvgx_match_batch.h). On
 //                        v_mfma_i32_16x16x64_i8, one v_max3 per two distances: running maxima of two partitions of the rows bound the
 //                        second-nearest distance from below, so most queries are rejected exactly and the rest leave as candidates
 //                        (see l2_filter_kernel for the argument, l2_filter16_kernel for the shape).
@@ -78,7 +79,9 @@ constexpr int kWinRows = kWinTiles * kTileRows;  // 256 -> 8 index bits in the p
 constexpr int kWaves = 4;                     // waves per workgroup
 constexpr int kNQ = 4;                        // query tiles per wave (register-resident)
 constexpr int kBlockQTiles = kWaves * kNQ;    // 16 tiles = 512 queries per workgroup
-constexpr int kRecQuads = 1 + kWaves;         // uint4 words of a wave-packed record (MatchParams::work8): the shared part + one part per wave
+using mvgx_records::kRecQuads;                // uint4 words of a block-granular record (MatchParams::work8): the shared part + two per wave
+static_assert(mvgx_records::kRecWaves == kWaves && mvgx_records::kUnitBlocks == 2 * kNQ && mvgx_records::kBlockRows * 2 == kTileRows,
+              "mvgx_match_batch.h builds the records for this kernel shape");
 constexpr int kStageBytes = kWinTiles * kTileBytes + kWinTiles * kTileRows * 4;  // 32768 + 1024
 constexpr int kRPad = INT_MIN + 512;
 constexpr int kCPad = -(1 << 27);             // accumulator init of pad slots (real values are > -2^22)
@@ -104,10 +107,10 @@ struct MatchParams {
   const uint2* pairs;              // batch-local (I, J)
   const uint2* work;               // (batch-local pair index, first query tile)
   const uint4* work8h;             // ... for l2_filter16h_kernel: one record per 8 query tiles (256 query slots)
-  const uint4* work8;              // wave-packed records of l2_filter16_kernel and its verify launch, kRecQuads words each: (tileI0, ntI, 0, 0) shared by
-                                   // the workgroup, then per wave (pair, tileJ0, first query tile, nJ) - a unit of kNQ DENSE query tiles (qtiles: tileJ0
-                                   // is J's first one, nJ its rows) of any pair with this database image; nJ = 0: an empty wave (loads and barriers
-                                   // as the others, stores nothing)
+  const uint4* work8;              // block-granular records of l2_filter16_kernel and its verify launch, kRecQuads words each: (tileI0, ntI, 0, 0) shared by
+                                   // the workgroup, then per wave two segments of a unit of 8 blocks of 16 query rows, (pair A, tileJ0 of JA, first block in
+                                   // JA, nJA) and (pair B, tileJ0 of JB, blocks of A, nJB) - consecutive blocks of the pairs with this database image, B from
+                                   // its block 0 (mvgx_match_batch.h); nJ = 0: an absent segment (loads and barriers as the others, stores nothing)
   uint32_t n_work;                 // entries of the list the first kernel of the batch walks (= its grid; no kernel reads it)
   uint32_t* best;                  // [batch pairs][qstride], indexed by query SLOT (l2_filter16_kernel and after it: dense slot = row): original index in I or kNoMatch
   int2* cd;                        // filter -> verify: (d0, upper bound of d1) of a candidate query slot
@@ -926,7 +929,16 @@ __device__ __forceinline__ void fold_window16(const int (&TW)[4], int (&TP)[4], 
   Q1 = max(Q1, v);
 }
 
-// MVGX_FINISH16 with the same two-instruction top-2 over the lane's four classes (p2 <= p1 throughout, as in fold_window16)
+// Block n (0..7) of a wave's unit (MatchParams::work8, mvgx_match_batch.h): segment A below the split, segment B from it on. With wave-uniform
+// segments and a constant n everything here is scalar; the verify stage calls it with a lane's own block.
+struct UnitBlock { uint32_t pair, tileJ0, row0, nJ; };   // batch-local pair, J's first dense tile, first row of the block in J, rows of J
+__device__ __forceinline__ UnitBlock unit_block(const uint4& a, const uint4& b, uint32_t n) {
+  const bool inA = n < b.z;
+  return UnitBlock{inA ? a.x : b.x, inA ? a.y : b.y, (inA ? a.z + n : n - b.z) * 16u, inA ? a.w : b.w};
+}
+
+// MVGX_FINISH16 with the same two-instruction top-2 over the lane's four classes (p2 <= p1 throughout, as in fold_window16), for query
+// block N of the wave's unit: lane l < 16 owns row ub.row0 + l of the block's own pair
 #define MVGX_FINISH16_MED3(N, INB, VALID)                                                                                                 \
   {                                                                                                                                       \
     int p1 = kNegInit, p2 = kNegInit, pc = 0;   /* best / second-best P-class of this lane */                                             \
@@ -947,12 +959,13 @@ __device__ __forceinline__ void fold_window16(const int (&TW)[4], int (&TP)[4], 
       code = mine ? code : oc;                                                                                                            \
       W1 = mine ? W1 : o1;                                                                                                                \
     }                                                                                                                                     \
-    const uint32_t q = (qt0 + (uint32_t)((N) >> 1)) * kTileRows + (uint32_t)((N) & 1) * 16 + (uint32_t)(lane & 15);                       \
+    const UnitBlock ub = unit_block(wa, wb, (uint32_t)(N));   /* wave-uniform: the block's segment says pair, rows and nJ */               \
+    const uint32_t q = ub.row0 + (uint32_t)(lane & 15);                                                                                   \
     if (lane < 16 && (INB)) {                                                                                                             \
       const int nq = qn[N];                                                                                                               \
       const int d0 = nq - W1, d1ub = nq - V2;                                                                                             \
       const bool cand = (VALID) && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));                                    \
-      const size_t o = (size_t)pair * p.qstride + q;                                                                                      \
+      const size_t o = (size_t)ub.pair * p.qstride + q;                                                                                   \
       p.best[o] = cand ? (uint32_t)code : kNoMatch;                                                                                       \
       if (cand) p.cd[o] = make_int2(d0, d1ub);                                                                                            \
     }                                                                                                                                     \
@@ -970,35 +983,37 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   // of data. Everything the staging loads and the barriers depend on (tileI0, ntI) is in the shared part: the four waves may serve four
   // different pairs, but they stream the same database image in step.
   const uint4* rec = p.work8 + (size_t)kRecQuads * w;
-  const uint4 wsh = rec[0], wun = rec[1 + wave];
+  const uint4 wsh = rec[0], wa = rec[1 + 2 * wave], wb = rec[2 + 2 * wave];   // segments A and B of this wave's unit, wave-uniform
   const uint32_t tileI0 = wsh.x;
   const int ntI = (int)wsh.y;
-  const uint32_t pair = wun.x, tileJ0 = wun.y, qt0 = wun.z;
-  const uint32_t nJ = wun.w;   // rows of the query image; 0: an empty wave of a record that was closed early
   const int nwin = (ntI + kWinTiles - 1) / kWinTiles;
 
   // byte offset of this lane's 16-byte chunk inside a tile, block 0, k-step 0 (see above)
   const int lane_chunk = ((lane >> 5) * 64 + ((lane >> 4) & 1) * 32 + (lane & 15)) * 16;
   v4i b[kNB16][2];
   {
-    // the query fragments come from the dense set (slot = original row): a unit covers 128 rows of J, not 64 of each norm parity
-    const int8_t* qsrc = p.qtiles + (size_t)(tileJ0 + qt0) * kTileBytes + lane_chunk;
+    // the query fragments come from the dense set (slot = original row), block by block: block n of the unit is a block of JA below the
+    // split and of JB from it on (a scalar base per block, the lane's chunk on top)
 #pragma unroll
-    for (int n = 0; n < kNB16; ++n)
+    for (int n = 0; n < kNB16; ++n) {
+      const UnitBlock ub = unit_block(wa, wb, (uint32_t)n);
+      const int8_t* qsrc = p.qtiles + ((size_t)(ub.tileJ0 + (ub.row0 >> 5)) * kTileBytes + ((ub.row0 >> 4) & 1u) * 256u) + lane_chunk;
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) b[n][ks] = *reinterpret_cast<const v4i*>(qsrc + (n >> 1) * kTileBytes + (n & 1) * 256 + ks * 2048);
+      for (int ks = 0; ks < 2; ++ks) b[n][ks] = *reinterpret_cast<const v4i*>(qsrc + ks * 2048);
+    }
   }
 
   const int8_t* gI = p.tiles + (size_t)tileI0 * kTileBytes;
   const int* gC = p.cinit + (size_t)tileI0 * kTileRows;
 
   // squared norm of the lane's eight query slots: fetched now, used after the last window (they used to be loaded there, one more trip
-  // to memory at the end of every workgroup). A dense slot is valid iff it is below nJ: no table says so.
+  // to memory at the end of every workgroup). A dense slot is valid iff it is below the nJ of its block's segment: no table says so.
   int qn[kNB16];
 #pragma unroll
   for (int n = 0; n < kNB16; ++n) {
-    const uint32_t q = (qt0 + (uint32_t)(n >> 1)) * kTileRows + (uint32_t)(n & 1) * 16 + (uint32_t)(lane & 15);
-    qn[n] = (lane < 16 && q < nJ) ? p.qtnorm[(size_t)tileJ0 * kTileRows + q] : 0;
+    const UnitBlock ub = unit_block(wa, wb, (uint32_t)n);
+    const uint32_t q = ub.row0 + (uint32_t)(lane & 15);
+    qn[n] = (lane < 16 && q < ub.nJ) ? p.qtnorm[(size_t)ub.tileJ0 * kTileRows + q] : 0;
   }
 
   int TP[kNB16][4];                         // P-class maxima of the run
@@ -1106,7 +1121,7 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   }
 
 #pragma unroll
-  for (int n = 0; n < kNB16; ++n) MVGX_FINISH16_MED3(n, q < nJ, true)   // a dense slot is a row of J: every one below nJ holds a row
+  for (int n = 0; n < kNB16; ++n) MVGX_FINISH16_MED3(n, q < ub.nJ, true)   // a dense slot is a row of its segment's J: every one below nJ holds a row
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1229,8 +1244,9 @@ __global__ __launch_bounds__(256, 3) void l2_filter16h_kernel(MatchParams p) {
 
 // ------------------------------------------------------------------------------------------------
 // l2_verify (variant 4, stage 2): finishes the candidates of the filter. Same work items as the filter: kWaveUnits = false, a
-// workgroup owns 512 query slots of one pair (p.work); kWaveUnits = true (after l2_filter16_kernel), each WAVE owns the 128 query
-// slots of its own part of a wave-packed record (p.work8) - the waves never shared anything here, each adds to count[] by itself.
+// workgroup owns 512 query slots of one pair (p.work); kWaveUnits = true (after l2_filter16_kernel), each WAVE owns the 8 blocks of 16
+// query rows of its own unit of a block-granular record (p.work8), which may belong to two pairs - the waves never shared anything here,
+// each adds to count[] of its one or two pairs by itself.
 // Either way exactly the slots of best[] that the filter launch before it wrote are read: the two batch slots reuse best[], and a
 // stale word is a valid candidate code of some other pair. 16 lanes per candidate recompute the exact distances of the 16 slots of its
 // (P-class, window, half) cell with v_dot4_i32_i8 on the tile bytes, take the cell's best (must equal d0) and its
@@ -1258,15 +1274,20 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   uint32_t pair, qt0, I, tileI0, tileJ0, qend;   // qend: query slots of J in the layout of the filter that ran
-  const uint8_t* rowsJ = nullptr;                // kWaveUnits: J's original rows (query slot = row)
+  // kWaveUnits: the two segments of the wave's unit and the original rows of their query images (query slot = row). A lane's block is
+  // part * 4 + lane / 16; pair, rows and nJ are those of the block's segment.
+  uint4 wa = make_uint4(0, 0, 0, 0), wb = wa;
+  const uint8_t *rowsJA = nullptr, *rowsJB = nullptr;
   if constexpr (kWaveUnits) {
     const uint4* rec = p.work8 + (size_t)kRecQuads * blockIdx.x;
-    const uint4 wun = rec[1 + __builtin_amdgcn_readfirstlane(wave)];   // wave-uniform: the unit stays in scalar registers
-    pair = wun.x; tileJ0 = wun.y; qt0 = wun.z; qend = wun.w;   // an empty wave (nJ = 0) reads no slot below
+    const int wu = __builtin_amdgcn_readfirstlane(wave);   // wave-uniform: the unit stays in scalar registers
+    wa = rec[1 + 2 * wu]; wb = rec[2 + 2 * wu];           // an absent segment (nJ = 0) reads no slot below
     tileI0 = rec[0].x;
-    const uint2 ij = p.pairs[pair];
-    I = ij.x;
-    rowsJ = p.rows_u8 + p.img_row_off[ij.y] * kDim;
+    const uint2 ijA = p.pairs[wa.x], ijB = p.pairs[wb.x];  // both pairs of a unit have the record's database image
+    I = ijA.x;
+    rowsJA = p.rows_u8 + p.img_row_off[ijA.y] * kDim;
+    rowsJB = p.rows_u8 + p.img_row_off[ijB.y] * kDim;
+    pair = 0; qt0 = 0; tileJ0 = 0; qend = 0;
   } else {
     const uint2 wk = p.work[blockIdx.x];
     const uint2 ij = p.pairs[wk.x];
@@ -1277,12 +1298,16 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
   }
   const uint32_t nEvenI = p.img_neven[I], nOddI = p.img_n[I] - nEvenI;
   const int l16 = lane & 15, sub = lane >> 4;
-  uint32_t accepted = 0;
+  uint32_t accepted = 0, acceptedB = 0;   // of the work item's pair, or of segment A's / of segment B's
   for (int part = 0; part < 2; ++part) {
     const uint32_t q0 = qt0 * kTileRows + (uint32_t)part * 64;
-    const uint32_t q = q0 + lane;
-    const bool inb = q < qend;
-    const uint32_t code = inb ? p.best[(size_t)pair * p.qstride + q] : kNoMatch;
+    uint32_t q = q0 + lane, qpair = pair;
+    bool inb = q < qend;
+    if constexpr (kWaveUnits) {
+      const UnitBlock ub = unit_block(wa, wb, (uint32_t)(part * 4 + sub));
+      q = ub.row0 + (uint32_t)l16; qpair = ub.pair; inb = q < ub.nJ;
+    }
+    const uint32_t code = inb ? p.best[(size_t)qpair * p.qstride + q] : kNoMatch;
     unsigned long long todo = __ballot(code != kNoMatch);
     while (todo) {
       // the sub-th pending candidate of this round goes to lane group `sub`
@@ -1292,7 +1317,15 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
       const int src = active ? __builtin_ctzll(m) : 0;
       for (int i = 0; i < 4; ++i) todo &= todo - 1;
       const uint32_t cc = (uint32_t)__shfl((int)code, src);
-      const uint32_t qs = q0 + (uint32_t)src;                      // query slot
+      uint32_t qs = q0 + (uint32_t)src, cpair = pair;              // query slot and pair of the candidate
+      bool inA = true;
+      const uint8_t* rowsJ = nullptr;
+      if constexpr (kWaveUnits) {                                  // ... of the block of lane src
+        const uint32_t cb = (uint32_t)(part * 4 + (src >> 4));
+        const UnitBlock ub = unit_block(wa, wb, cb);
+        qs = ub.row0 + (uint32_t)(src & 15); cpair = ub.pair; inA = cb < wb.z;
+        rowsJ = inA ? rowsJA : rowsJB;
+      }
       const int s1 = cc & 7, hw = (cc >> 3) & 1, g1 = (int)(cc >> 4);
       // Row rho (0..15) of the cell sits in tile g1*8 + (rho >> 1), in-tile row slot_row(2*s1 + (rho & 1), hw); rows
       // 2c and 2c+1 are adjacent slots = 256 contiguous bytes of rows_slot. Load c (0..7) of the group therefore reads
@@ -1302,7 +1335,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
       const int mrow = slot_row(2 * s1 + rsel, hw);
       const size_t slot0 = (size_t)tileI0 * kTileRows + (active ? (size_t)g1 * kWinTiles * kTileRows + mrow : 0);
       const size_t slotQ = (size_t)tileJ0 * kTileRows + (active ? qs : 0);
-      const size_t o = (size_t)pair * p.qstride + (active ? qs : 0);
+      const size_t o = (size_t)cpair * p.qstride + (active ? qs : 0);
       // the row this lane finally owns: rho = 2 * (l16 & 7) + (l16 >> 3)  (a permutation of 0..15)
       const uint32_t tt = (uint32_t)g1 * kWinTiles + (uint32_t)piece;
       const size_t slotI = active ? slot0 + (size_t)piece * kTileRows : slot0;
@@ -1356,10 +1389,16 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
         ok = __int2float_rn(dbest) < __fmul_rn(p.ratio_sq, __int2float_rn(d1));
         p.best[o] = ok ? p.perm[slotI] : kNoMatch;
       }
-      accepted += (uint32_t)__popcll(__ballot(ok));
+      accepted += (uint32_t)__popcll(__ballot(ok && inA));
+      if constexpr (kWaveUnits) acceptedB += (uint32_t)__popcll(__ballot(ok && !inA));
     }
   }
-  if (lane == 0 && accepted) atomicAdd(&p.count[pair], accepted);
+  if constexpr (kWaveUnits) {   // up to two pairs per wave
+    if (lane == 0 && accepted) atomicAdd(&p.count[wa.x], accepted);
+    if (lane == 0 && acceptedB) atomicAdd(&p.count[wb.x], acceptedB);
+  } else {
+    if (lane == 0 && accepted) atomicAdd(&p.count[pair], accepted);
+  }
 }
 
 // statistics (profile mode only): candidates the filter hands to the verify stage. One atomic per 16 K slots — a single
@@ -1383,18 +1422,20 @@ __global__ __launch_bounds__(256) void count_candidates_kernel(const uint32_t* _
   if (threadIdx.x == 0 && s_sum) atomicAdd(counter, s_sum);
 }
 
-// ... after l2_filter16_kernel: the same count over the wave units of the records, i.e. over exactly the slots that launch wrote (the
+// ... after l2_filter16_kernel: the same count over the blocks of the units of the records, i.e. over exactly the slots that launch wrote (the
 // sweep above would also count what an earlier batch left in the tiles between 4 * ceil(ntJ / 4) and ntJpad). One atomic per record.
 __global__ __launch_bounds__(256) void count_candidates_units_kernel(MatchParams p, uint32_t* __restrict__ counter) {
   __shared__ uint32_t s_sum;
   if (threadIdx.x == 0) s_sum = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint4 wun = p.work8[(size_t)kRecQuads * blockIdx.x + 1 + wave];
+  const uint4* rec = p.work8 + (size_t)kRecQuads * blockIdx.x;
+  const uint4 wa = rec[1 + 2 * wave], wb = rec[2 + 2 * wave];
   uint32_t c = 0;
   for (int part = 0; part < 2; ++part) {
-    const uint32_t q = wun.z * kTileRows + (uint32_t)part * 64 + (uint32_t)lane;
-    const bool cand = q < wun.w && p.best[(size_t)wun.x * p.qstride + q] != kNoMatch;
+    const UnitBlock ub = unit_block(wa, wb, (uint32_t)(part * 4 + (lane >> 4)));
+    const uint32_t q = ub.row0 + (uint32_t)(lane & 15);
+    const bool cand = q < ub.nJ && p.best[(size_t)ub.pair * p.qstride + q] != kNoMatch;
     c += (uint32_t)__popcll(__ballot(cand));
   }
   if (lane == 0 && c) atomicAdd(&s_sum, c);
@@ -1578,7 +1619,7 @@ KernelForm resolve_form(const mvgx_match_ctx* c) { return form_for(c->variant, c
 // The three work lists of a batch of nb pairs ij[2 k], ij[2 k + 1]; each builder returns the entries it wrote. A pair with nJ > 0 and nI >= 2
 // has at least one entry in every list, any other pair none:
 // matcher_brute_force.hpp:108-113: NN(=2) > rows -> no result; Matcher_Regions.cpp:65-69,85-90: empty regions skipped
-bool pair_has_work(const mvgx_match_ctx* c, uint32_t I, uint32_t J) { return c->h_n[I] >= 2 && c->h_n[J] != 0; }
+bool pair_has_work(const mvgx_match_ctx* c, uint32_t I, uint32_t J) { return mvgx_records::pair_has_work(c->h_n.data(), I, J); }
 
 // MatchParams::work: (batch-local pair, first query tile) per kBlockQTiles occupied parity tiles of J
 uint32_t build_items16(const mvgx_match_ctx* c, const uint32_t* ij, uint32_t nb, uint2* out) {
@@ -1604,29 +1645,11 @@ uint32_t build_items8h(const mvgx_match_ctx* c, const uint32_t* ij, uint32_t nb,
   }
   return n;
 }
-// MatchParams::work8: units of kNQ DENSE query tiles (ceil(nJ / 32) of them in J, never more than its parity tiles), one per wave, packed
-// four to a workgroup across the pairs that share I - a pair costs ceil(dense tiles / 4) waves, and no more of them than nJ rows need
-// whatever their norm parities are. A record holds everything its workgroup needs to start (no walk work -> pairs -> three per-image
-// tables). It is closed when it is full, when I changes and at the end of the batch; its unused waves are empty units (nJ = 0: nothing
-// stored) whose query pointer is aimed at I's own first dense tiles. The units of a pair are consecutive and share I, so they leave at most
-// one record part-filled per pair.
+// MatchParams::work8: mvgx_records::build_block_records (mvgx_match_batch.h) over this context's image tables - units of 8 blocks of 16
+// query rows, packed across the pairs that share I, so that a run of pairs costs ceil(blocks of the run / 8) waves
 uint32_t build_records(const mvgx_match_ctx* c, const uint32_t* ij, uint32_t nb, uint4* out) {
-  uint32_t n_rec = 0, rec_used = kWaves, rec_I = 0;   // records written; waves taken in the open one (kWaves: none is open) and its database image
-  for (uint32_t k = 0; k < nb; ++k) {
-    const uint32_t I = ij[2 * k], J = ij[2 * k + 1];
-    if (!pair_has_work(c, I, J)) continue;
-    const uint32_t ntJq = c->h_qtile_off[J + 1] - c->h_qtile_off[J];
-    for (uint32_t qt = 0; qt < ntJq; qt += kNQ) {
-      if (rec_used == kWaves || rec_I != I) {
-        uint4* r = out + (size_t)kRecQuads * n_rec++;
-        r[0] = make_uint4(c->h_tile_off[I], c->h_ntiles[I], 0, 0);
-        for (int w = 0; w < kWaves; ++w) r[1 + w] = make_uint4(0, c->h_qtile_off[I], 0, 0);
-        rec_used = 0; rec_I = I;
-      }
-      out[(size_t)kRecQuads * (n_rec - 1) + 1 + rec_used++] = make_uint4(k, c->h_qtile_off[J], qt, c->h_n[J]);
-    }
-  }
-  return n_rec;
+  const mvgx_records::ImageTables im{c->h_n.data(), c->h_tile_off.data(), c->h_ntiles.data(), c->h_qtile_off.data()};
+  return mvgx_records::build_block_records(im, ij, nb, reinterpret_cast<uint32_t*>(out));
 }
 
 // host list -> device, n elements (the device buffer exists even for an empty list)
@@ -1696,8 +1719,9 @@ int prep_regions(mvgx_match_ctx* c) {
   if ((rc = c->d_cinit.ensure(alloc_slots))) return rc;
   if ((rc = c->d_qnorm.ensure(alloc_slots))) return rc;
   if ((rc = c->d_perm.ensure(alloc_slots))) return rc;
-  // the dense query set: a wave unit reads kNQ tiles from a multiple of kNQ below ceil(n / 32), i.e. up to kNQ - 1 tiles past its image -
-  // into the next image's tiles or the zeroed slack after the last one (the results of those columns are not stored)
+  // the dense query set: the second segment of a wave's unit (or an absent one, aimed at I) reads up to 8 blocks = kNQ tiles from its image's
+  // first dense tile, i.e. up to kNQ - 1 tiles past a short image - into the next image's tiles or the zeroed slack after the last one (the
+  // results of those columns are not stored)
   const size_t total_qtiles = c->h_qtile_off[n_images];
   if ((rc = c->d_qtiles.ensure((total_qtiles + kTailTiles) * kTileBytes))) return rc;
   if ((rc = c->d_qtnorm.ensure((total_qtiles + kTailTiles) * kTileRows))) return rc;
