@@ -656,7 +656,7 @@ int mvgx_triangulate_tracks(int device,
  * of p at [out_inlier_start[p], out_inlier_start[p + 1]), indices within the problem in the reference's order (ascending residual);
  * room for start[n_problems] - start[0] entries. A problem of three or fewer correspondences: not ok, zeros, nothing else written.
  * MVGX_ERR_UNSUPPORTED: a solver other than the two P3P ones below, a finite error_max (the quantified NFA with the max-consensus early
- * exit), an unknown camera model. MVGX_ERR_ARG: NULL arrays, a start that decreases, more than 65 536 correspondences in one problem.
+ * exit: mvgx_resection_localize_bounded below), an unknown camera model. MVGX_ERR_ARG: NULL arrays, a start that decreases, more than 65 536 correspondences in one problem.
  * Parity: decisions, sample sequence and inlier order as the reference's, numbers to rounding ("Resection"); a model with a
  * non-finite entry is skipped. */
 #define MVGX_RESECTION_P3P_NORDBERG 3   /* resection::SolverType::P3P_NORDBERG_ECCV18 */
@@ -679,6 +679,22 @@ int mvgx_resection_localize(int device, uint32_t n_problems, const uint64_t* sta
                             double* out_P /* n_problems x 12 */, double* out_error_max, double* out_min_nfa,
                             uint64_t* out_inlier_start /* n_problems + 1 */, uint32_t* out_inliers,
                             mvgx_resection_stats* stats /* may be NULL */);
+/* The bounded form (no ABI bump: detect it by the symbol): SfM_Localizer::Localize with a finite error_max, as main_SfM_Localization -r
+ * and SfM_Localizer_Single_3DTrackObservation_Database::Localize call it. Arguments, options struct and outputs are those of
+ * mvgx_resection_localize; opt->error_max is the bound in pixels (Image_Localizer_Match_Data::error_max on entry) and must be finite and
+ * > 0 (MVGX_ERR_ARG otherwise: infinity is mvgx_resection_localize's form). ACRANSAC then (robust_estimator_ACRansac.hpp:205-256, :351-358,
+ * :375, :386-389, :402-413, :446-452) reads the NFA off a 20-bin histogram of the residuals below the bound - no sort -, starts as a
+ * max-consensus loop with the rejection sampler (rand_sampling.hpp:36-58), turns a-contrario at the first model with more than 2.5 * 3
+ * residuals inside the bound and gives up after 2 (max_iteration / 10) + 2 iterations if there is none. out_error_max: the threshold
+ * ACRANSAC found, as Localize writes it back (one of 19 steps of the bound). out_inliers: ASCENDING INDEX order in this form.
+ * Besides the skipped non-finite model: an adopted sampling pool of fewer than three entries ends the problem with its current result
+ * (the reference's sampler returns false there, unchecked, and a stale sample is evaluated again). */
+int mvgx_resection_localize_bounded(int device, uint32_t n_problems, const uint64_t* start /* n_problems + 1 */, const double* x2d, const double* X3d,
+                                    const int32_t* intr_model /* n_problems */, const double* intrinsics /* n_problems x MVGX_BA_MAX_INTR_PARAMS */,
+                                    const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose /* n_problems x 15 */,
+                                    double* out_P /* n_problems x 12 */, double* out_error_max, double* out_min_nfa,
+                                    uint64_t* out_inlier_start /* n_problems + 1 */, uint32_t* out_inliers,
+                                    mvgx_resection_stats* stats /* may be NULL */);
 
 #ifdef __cplusplus
 }

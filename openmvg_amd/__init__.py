@@ -3,7 +3,8 @@
   matching : brute-force L2 2-NN + Lowe ratio on 128-D uint8 descriptors  (openmvg_amd.matching)
   ba       : Levenberg-Marquardt bundle adjustment                         (openmvg_amd.ba)
   triangulation : blind / robust triangulation of the tracks of a scene    (openmvg_amd.triangulation)
-  resection     : robust resection of views (AC-RANSAC over P3P), batched   (openmvg_amd.resection)
+  resection     : robust resection of views (AC-RANSAC over P3P), batched   (openmvg_amd.resection: localize for an unbounded
+                  precision, localize_bounded for a finite error_max)
 
 All compute lives in openmvg_amd/lib/libmvgx_hip.so (hand-written HIP, C ABI in include/mvgx.h);
 the Python modules only mirror the reference's host interfaces. No CPU fallback exists.

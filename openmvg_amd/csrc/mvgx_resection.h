@@ -1,10 +1,14 @@
-// mvgx_resection.h - robust camera resection on the device: AC-RANSAC with the exhaustive NFA over a P3P solver, a batch of independent
-// problems per call (mvgx_resection_localize). Included at the end of mvgx_geofilter.hip: it uses that unit's std::mt19937, bounded draw,
-// logcombi and un-contracted mul_rn / add_rn, and ba_math.h for the camera models. What is restated (paths under src/openMVG of the reference):
+// mvgx_resection.h - robust camera resection on the device: AC-RANSAC over a P3P solver, a batch of independent problems per call, in
+// the reference's two forms: the exhaustive NFA of an unbounded precision (mvgx_resection_localize) and the quantified NFA with the
+// max-consensus warm-up of a bounded one (mvgx_resection_localize_bounded). Included at the end of mvgx_geofilter.hip: it uses that
+// unit's std::mt19937, bounded draw, logcombi, histogram scan and un-contracted mul_rn / add_rn, and ba_math.h for the camera models.
+// What is restated (paths under src/openMVG of the reference):
 //   sfm/pipelines/localization/SfM_Localizer.cpp:31-343          ACKernelAdaptorResection_Intrinsics, SfM_Localizer::Localize
 //   robust_estimation/robust_estimator_ACRansac.hpp:257-304      the exhaustive NFA of one model
-//   robust_estimation/robust_estimator_ACRansac.hpp:326-489      the a-contrario loop
+//   robust_estimation/robust_estimator_ACRansac.hpp:205-256      the quantified NFA of one model (third_party/histogram/histogram.hpp)
+//   robust_estimation/robust_estimator_ACRansac.hpp:326-489      the a-contrario loop, its warm-up and early exit
 //   robust_estimation/rand_sampling.hpp:71-100                   UniformSample on the pool (three Fisher-Yates swaps at its head)
+//   robust_estimation/rand_sampling.hpp:36-58                    UniformSample(3, nData, ...) of the warm-up (rejection)
 //   multiview/solver_resection_p3p_ding.cpp:33-325               P3PSolver_Ding
 //   multiview/solver_resection_p3p_nordberg.cpp:31-454           P3PSolver_Nordberg
 //   multiview/projection.cpp:40-132                              KRt_From_P (host)
@@ -674,6 +678,344 @@ __global__ __launch_bounds__(64 * kResWaves) void resection_acransac_kernel(cons
   }
 }
 
+// ---- the bounded form (mvgx_resection_localize_bounded): a finite precision ----
+// robust_estimator_ACRansac.hpp:205-256 (the NFA read off a 20-bin histogram), :351-358, :375, :386-389 (the warm-up's rejection sampler,
+// rand_sampling.hpp:36-58), :402-413 (max-consensus until a model has more than 2.5 x 3 residuals inside the bound), :446-452 (the early
+// exit). No sort: per model n residuals, 20 counters and, for a model that lowers minNFA, one list in index order. The mapping is the
+// loop's above - one workgroup per problem, one wave per iteration evaluated ahead - with two more kinds of event: the switch to the
+// a-contrario mode, and a list that was rebuilt but came out too short to count as a better model (:243-255).
+// Deliberate differences: a model with a non-finite entry is skipped (as above); an adopted pool of fewer than three entries stops the
+// problem with its current result (the reference's sampler returns false there, unchecked, and the stale sample is evaluated again).
+constexpr uint32_t kResBLdsMaxN = 8192;       // largest n whose four tables live in LDS (DESIGN.md derives it)
+constexpr int kResBVerdict = 32;              // doubles per wave: flags | nfa | threshold | unused | P[12] | models evaluated | list threshold | list P[12] | unused
+constexpr int kResBBetter = 1, kResBRebuilt = 2, kResBSwitched = 4;   // a verdict's flags
+struct ResBound {         // per problem, prepared on the host (glibc's log10)
+  double max_threshold, bins_by_interval;   // error_max^2 n1^2; 20 / max_threshold
+  double bin_value[kBins];                  // (max_threshold / 19) b: histogram.hpp:105-112, not the bins' edges
+  double logalpha_bin[kBins];               // logalpha0 + log10(bin_value + FLT_EPSILON)
+};
+// words of LDS: generator | its copy | verdicts | models | samples, swaps, counts | histograms | compaction counts (two sets) | best model | (LDS form) tables
+__host__ __device__ constexpr uint32_t resb_fixed_words() {
+  return 2 * kMtN + 2 * kResWaves * kResBVerdict + 2 * kResWaves * 48 + 8 * kResWaves + kResWaves * kBins + 2 * kResWaves + 24;
+}
+inline size_t resb_scratch_bytes(uint32_t n) { return ((size_t)4 * res_table_words(n) + 255) / 256 * 256; }
+inline uint32_t resb_lds_bytes(uint32_t n_lds_max) { return 4 * (resb_fixed_words() + (n_lds_max ? res_table_words(n_lds_max) : 0)); }
+
+struct ResRt { double m0, m1, m2, m3, m4, m5, m6, m7, m8, m9, m10, m11; };
+__device__ __forceinline__ ResRt res_rt_load(const double* __restrict__ M) { return {M[0], M[1], M[2], M[3], M[4], M[5], M[6], M[7], M[8], M[9], M[10], M[11]}; }
+// the residual of correspondence i under M: the expression of the loop above, term for term (every pass of the bounded form goes
+// through here, so a residual has the same bits wherever it is compared)
+__device__ __forceinline__ double res_error_of(const ResRt& M, int res_model, const double* __restrict__ intr, double n1norm, const double* __restrict__ pX,
+                                               const double2* __restrict__ px, uint32_t i) {
+  const double X = pX[3 * i], Y = pX[3 * i + 1], Z = pX[3 * i + 2];
+  const double pc[3] = {M.m0 * X + M.m1 * Y + M.m2 * Z + M.m3, M.m4 * X + M.m5 * Y + M.m6 * Z + M.m7, M.m8 * X + M.m9 * Y + M.m10 * Z + M.m11};
+  const double2 obs = px[i];
+  const double ob[2] = {obs.x, obs.y};
+  double r[2];
+  mvgx_ba::project_residual(res_model, intr, pc, ob, r);
+  const double rx = mul_rn(r[0], n1norm), ry = mul_rn(r[1], n1norm);
+  return add_rn(mul_rn(rx, rx), mul_rn(ry, ry));
+}
+// UniformSample(3, nData, ...) (rand_sampling.hpp:36-58): three distinct indices of [0, n - 1], a repeated one drawn again (n > 3 here)
+__device__ __forceinline__ void resb_draw_distinct(uint32_t* mt, int& mt_idx, int lane, uint32_t n, uint32_t& c0, uint32_t& c1, uint32_t& c2) {
+  c0 = uniform_u32(mt, mt_idx, lane, 0, n - 1);
+  do { c1 = uniform_u32(mt, mt_idx, lane, 0, n - 1); } while (c1 == c0);
+  do { c2 = uniform_u32(mt, mt_idx, lane, 0, n - 1); } while (c2 == c0 || c2 == c1);
+}
+// the inlier list of (M, thr) by the whole workgroup: the indices with e <= thr in index order. 512 consecutive indices per round: a
+// ballot and a count per wave, the prefix over the eight waves' counts (two sets of counts: one barrier per round). Returns the length.
+__device__ __forceinline__ uint32_t resb_rebuild_list(const ResRt& M, double thr, int res_model, const double* __restrict__ intr, double n1norm, const double* __restrict__ pX,
+                                                      const double2* __restrict__ px, uint32_t n, uint32_t* inliers, uint32_t* wcount, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  uint32_t total = 0, set = 0;
+  for (uint32_t base = 0; base < n; base += 64 * kResWaves, set ^= (uint32_t)kResWaves) {
+    const uint32_t i = base + (uint32_t)tid;
+    const bool in = i < n && res_error_of(M, res_model, intr, n1norm, pX, px, i) <= thr;   // (a NaN is no inlier)
+    const unsigned long long bal = __ballot(in);
+    if (lane == 0) wcount[set + wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kResWaves; ++w) {
+      const uint32_t c = wcount[set + w];
+      before += w < wave ? c : 0u;
+      all += c;
+    }
+    if (in) inliers[total + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = i;
+    total += all;
+  }
+  __syncthreads();
+  return total;
+}
+
+template <bool kGlobal>
+__global__ __launch_bounds__(64 * kResWaves) void resection_acransac_bounded_kernel(const ResProblem* __restrict__ problems, const ResBound* __restrict__ bounds,
+                                                                                    const uint32_t* __restrict__ order, uint32_t n_work, const double* __restrict__ x2d,
+                                                                                    const double* __restrict__ X3d, const double* __restrict__ bear, const float* __restrict__ l10,
+                                                                                    const uint32_t* __restrict__ mt_init, uint32_t max_iteration, int solver, uint32_t waves_ahead,
+                                                                                    unsigned char* __restrict__ scratch, ResResult* __restrict__ results, uint32_t* __restrict__ inliers_out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_u32[];
+  if (blockIdx.x >= n_work) return;
+  const uint32_t pi = order[blockIdx.x];
+  const ResProblem& P = problems[pi];
+  const ResBound& B = bounds[pi];
+  const uint32_t n = P.n;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n_threads = 64 * kResWaves;
+
+  uint32_t* const mt = lds_u32;
+  uint32_t* const mt_saved = mt + kMtN;
+  double* const verdicts = reinterpret_cast<double*>(mt_saved + kMtN);
+  double* const models = verdicts + kResWaves * kResBVerdict;       // 48 doubles per wave
+  uint32_t* const samples = reinterpret_cast<uint32_t*>(models + kResWaves * 48);   // 3 per wave | swap partners, 3 per wave | models per wave
+  uint32_t* const swaps = samples + 3 * kResWaves;
+  uint32_t* const n_mod = swaps + 3 * kResWaves;
+  uint32_t* const hists = samples + 8 * kResWaves;                  // kBins counters per wave
+  uint32_t* const wcount = hists + kResWaves * kBins;               // resb_rebuild_list's counts
+  double* const best_model = reinterpret_cast<double*>(wcount + 2 * kResWaves);   // the winning [R | t] (thread 0 writes and reads it)
+  uint32_t* const tables = kGlobal ? reinterpret_cast<uint32_t*>(scratch + P.scratch) : lds_u32 + resb_fixed_words();
+  const uint32_t n1 = n + 1;
+  uint32_t* const pool = tables;
+  uint32_t* const inliers = pool + n1;
+  float* const logc_n = reinterpret_cast<float*>(inliers + n1);
+  float* const logc_k = logc_n + n1;
+  uint32_t* const my_hist = hists + kBins * wave;
+
+  const double2* const px = reinterpret_cast<const double2*>(x2d) + P.start;
+  const double* const pX = X3d + 3 * P.start;
+  const double* const pb = bear + 3 * P.start;
+  const double n1norm = P.n1, loge0 = P.loge0;
+  const double max_threshold = B.max_threshold, bins_by_interval = B.bins_by_interval;
+  const double my_bin_value = lane < kBins ? B.bin_value[lane] : 0.0, my_logalpha = lane < kBins ? B.logalpha_bin[lane] : 0.0;
+  const int res_model = P.model == (uint32_t)mvgx_ba::kCamSpherical ? mvgx_ba::kCamSpherical : mvgx_ba::kCamPinhole;   // ignore_distortion
+
+  // tables and generator (as above)
+  for (uint32_t k = tid; k <= n; k += n_threads) {
+    pool[k] = k;
+    logc_k[k] = logcombi(3, k, l10);
+  }
+  if (tid == 0) {
+    float r = 0.f;
+    logc_n[0] = 0.f;
+    for (uint32_t i = 1; i <= n / 2; ++i) { r += l10[n - i + 1] - l10[i]; logc_n[i] = r; }
+  }
+  __syncthreads();
+  for (uint32_t k = n / 2 + 1 + tid; k <= n; k += n_threads) logc_n[k] = k >= n ? 0.f : logc_n[n - k];
+  for (int i = tid; i < kMtN; i += n_threads) mt[i] = mt_init[i];
+  int mt_idx = kMtN, mt_idx_saved = kMtN;   // (tracked by wave 0 alone)
+  __syncthreads();
+
+  const uint32_t Wa = waves_ahead ? waves_ahead : (uint32_t)kResWaves;
+  double minNFA = INFINITY, errorMax = INFINITY;
+  if (tid == 0)
+    for (int e = 0; e < 12; ++e) best_model[e] = 0.0;
+  bool ac = false, stop = false;   // bACRansacMode; an adopted pool was too small to sample from
+  uint32_t n_inl = 0, pool_n = n;  // the length of vec_inliers, of vec_index
+  int nIterReserve = (int)(max_iteration / 10);
+  uint32_t nIter = max_iteration - (uint32_t)nIterReserve;
+  uint32_t iter = 0, n_models_total = 0;
+
+  while (!stop && iter < nIter && iter < max_iteration) {
+    uint32_t nb = min(Wa, min(nIter - iter, max_iteration - iter));
+    // the warm-up gives up after iteration 2 nIterReserve + 1 (:448): nothing is evaluated ahead past it
+    if (!ac) nb = min(nb, 2u * (uint32_t)nIterReserve + 2u - iter);
+    const bool ac_at_start = ac;
+    // ---- the samples of the block, drawn in iteration order from the one generator (wave 0), in the block's mode ----
+    if (wave == 0) {
+      for (int i = lane; i < kMtN; i += 64) mt_saved[i] = mt[i];
+      wave_sync();
+      mt_idx_saved = mt_idx;
+      for (uint32_t j = 0; j < nb; ++j) {
+        if (ac) {
+          for (uint32_t i = 0; i < 3; ++i) {
+            const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
+            if (lane == 0) {   // (lane 0 alone reads and writes the pool here)
+              const uint32_t a = pool[i], b = pool[r];
+              pool[i] = b; pool[r] = a;
+              swaps[3 * j + i] = r;
+            }
+          }
+          if (lane == 0) { samples[3 * j] = pool[0]; samples[3 * j + 1] = pool[1]; samples[3 * j + 2] = pool[2]; }
+        } else {   // the warm-up never touches the pool
+          uint32_t c0, c1, c2;
+          resb_draw_distinct(mt, mt_idx, lane, n, c0, c1, c2);
+          if (lane == 0) { samples[3 * j] = c0; samples[3 * j + 1] = c1; samples[3 * j + 2] = c2; }
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- one wave, one iteration ----
+    if ((uint32_t)wave < nb) {
+      double* const my_models = models + 48 * wave;
+      // the sample's vectors in the wave's verdict slot, read by lane 0's solve before the verdict is written
+      double* const my_verdict = verdicts + kResBVerdict * wave;
+      if (lane < 3) {
+        const uint32_t s = samples[3 * wave + lane];
+        my_verdict[3 * lane] = pb[3 * s]; my_verdict[3 * lane + 1] = pb[3 * s + 1]; my_verdict[3 * lane + 2] = pb[3 * s + 2];
+        my_verdict[9 + 3 * lane] = pX[3 * s]; my_verdict[9 + 3 * lane + 1] = pX[3 * s + 1]; my_verdict[9 + 3 * lane + 2] = pX[3 * s + 2];
+      }
+      wave_sync();
+      if (lane == 0) n_mod[wave] = (uint32_t)res_solve(solver, my_verdict, my_verdict + 9, my_models);
+      wave_sync();
+      const int nm = (int)n_mod[wave];
+      bool my_ac = ac;
+      double run_min = minNFA, win_thr = 0.0, list_thr = 0.0;
+      int winner = -1, lister = -1;
+      uint32_t evaluated = 0, flags = 0;
+      for (int m = 0; m < nm; ++m) {
+        const ResRt M = res_rt_load(my_models + 12 * m);
+        // a model with a non-finite entry is skipped
+        const double probe = M.m0 + M.m1 + M.m2 + M.m3 + M.m4 + M.m5 + M.m6 + M.m7 + M.m8 + M.m9 + M.m10 + M.m11;
+        if (!(fabs(probe) < INFINITY)) continue;
+        ++evaluated;
+        if (lane < kBins) my_hist[lane] = 0;
+        wave_sync();
+        uint32_t n_le = 0;
+        for (uint32_t base = 0; base < n; base += 64) {
+          const uint32_t i = base + lane;
+          const double e = i < n ? res_error_of(M, res_model, P.intr, n1norm, pX, px, i) : INFINITY;
+          if (!my_ac) n_le += (uint32_t)__popcll(__ballot(i < n && e <= max_threshold));
+          // Histogram::Add (histogram.hpp:74-86): a NaN or a huge value ends in no bin, like the cast to size_t on x86-64
+          const double t = mul_rn(e, bins_by_interval);
+          if (i < n && t >= 0.0 && t < (double)kBins) atomicAdd(&my_hist[(int)t], 1u);
+        }
+        if (!my_ac && (double)n_le > 2.5 * 3) { my_ac = true; flags |= (uint32_t)kResBSwitched; }   // for this model and every later one
+        wave_sync();
+        if (my_ac) {   // ComputeNFA_and_inliers, quantified form: lane b holds bin b (the geometric filter's scan and selection)
+          uint32_t cum = lane < kBins ? my_hist[lane] : 0u;
+          cum += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cum, 0x111, 0xF, 0xF, true);
+          cum += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cum, 0x112, 0xF, 0xF, true);
+          cum += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cum, 0x114, 0xF, 0xF, true);
+          cum += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cum, 0x118, 0xF, 0xF, true);
+          {
+            const uint32_t row0 = (uint32_t)__builtin_amdgcn_readlane((int)cum, 15);
+            if (lane >= 16) cum += row0;
+          }
+          double cur = INFINITY;
+          if (lane < kBins && cum > 3u && my_bin_value > kResFltEps) {
+            cur = add_rn(add_rn(add_rn(loge0, mul_rn(my_logalpha, (double)(cum - 3u))), (double)logc_n[cum]), (double)logc_k[cum]);
+            if (!(cur < 0)) cur = INFINITY;
+          }
+          // the first bin of strictly smallest NFA among the negative ones: wave maxima of an order-reversing key of the value's bits
+          double cb_nfa = INFINITY, cb_thr = 0.0;
+          {
+            const bool cand = lane < kBins && cur < INFINITY;
+            unsigned long long bits = (unsigned long long)__double_as_longlong(cur);
+            bits = (bits >> 63) ? bits : ~(bits | 0x8000000000000000ull);
+            const uint32_t hi = cand ? (uint32_t)(bits >> 32) : 0u;
+            const uint32_t best_hi = wave_max_u32(hi);
+            if (best_hi != 0u) {   // (wave-uniform; 0: no candidate)
+              const bool top = cand && hi == best_hi;
+              const uint32_t lo = top ? (uint32_t)bits : 0u;
+              const uint32_t best_lo = wave_max_u32(lo);
+              const unsigned long long holders = __ballot(top && lo == best_lo);
+              const int b = (int)__builtin_ctzll(holders);
+              cb_nfa = lane_value_f64(cur, b);
+              cb_thr = lane_value_f64(my_bin_value, b);
+            }
+          }
+          if (cb_nfa < run_min) {   // the list is rebuilt (by the workgroup, once the verdicts are read) before its size decides (:243-255)
+            uint32_t cnt = 0;
+            for (uint32_t base = 0; base < n; base += 64) {
+              const uint32_t i = base + lane;
+              cnt += (uint32_t)__popcll(__ballot(i < n && res_error_of(M, res_model, P.intr, n1norm, pX, px, i) <= cb_thr));
+            }
+            lister = m; list_thr = cb_thr; flags |= (uint32_t)kResBRebuilt;
+            if (cnt > 3u) { run_min = cb_nfa; winner = m; win_thr = cb_thr; flags |= (uint32_t)kResBBetter; }
+          }
+        }
+        wave_sync();   // (the histogram has been read before the next model clears it)
+      }
+      wave_sync();   // every lane has read the sample's vectors before the verdict overwrites the slot
+      if (lane == 0) {
+        my_verdict[0] = (double)flags;
+        my_verdict[1] = run_min; my_verdict[2] = win_thr; my_verdict[3] = 0.0;
+        const double* const Mw = my_models + 12 * (winner >= 0 ? winner : 0);
+        const double* const Ml = my_models + 12 * (lister >= 0 ? lister : 0);
+        for (int e = 0; e < 12; ++e) { my_verdict[4 + e] = Mw[e]; my_verdict[18 + e] = Ml[e]; }
+        my_verdict[16] = (double)evaluated; my_verdict[17] = list_thr;
+      }
+    }
+    __syncthreads();
+
+    // ---- the verdicts in iteration order: the first event is applied, what follows it is void ----
+    uint32_t done = nb;
+    bool event = false;
+    for (uint32_t j = 0; j < nb && !event; ++j) {
+      const double* const v = verdicts + kResBVerdict * j;
+      n_models_total += (uint32_t)v[16];
+      const uint32_t flags = (uint32_t)v[0];
+      const bool better = (flags & (uint32_t)kResBBetter) != 0, rebuilt = (flags & (uint32_t)kResBRebuilt) != 0;
+      if (flags & (uint32_t)kResBSwitched) ac = true;
+      if (rebuilt) {   // vec_inliers of the iteration's last rebuild; a better model's is the last one or the size test failed after it
+        n_inl = resb_rebuild_list(res_rt_load(v + 18), v[17], res_model, P.intr, n1norm, pX, px, n, inliers, wcount, tid);
+        if (better) {
+          minNFA = v[1]; errorMax = v[2];
+          if (tid == 0)
+            for (int e = 0; e < 12; ++e) best_model[e] = v[4 + e];
+        }
+      }
+      // loop control (:446-474)
+      bool take_pool = false, branch = false, early = false;
+      if (!ac && (iter + j) > (uint32_t)(nIterReserve * 2)) { nIter = 0; early = true; }
+      else if (ac && ((better && minNFA < 0) || ((iter + j + 1) == nIter && nIterReserve > 0))) {
+        branch = true;
+        if (n_inl == 0) { ++nIter; --nIterReserve; }
+        else {
+          take_pool = true;
+          if (nIterReserve) { nIter = iter + j + 1 + (uint32_t)nIterReserve; nIterReserve = 0; }
+        }
+      }
+      if (rebuilt || ac != ac_at_start || branch || early) {
+        event = true;
+        done = j + 1;
+        __syncthreads();   // the inlier list is complete; wave 0 may touch the pool
+        if (done < nb && !early && wave == 0) {
+          // the generator and the pool as they stood after iteration j: undo the block's swaps, restore the state, draw j + 1 again - in the
+          // mode the block was drawn in (a switch voids what was drawn ahead in the warm-up's mode)
+          if (ac_at_start && lane == 0)
+            for (int s = 3 * (int)nb - 1; s >= 0; --s) {
+              const uint32_t i = (uint32_t)s % 3, r = swaps[s];
+              const uint32_t a = pool[i], b = pool[r];
+              pool[i] = b; pool[r] = a;
+            }
+          for (int i = lane; i < kMtN; i += 64) mt[i] = mt_saved[i];
+          wave_sync();
+          mt_idx = mt_idx_saved;
+          for (uint32_t jj = 0; jj < done; ++jj) {
+            if (ac_at_start) {
+              for (uint32_t i = 0; i < 3; ++i) {
+                const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
+                if (lane == 0) { const uint32_t a = pool[i], b = pool[r]; pool[i] = b; pool[r] = a; }
+              }
+            } else {
+              uint32_t c0, c1, c2;
+              resb_draw_distinct(mt, mt_idx, lane, n, c0, c1, c2);
+            }
+          }
+        }
+        __syncthreads();
+        if (take_pool) {   // vec_index = vec_inliers: in index order
+          for (uint32_t i = tid; i < n_inl; i += n_threads) pool[i] = inliers[i];
+          pool_n = n_inl;
+          if (pool_n < 3) stop = true;
+        }
+      }
+    }
+    iter += done;
+    __syncthreads();
+  }
+
+  if (minNFA >= 0) n_inl = 0;   // no meaningful model
+  for (uint32_t i = tid; i < n_inl; i += n_threads) inliers_out[P.start + i] = inliers[i];
+  if (tid == 0) {
+    ResResult& R = results[pi];
+    for (int e = 0; e < 12; ++e) R.P[e] = best_model[e];
+    R.error_max = errorMax; R.min_nfa = minNFA; R.n_inliers = n_inl; R.n_iterations = iter; R.n_models = n_models_total; R.pad_ = 0;
+  }
+}
+
 // ---- host ----
 // KRt_From_P (multiview/projection.cpp:40-132) of P = [R | t]: RQ of the left block by three Givens rotations, the signs fixed, t = K^-1 p4
 inline void res_mul3(const double* A, const double* B, double* C) {
@@ -753,6 +1095,222 @@ inline void res_krt_from_p(const double* P, double* K, double* R, double* t) {
   for (int e = 0; e < 9; ++e) K[e] /= k22;
 }
 
+// What mvgx_resection_localize and mvgx_resection_localize_bounded share: argument checks, problem table, staging, the bearing pass and
+// the unpacking of the results. The buffers of one call; on scope exit the stream is drained and handed back before any of them is freed.
+struct ResCall {
+  const char* entry = "";
+  bool bounded = false;
+  uint32_t n_problems = 0, n_max = 0;
+  uint64_t base = 0, n_total = 0;
+  std::vector<uint32_t> in_lds, in_global;   // problems that reach the loop (n > 3), the largest first; the two storage forms
+  // one page-locked staging buffer: problems | (bounded) bounds | launch lists | log10 table | generator state
+  mvgx::PinnedBuf<uint64_t> stage;
+  size_t stage_words = 0, prob_words = 0, bound_words = 0, n_lists = 0, l10_n = 0, scratch_bytes = 0;
+  ResProblem* hp = nullptr;
+  ResBound* h_bound = nullptr;
+  uint32_t* h_lists = nullptr;
+  mvgx::DevBuf<uint64_t> d_stage;
+  mvgx::DevBuf<double> d_x2d, d_X, d_bear;
+  mvgx::DevBuf<unsigned char> d_scratch;
+  mvgx::DevBuf<ResResult> d_res;
+  mvgx::DevBuf<uint32_t> d_inl, d_trace;
+  mvgx::PinnedBuf<ResResult> h_res;
+  hipStream_t stream = nullptr;
+  int stream_device = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ResCall() = default;
+  ResCall(const ResCall&) = delete;
+  ResCall& operator=(const ResCall&) = delete;
+  ~ResCall() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (stream) { (void)hipStreamSynchronize(stream); mvgx::release_stream(stream_device, stream); }
+  }
+  // (launch arguments are plain pointers and counts: the test-suite's emulation captures them by value)
+  const ResProblem* p_prob() const { return reinterpret_cast<const ResProblem*>(d_stage.p); }
+  const ResBound* p_bound() const { return reinterpret_cast<const ResBound*>(reinterpret_cast<const uint32_t*>(d_stage.p) + prob_words); }
+  const uint32_t* p_lists() const { return reinterpret_cast<const uint32_t*>(d_stage.p) + prob_words + bound_words; }
+  const float* p_l10() const { return reinterpret_cast<const float*>(p_lists() + n_lists); }
+  const uint32_t* p_mt() const { return reinterpret_cast<const uint32_t*>(p_l10() + l10_n); }
+};
+
+// The checks of both entries, in one order; sets c.n_max
+int res_check_arguments(ResCall& c, uint32_t n_problems, const uint64_t* start, const int32_t* intr_model, const double* intrinsics, const mvgx_resection_options* opt,
+                        const uint8_t* out_ok, const double* out_pose, const double* out_P, const double* out_error_max, const double* out_min_nfa,
+                        const uint64_t* out_inlier_start) {
+  const char* const fn = c.entry;
+  MVGX_REQUIRE(opt && start && out_ok && out_pose && out_P && out_error_max && out_min_nfa && out_inlier_start, MVGX_ERR_ARG, "%s: NULL argument", fn);
+  MVGX_REQUIRE(n_problems == 0 || (intr_model && intrinsics), MVGX_ERR_ARG, "%s: NULL camera arrays", fn);
+  MVGX_REQUIRE(opt->solver >= 0 && opt->solver <= 5, MVGX_ERR_ARG, "%s: solver %d is no resection::SolverType", fn, opt->solver);
+  MVGX_REQUIRE(opt->solver == MVGX_RESECTION_P3P_DING || opt->solver == MVGX_RESECTION_P3P_NORDBERG, MVGX_ERR_UNSUPPORTED,
+               "%s: solver %d has no device path (P3P_DING_CVPR23 = 4 and P3P_NORDBERG_ECCV18 = 3 have)", fn, opt->solver);
+  if (c.bounded)
+    MVGX_REQUIRE(std::isfinite(opt->error_max) && opt->error_max > 0, MVGX_ERR_ARG,
+                 "%s: error_max must be a finite bound in pixels, > 0 (infinity - the exhaustive NFA - is mvgx_resection_localize's form)", fn);
+  else
+    MVGX_REQUIRE(std::isinf(opt->error_max) && opt->error_max > 0, MVGX_ERR_UNSUPPORTED,
+                 "%s: a finite error_max selects the quantified NFA with the max-consensus early exit: that form is mvgx_resection_localize_bounded", fn);
+  MVGX_REQUIRE(opt->waves_ahead <= (uint32_t)kResWaves, MVGX_ERR_ARG, "%s: waves_ahead %u exceeds the build's %d", fn, opt->waves_ahead, kResWaves);
+  c.n_problems = n_problems;
+  c.n_max = 0;
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    MVGX_REQUIRE(start[p + 1] >= start[p], MVGX_ERR_ARG, "%s: start decreases at problem %u", fn, p);
+    const uint64_t n = start[p + 1] - start[p];
+    MVGX_REQUIRE(n <= kResMaxN, MVGX_ERR_ARG, "%s: problem %u has %llu correspondences, the supported maximum is %u", fn, p, (unsigned long long)n, kResMaxN);
+    const int m = intr_model[p];
+    MVGX_REQUIRE(mvgx_ba::intr_param_count(m) >= 0, MVGX_ERR_UNSUPPORTED, "%s: problem %u: camera model %d is not supported", fn, p, m);
+    c.n_max = std::max(c.n_max, (uint32_t)n);
+  }
+  return MVGX_OK;
+}
+
+// Clears the outputs and sorts the problems into the two storage forms; *work = whether any problem reaches the loop
+int res_classify(ResCall& c, const uint64_t* start, const double* x2d, const double* X3d, const uint32_t* out_inliers, uint32_t lds_bound, uint8_t* out_ok,
+                 double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, mvgx_resection_stats* stats, bool* work) {
+  const uint32_t n_problems = c.n_problems;
+  *work = false;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  for (uint32_t p = 0; p < n_problems; ++p) { out_ok[p] = 0; out_error_max[p] = 0.0; out_min_nfa[p] = 0.0; }
+  for (uint32_t p = 0; p <= n_problems; ++p) out_inlier_start[p] = 0;
+  if (!n_problems) return MVGX_OK;
+  c.base = start[0];
+  c.n_total = start[n_problems] - c.base;
+  MVGX_REQUIRE(c.n_total == 0 || (x2d && X3d && out_inliers), MVGX_ERR_ARG, "%s: NULL correspondence arrays", c.entry);
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    const uint64_t n = start[p + 1] - start[p];
+    if (n > 3) (n <= lds_bound ? c.in_lds : c.in_global).push_back(p);
+  }
+  const auto by_n = [&](uint32_t a, uint32_t b) { const uint64_t na = start[a + 1] - start[a], nb = start[b + 1] - start[b]; return na != nb ? na > nb : a < b; };
+  std::sort(c.in_lds.begin(), c.in_lds.end(), by_n);
+  std::sort(c.in_global.begin(), c.in_global.end(), by_n);
+  *work = !(c.in_lds.empty() && c.in_global.empty());
+  return MVGX_OK;
+}
+
+// The staging buffer: the problem table (and, bounded, the histogram's constants of every problem), the launch lists, the log10 table and
+// the generator's initial state. glibc's log10: the reference's values.
+int res_stage(ResCall& c, const uint64_t* start, const int32_t* intr_model, const double* intrinsics, double error_max, size_t (*scratch_bytes_of)(uint32_t)) {
+  const uint32_t n_problems = c.n_problems;
+  int rc;
+  c.n_lists = c.in_lds.size() + c.in_global.size();
+  c.prob_words = (size_t)n_problems * sizeof(ResProblem) / 4;
+  c.bound_words = c.bounded ? (size_t)n_problems * sizeof(ResBound) / 4 : 0;
+  c.l10_n = (size_t)c.n_max + 2;
+  c.stage_words = c.prob_words + c.bound_words + c.n_lists + c.l10_n + kMtN;
+  if ((rc = c.stage.ensure((c.stage_words + 1) / 2))) return rc;
+  c.hp = reinterpret_cast<ResProblem*>(c.stage.p);
+  c.h_bound = reinterpret_cast<ResBound*>(reinterpret_cast<uint32_t*>(c.stage.p) + c.prob_words);
+  c.h_lists = reinterpret_cast<uint32_t*>(c.stage.p) + c.prob_words + c.bound_words;
+  float* const h_l10 = reinterpret_cast<float*>(c.h_lists + c.n_lists);
+  uint32_t* const h_mt = reinterpret_cast<uint32_t*>(h_l10 + c.l10_n);
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    ResProblem& g = c.hp[p];
+    const uint32_t n = (uint32_t)(start[p + 1] - start[p]);
+    g.start = start[p] - c.base; g.n = n; g.model = (uint32_t)intr_model[p]; g.scratch = 0;
+    memcpy(g.intr, intrinsics + 8 * (size_t)p, sizeof(g.intr));
+    // imagePlane_toCameraPlaneError(1): 1 / focal (pinhole family), 1 / max(w, h) (spherical)
+    g.n1 = intr_model[p] == mvgx_ba::kCamSpherical ? 1.0 / std::max(g.intr[0], g.intr[1]) : 1.0 / g.intr[0];
+    g.loge0 = n > 3 ? std::log10(4.0 * (double)(n - 3)) : 0.0;   // MAX_MODELS = 4, MINIMUM_SAMPLES = 3
+    if (c.bounded) {
+      // maxThreshold = precision N(0,0)^2 with precision = Square(error_max) (SfM_Localizer.cpp:125-128, robust_estimator_ACRansac.hpp:351-353);
+      // Histogram(0, maxThreshold, 20): nBins_by_interval and GetXbinsValue (histogram.hpp:49-61, :105-112); logalpha per bin value (:229-231)
+      ResBound& b = c.h_bound[p];
+      b.max_threshold = error_max * error_max * g.n1 * g.n1;
+      b.bins_by_interval = kBins / (b.max_threshold - 0.0);
+      const double val = (b.max_threshold - 0.0) / static_cast<double>(kBins - 1);
+      for (int k = 0; k < kBins; ++k) {
+        b.bin_value[k] = val * static_cast<double>(k) + 0.0;
+        b.logalpha_bin[k] = std::log10(M_PI) + 1.0 * std::log10(b.bin_value[k] + std::numeric_limits<float>::epsilon());
+      }
+    }
+  }
+  c.scratch_bytes = 0;
+  for (uint32_t p : c.in_global) { c.hp[p].scratch = c.scratch_bytes; c.scratch_bytes += scratch_bytes_of(c.hp[p].n); }
+  if (!c.in_lds.empty()) memcpy(c.h_lists, c.in_lds.data(), c.in_lds.size() * 4);
+  if (!c.in_global.empty()) memcpy(c.h_lists + c.in_lds.size(), c.in_global.data(), c.in_global.size() * 4);
+  for (size_t i = 0; i < c.l10_n; ++i) h_l10[i] = (float)::log10((double)static_cast<float>(i));
+  h_mt[0] = 5489u;   // std::mt19937::default_seed
+  for (int i = 1; i < kMtN; ++i) h_mt[i] = 1812433253u * (h_mt[i - 1] ^ (h_mt[i - 1] >> 30)) + (uint32_t)i;
+  return MVGX_OK;
+}
+
+// Stream, events and device buffers; the uploads
+int res_upload(ResCall& c, const double* x2d, const double* X3d) {
+  int rc;
+  if ((rc = mvgx::acquire_stream(&c.stream))) return rc;
+  MVGX_HIP(hipGetDevice(&c.stream_device));
+  MVGX_HIP(hipEventCreate(&c.e0));
+  MVGX_HIP(hipEventCreate(&c.e1));
+  const uint64_t n_total = c.n_total;
+  if ((rc = c.d_stage.ensure((c.stage_words + 1) / 2)) || (rc = c.d_x2d.ensure(2 * n_total)) || (rc = c.d_X.ensure(3 * n_total)) || (rc = c.d_bear.ensure(3 * n_total)) ||
+      (rc = c.d_scratch.ensure(std::max<size_t>(c.scratch_bytes, 1))) || (rc = c.d_res.ensure(c.n_problems)) || (rc = c.d_inl.ensure(n_total)) ||
+      (rc = c.h_res.ensure(c.n_problems)))
+    return rc;
+  MVGX_HIP(hipMemcpyAsync(c.d_stage.p, c.stage.p, (c.stage_words + 1) / 2 * 8, hipMemcpyHostToDevice, c.stream));
+  MVGX_HIP(hipMemcpyAsync(c.d_x2d.p, x2d + 2 * c.base, 2 * n_total * sizeof(double), hipMemcpyHostToDevice, c.stream));
+  MVGX_HIP(hipMemcpyAsync(c.d_X.p, X3d + 3 * c.base, 3 * n_total * sizeof(double), hipMemcpyHostToDevice, c.stream));
+  MVGX_HIP(hipMemsetAsync(c.d_res.p, 0, (size_t)c.n_problems * sizeof(ResResult), c.stream));
+  return MVGX_OK;
+}
+// The first event, then the bearing pass
+int res_bear(ResCall& c) {
+  const ResProblem* const p_prob = c.p_prob();
+  const double* const p_x2d = c.d_x2d.p;
+  double* const p_bear = c.d_bear.p;
+  const uint32_t n_problems = c.n_problems;
+  const uint64_t n_total = c.n_total;
+  MVGX_HIP(hipEventRecord(c.e0, c.stream));
+  hipLaunchKernelGGL(resection_bearing_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c.stream, p_prob, n_problems, n_total, p_x2d, p_bear);
+  MVGX_HIP(hipGetLastError());
+  return MVGX_OK;
+}
+
+// After the loop kernels: the second event, the results and the inlier lists back, KRt_From_P of every problem with enough inliers
+int res_finish(ResCall& c, uint32_t* host_trace, size_t trace_words, uint8_t* out_ok, double* out_pose, double* out_P, double* out_error_max, double* out_min_nfa,
+               uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats, std::chrono::steady_clock::time_point t_begin) {
+  const uint32_t n_problems = c.n_problems;
+  MVGX_HIP(hipEventRecord(c.e1, c.stream));
+  MVGX_HIP(hipMemcpyAsync(c.h_res.p, c.d_res.p, (size_t)n_problems * sizeof(ResResult), hipMemcpyDeviceToHost, c.stream));
+  // the inlier lists come back in place (one list per problem at its start), then are packed
+  std::vector<uint32_t> inl(c.n_total);
+  MVGX_HIP(hipMemcpyAsync(inl.data(), c.d_inl.p, c.n_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+  if (host_trace) MVGX_HIP(hipMemcpyAsync(host_trace, c.d_trace.p, trace_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+  MVGX_HIP(hipStreamSynchronize(c.stream));
+
+  uint64_t at = 0, iterations = 0, n_models = 0;
+  for (uint32_t p = 0; p < n_problems; ++p) {
+    out_inlier_start[p] = at;
+    const ResResult& r = c.h_res.p[p];
+    if (c.hp[p].n <= 3) continue;   // ACRANSAC's early return of (0, 0): nothing else is written
+    iterations += r.n_iterations; n_models += r.n_models;
+    out_min_nfa[p] = r.min_nfa;
+    const double n1 = c.hp[p].n1;
+    out_error_max[p] = r.n_inliers ? std::sqrt(r.error_max) / n1 : r.error_max;   // unormalizeError
+    if (r.n_inliers) memcpy(out_inliers + at, inl.data() + c.hp[p].start, (size_t)r.n_inliers * sizeof(uint32_t));
+    at += r.n_inliers;
+    if ((double)r.n_inliers > 2.5 * 3) {
+      double K[9], R[9], t[3];
+      res_krt_from_p(r.P, K, R, t);
+      double* const pose = out_pose + 15 * (size_t)p;
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) pose[4 * i + j] = R[3 * i + j];
+        pose[4 * i + 3] = t[i];
+        pose[12 + i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);   // C = -R^T t
+      }
+      memcpy(out_P + 12 * (size_t)p, r.P, 12 * sizeof(double));
+      out_ok[p] = 1;
+    }
+  }
+  out_inlier_start[n_problems] = at;
+  if (stats) {
+    float kernel_ms = 0.f;
+    (void)hipEventElapsedTime(&kernel_ms, c.e0, c.e1);
+    stats->n_problems = n_problems; stats->n_iterations = iterations; stats->n_models = n_models; stats->kernel_ms = kernel_ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return MVGX_OK;
+}
+
 template <bool kGlobal>
 int res_launch(uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, const ResProblem* problems, const uint32_t* order, const double* x2d, const double* X3d,
                const double* bear, const float* l10, const uint32_t* mt_init, uint32_t max_iteration, int solver, uint32_t waves_ahead, uint32_t n_lds_max,
@@ -760,6 +1318,16 @@ int res_launch(uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, const Re
   MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resection_acransac_kernel<kGlobal>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   hipLaunchKernelGGL((resection_acransac_kernel<kGlobal>), dim3(n_work), dim3(64 * kResWaves), lds_bytes, stream, problems, order, n_work, x2d, X3d, bear, l10,
                      mt_init, max_iteration, solver, waves_ahead, n_lds_max, scratch, results, inliers_out, trace, trace_events);
+  MVGX_HIP(hipGetLastError());
+  return MVGX_OK;
+}
+template <bool kGlobal>
+int resb_launch(uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, const ResProblem* problems, const ResBound* bounds, const uint32_t* order, const double* x2d,
+                const double* X3d, const double* bear, const float* l10, const uint32_t* mt_init, uint32_t max_iteration, int solver, uint32_t waves_ahead,
+                unsigned char* scratch, ResResult* results, uint32_t* inliers_out) {
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resection_acransac_bounded_kernel<kGlobal>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL((resection_acransac_bounded_kernel<kGlobal>), dim3(n_work), dim3(64 * kResWaves), lds_bytes, stream, problems, bounds, order, n_work, x2d, X3d,
+                     bear, l10, mt_init, max_iteration, solver, waves_ahead, scratch, results, inliers_out);
   MVGX_HIP(hipGetLastError());
   return MVGX_OK;
 }
@@ -778,167 +1346,77 @@ void mvgx_resection_default_options(mvgx_resection_options* o) {
 int mvgx_resection_localize(int device, uint32_t n_problems, const uint64_t* start, const double* x2d, const double* X3d, const int32_t* intr_model,
                             const double* intrinsics, const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose, double* out_P,
                             double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats) {
-  using clock = std::chrono::steady_clock;
-  const auto t_begin = clock::now();
-  MVGX_REQUIRE(opt && start && out_ok && out_pose && out_P && out_error_max && out_min_nfa && out_inlier_start, MVGX_ERR_ARG, "%s: NULL argument", __func__);
-  MVGX_REQUIRE(n_problems == 0 || (intr_model && intrinsics), MVGX_ERR_ARG, "%s: NULL camera arrays", __func__);
-  MVGX_REQUIRE(opt->solver >= 0 && opt->solver <= 5, MVGX_ERR_ARG, "%s: solver %d is no resection::SolverType", __func__, opt->solver);
-  MVGX_REQUIRE(opt->solver == MVGX_RESECTION_P3P_DING || opt->solver == MVGX_RESECTION_P3P_NORDBERG, MVGX_ERR_UNSUPPORTED,
-               "%s: solver %d has no device path (P3P_DING_CVPR23 = 4 and P3P_NORDBERG_ECCV18 = 3 have)", __func__, opt->solver);
-  MVGX_REQUIRE(std::isinf(opt->error_max) && opt->error_max > 0, MVGX_ERR_UNSUPPORTED,
-               "%s: a finite error_max selects the quantified NFA with the max-consensus early exit, which has no device path yet", __func__);
-  MVGX_REQUIRE(opt->waves_ahead <= (uint32_t)kResWaves, MVGX_ERR_ARG, "%s: waves_ahead %u exceeds the build's %d", __func__, opt->waves_ahead, kResWaves);
-  uint32_t n_max = 0;
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    MVGX_REQUIRE(start[p + 1] >= start[p], MVGX_ERR_ARG, "%s: start decreases at problem %u", __func__, p);
-    const uint64_t n = start[p + 1] - start[p];
-    MVGX_REQUIRE(n <= kResMaxN, MVGX_ERR_ARG, "%s: problem %u has %llu correspondences, the supported maximum is %u", __func__, p, (unsigned long long)n, kResMaxN);
-    const int m = intr_model[p];
-    MVGX_REQUIRE(mvgx_ba::intr_param_count(m) >= 0, MVGX_ERR_UNSUPPORTED, "%s: problem %u: camera model %d is not supported", __func__, p, m);
-    n_max = std::max(n_max, (uint32_t)n);
-  }
-  if (stats) memset(stats, 0, sizeof(*stats));
-  for (uint32_t p = 0; p < n_problems; ++p) { out_ok[p] = 0; out_error_max[p] = 0.0; out_min_nfa[p] = 0.0; }
-  for (uint32_t p = 0; p <= n_problems; ++p) out_inlier_start[p] = 0;
-  if (!n_problems) return MVGX_OK;
-  const uint64_t base = start[0], n_total = start[n_problems] - base;
-  MVGX_REQUIRE(n_total == 0 || (x2d && X3d && out_inliers), MVGX_ERR_ARG, "%s: NULL correspondence arrays", __func__);
-
-  // problems that reach the loop (n > 3), the largest first; the two storage forms
-  const uint32_t lds_bound = opt->global_above ? std::min(opt->global_above, kResLdsMaxN) : kResLdsMaxN;
-  std::vector<uint32_t> in_lds, in_global;
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    const uint64_t n = start[p + 1] - start[p];
-    if (n > 3) (n <= lds_bound ? in_lds : in_global).push_back(p);
-  }
-  const auto by_n = [&](uint32_t a, uint32_t b) { const uint64_t na = start[a + 1] - start[a], nb = start[b + 1] - start[b]; return na != nb ? na > nb : a < b; };
-  std::sort(in_lds.begin(), in_lds.end(), by_n);
-  std::sort(in_global.begin(), in_global.end(), by_n);
+  const auto t_begin = std::chrono::steady_clock::now();
+  ResCall c;
+  c.entry = __func__;
   int rc;
-  if (in_lds.empty() && in_global.empty()) return MVGX_OK;
+  bool work = false;
+  if ((rc = res_check_arguments(c, n_problems, start, intr_model, intrinsics, opt, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start))) return rc;
+  const uint32_t lds_bound = opt->global_above ? std::min(opt->global_above, kResLdsMaxN) : kResLdsMaxN;
+  if ((rc = res_classify(c, start, x2d, X3d, out_inliers, lds_bound, out_ok, out_error_max, out_min_nfa, out_inlier_start, stats, &work))) return rc;
+  if (!work) return MVGX_OK;
   if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
-
-  // one page-locked staging buffer: problems | launch lists | log10 table | generator state
-  const size_t n_lists = in_lds.size() + in_global.size();
-  const size_t prob_words = (size_t)n_problems * sizeof(ResProblem) / 4, l10_n = (size_t)n_max + 2;
-  mvgx::PinnedBuf<uint64_t> stage;
-  const size_t stage_words = prob_words + n_lists + l10_n + kMtN;
-  if ((rc = stage.ensure((stage_words + 1) / 2))) return rc;
-  ResProblem* const hp = reinterpret_cast<ResProblem*>(stage.p);
-  uint32_t* const h_lists = reinterpret_cast<uint32_t*>(stage.p) + prob_words;
-  float* const h_l10 = reinterpret_cast<float*>(h_lists + n_lists);
-  uint32_t* const h_mt = reinterpret_cast<uint32_t*>(h_l10 + l10_n);
-  size_t scratch_bytes = 0;
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    ResProblem& g = hp[p];
-    const uint32_t n = (uint32_t)(start[p + 1] - start[p]);
-    g.start = start[p] - base; g.n = n; g.model = (uint32_t)intr_model[p]; g.scratch = 0;
-    memcpy(g.intr, intrinsics + 8 * (size_t)p, sizeof(g.intr));
-    // imagePlane_toCameraPlaneError(1): 1 / focal (pinhole family), 1 / max(w, h) (spherical)
-    g.n1 = intr_model[p] == mvgx_ba::kCamSpherical ? 1.0 / std::max(g.intr[0], g.intr[1]) : 1.0 / g.intr[0];
-    g.loge0 = n > 3 ? std::log10(4.0 * (double)(n - 3)) : 0.0;   // MAX_MODELS = 4, MINIMUM_SAMPLES = 3
-  }
-  for (uint32_t p : in_global) { hp[p].scratch = scratch_bytes; scratch_bytes += res_scratch_bytes(hp[p].n); }
-  if (!in_lds.empty()) memcpy(h_lists, in_lds.data(), in_lds.size() * 4);
-  if (!in_global.empty()) memcpy(h_lists + in_lds.size(), in_global.data(), in_global.size() * 4);
-  for (size_t i = 0; i < l10_n; ++i) h_l10[i] = (float)::log10((double)static_cast<float>(i));
-  h_mt[0] = 5489u;   // std::mt19937::default_seed
-  for (int i = 1; i < kMtN; ++i) h_mt[i] = 1812433253u * (h_mt[i - 1] ^ (h_mt[i - 1] >> 30)) + (uint32_t)i;
-
-  mvgx::DevBuf<uint64_t> d_stage;   // (before the stream guard: drained first, freed after)
-  mvgx::DevBuf<double> d_x2d, d_X, d_bear;
-  mvgx::DevBuf<unsigned char> d_scratch;
-  mvgx::DevBuf<ResResult> d_res;
-  mvgx::DevBuf<uint32_t> d_inl, d_trace;
-  mvgx::PinnedBuf<ResResult> h_res;
-  hipStream_t stream = nullptr;
-  if ((rc = mvgx::acquire_stream(&stream))) return rc;
-  int stream_device = 0;
-  MVGX_HIP(hipGetDevice(&stream_device));
-  mvgx::StreamGuard sg{stream_device, stream};
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  MVGX_HIP(hipEventCreate(&e0));
-  MVGX_HIP(hipEventCreate(&e1));
-  mvgx::EventGuard eg{e0, e1};
-  if ((rc = d_stage.ensure((stage_words + 1) / 2)) || (rc = d_x2d.ensure(2 * n_total)) || (rc = d_X.ensure(3 * n_total)) || (rc = d_bear.ensure(3 * n_total)) ||
-      (rc = d_scratch.ensure(std::max<size_t>(scratch_bytes, 1))) || (rc = d_res.ensure(n_problems)) || (rc = d_inl.ensure(n_total)) || (rc = h_res.ensure(n_problems)))
-    return rc;
-  MVGX_HIP(hipMemcpyAsync(d_stage.p, stage.p, (stage_words + 1) / 2 * 8, hipMemcpyHostToDevice, stream));
-  MVGX_HIP(hipMemcpyAsync(d_x2d.p, x2d + 2 * base, 2 * n_total * sizeof(double), hipMemcpyHostToDevice, stream));
-  MVGX_HIP(hipMemcpyAsync(d_X.p, X3d + 3 * base, 3 * n_total * sizeof(double), hipMemcpyHostToDevice, stream));
-  MVGX_HIP(hipMemsetAsync(d_res.p, 0, (size_t)n_problems * sizeof(ResResult), stream));
+  if ((rc = res_stage(c, start, intr_model, intrinsics, opt->error_max, &res_scratch_bytes))) return rc;
+  if ((rc = res_upload(c, x2d, X3d))) return rc;
   uint32_t* const host_trace = g_res_trace;   // (one call only)
   const uint32_t trace_events = host_trace ? g_res_trace_events : 0;
   g_res_trace = nullptr;
   const size_t trace_words = (size_t)n_problems * res_trace_words(trace_events);
   if (host_trace) {
-    if ((rc = d_trace.ensure(trace_words))) return rc;
-    MVGX_HIP(hipMemsetAsync(d_trace.p, 0, trace_words * sizeof(uint32_t), stream));
+    if ((rc = c.d_trace.ensure(trace_words))) return rc;
+    MVGX_HIP(hipMemsetAsync(c.d_trace.p, 0, trace_words * sizeof(uint32_t), c.stream));
   }
-  uint32_t* const p_trace = host_trace ? d_trace.p : nullptr;
-
-  // (launch arguments are plain pointers and counts: the test-suite's emulation captures them by value)
-  const ResProblem* const p_prob = reinterpret_cast<const ResProblem*>(d_stage.p);
-  const uint32_t* const p_lists = reinterpret_cast<const uint32_t*>(d_stage.p) + prob_words;
-  const float* const p_l10 = reinterpret_cast<const float*>(p_lists + n_lists);
-  const uint32_t* const p_mt = reinterpret_cast<const uint32_t*>(p_l10 + l10_n);
-  const double *p_x2d = d_x2d.p, *p_X = d_X.p;
-  double* const p_bear = d_bear.p;
-  MVGX_HIP(hipEventRecord(e0, stream));
-  hipLaunchKernelGGL(resection_bearing_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, stream, p_prob, n_problems, n_total, p_x2d, p_bear);
-  MVGX_HIP(hipGetLastError());
-  if (!in_lds.empty()) {
-    const uint32_t n_lds_max = hp[in_lds[0]].n;
-    if ((rc = res_launch<false>((uint32_t)in_lds.size(), res_lds_bytes(n_lds_max), stream, p_prob, p_lists, p_x2d, p_X, p_bear, p_l10, p_mt, opt->max_iteration,
-                                opt->solver, opt->waves_ahead, n_lds_max, d_scratch.p, d_res.p, d_inl.p, p_trace, trace_events)))
+  uint32_t* const p_trace = host_trace ? c.d_trace.p : nullptr;
+  if ((rc = res_bear(c))) return rc;
+  if (!c.in_lds.empty()) {
+    const uint32_t n_lds_max = c.hp[c.in_lds[0]].n;
+    if ((rc = res_launch<false>((uint32_t)c.in_lds.size(), res_lds_bytes(n_lds_max), c.stream, c.p_prob(), c.p_lists(), c.d_x2d.p, c.d_X.p, c.d_bear.p, c.p_l10(), c.p_mt(),
+                                opt->max_iteration, opt->solver, opt->waves_ahead, n_lds_max, c.d_scratch.p, c.d_res.p, c.d_inl.p, p_trace, trace_events)))
       return rc;
   }
-  if (!in_global.empty()) {
-    if ((rc = res_launch<true>((uint32_t)in_global.size(), res_lds_bytes(0), stream, p_prob, p_lists + in_lds.size(), p_x2d, p_X, p_bear, p_l10, p_mt,
-                               opt->max_iteration, opt->solver, opt->waves_ahead, 0, d_scratch.p, d_res.p, d_inl.p, p_trace, trace_events)))
+  if (!c.in_global.empty()) {
+    if ((rc = res_launch<true>((uint32_t)c.in_global.size(), res_lds_bytes(0), c.stream, c.p_prob(), c.p_lists() + c.in_lds.size(), c.d_x2d.p, c.d_X.p, c.d_bear.p, c.p_l10(),
+                               c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, 0, c.d_scratch.p, c.d_res.p, c.d_inl.p, p_trace, trace_events)))
       return rc;
   }
-  MVGX_HIP(hipEventRecord(e1, stream));
-  MVGX_HIP(hipMemcpyAsync(h_res.p, d_res.p, (size_t)n_problems * sizeof(ResResult), hipMemcpyDeviceToHost, stream));
-  // the inlier lists come back in place (one list per problem at its start), then are packed
-  std::vector<uint32_t> inl(n_total);
-  MVGX_HIP(hipMemcpyAsync(inl.data(), d_inl.p, n_total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  if (host_trace) MVGX_HIP(hipMemcpyAsync(host_trace, d_trace.p, trace_words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  MVGX_HIP(hipStreamSynchronize(stream));
-
-  uint64_t at = 0, iterations = 0, n_models = 0;
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    out_inlier_start[p] = at;
-    const ResResult& r = h_res.p[p];
-    if (hp[p].n <= 3) continue;   // ACRANSAC's early return of (0, 0): nothing else is written
-    iterations += r.n_iterations; n_models += r.n_models;
-    out_min_nfa[p] = r.min_nfa;
-    const double n1 = hp[p].n1;
-    out_error_max[p] = r.n_inliers ? std::sqrt(r.error_max) / n1 : r.error_max;   // unormalizeError
-    if (r.n_inliers) memcpy(out_inliers + at, inl.data() + hp[p].start, (size_t)r.n_inliers * sizeof(uint32_t));
-    at += r.n_inliers;
-    if ((double)r.n_inliers > 2.5 * 3) {
-      double K[9], R[9], t[3];
-      res_krt_from_p(r.P, K, R, t);
-      double* const pose = out_pose + 15 * (size_t)p;
-      for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) pose[4 * i + j] = R[3 * i + j];
-        pose[4 * i + 3] = t[i];
-        pose[12 + i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);   // C = -R^T t
-      }
-      memcpy(out_P + 12 * (size_t)p, r.P, 12 * sizeof(double));
-      out_ok[p] = 1;
-    }
-  }
-  out_inlier_start[n_problems] = at;
-  if (stats) {
-    float kernel_ms = 0.f;
-    (void)hipEventElapsedTime(&kernel_ms, e0, e1);
-    stats->n_problems = n_problems; stats->n_iterations = iterations; stats->n_models = n_models; stats->kernel_ms = kernel_ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(clock::now() - t_begin).count();
-  }
-  return MVGX_OK;
+  return res_finish(c, host_trace, trace_words, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start, out_inliers, stats, t_begin);
 }
+
+// The bounded form: opt->error_max is the bound in pixels (Image_Localizer_Match_Data::error_max on entry), finite and > 0. ACRANSAC then
+// reads the NFA off a 20-bin histogram of the residuals below the bound, starts as a max-consensus loop with the rejection sampler and
+// gives up after 2 (max_iteration / 10) + 2 iterations if no model has more than 2.5 x 3 residuals inside the bound. The inlier lists
+// come back in ascending index order.
+int mvgx_resection_localize_bounded(int device, uint32_t n_problems, const uint64_t* start, const double* x2d, const double* X3d, const int32_t* intr_model,
+                                    const double* intrinsics, const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose, double* out_P,
+                                    double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  ResCall c;
+  c.entry = __func__;
+  c.bounded = true;
+  int rc;
+  bool work = false;
+  if ((rc = res_check_arguments(c, n_problems, start, intr_model, intrinsics, opt, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start))) return rc;
+  const uint32_t lds_bound = opt->global_above ? std::min(opt->global_above, kResBLdsMaxN) : kResBLdsMaxN;
+  if ((rc = res_classify(c, start, x2d, X3d, out_inliers, lds_bound, out_ok, out_error_max, out_min_nfa, out_inlier_start, stats, &work))) return rc;
+  if (!work) return MVGX_OK;
+  if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
+  if ((rc = res_stage(c, start, intr_model, intrinsics, opt->error_max, &resb_scratch_bytes))) return rc;
+  if ((rc = res_upload(c, x2d, X3d))) return rc;
+  if ((rc = res_bear(c))) return rc;
+  if (!c.in_lds.empty()) {
+    const uint32_t n_lds_max = c.hp[c.in_lds[0]].n;   // (every workgroup of the launch gets the LDS of its largest problem)
+    if ((rc = resb_launch<false>((uint32_t)c.in_lds.size(), resb_lds_bytes(n_lds_max), c.stream, c.p_prob(), c.p_bound(), c.p_lists(), c.d_x2d.p, c.d_X.p, c.d_bear.p,
+                                 c.p_l10(), c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, c.d_scratch.p, c.d_res.p, c.d_inl.p)))
+      return rc;
+  }
+  if (!c.in_global.empty()) {
+    if ((rc = resb_launch<true>((uint32_t)c.in_global.size(), resb_lds_bytes(0), c.stream, c.p_prob(), c.p_bound(), c.p_lists() + c.in_lds.size(), c.d_x2d.p, c.d_X.p,
+                                c.d_bear.p, c.p_l10(), c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, c.d_scratch.p, c.d_res.p, c.d_inl.p)))
+      return rc;
+  }
+  return res_finish(c, nullptr, 0, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start, out_inliers, stats, t_begin);
+}
+
 
 // Test hook (not declared in include/mvgx.h): the NEXT mvgx_resection_localize call of this process leaves in `out`, per problem,
 // 1 + 10 * events words: the number of iterations that found a better model, then per such iteration (the first `events` of them)

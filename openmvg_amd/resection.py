@@ -1,7 +1,9 @@
-"""Robust camera resection on the device (mvgx_resection_localize): a batch of independent problems.
+"""Robust camera resection on the device (mvgx_resection_localize, mvgx_resection_localize_bounded): a batch of independent problems.
 
-  SfM_Localizer::Localize (error_max = infinity)   sfm/pipelines/localization/SfM_Localizer.cpp:109-343
+  SfM_Localizer::Localize (error_max = infinity)   sfm/pipelines/localization/SfM_Localizer.cpp:109-343      localize
+  SfM_Localizer::Localize (a finite error_max)      the same, ACRANSAC in its quantified form                 localize_bounded
   ACRANSAC, exhaustive NFA                          robust_estimation/robust_estimator_ACRansac.hpp:257-304, :326-489
+  ACRANSAC, quantified NFA, warm-up, early exit     robust_estimation/robust_estimator_ACRansac.hpp:205-256, :351-358, :375-475
   P3PSolver_Ding / P3PSolver_Nordberg               multiview/solver_resection_p3p_{ding,nordberg}.cpp
   KRt_From_P                                        multiview/projection.cpp:40-132
 
@@ -29,7 +31,7 @@ def default_options(**kw):
 
 class Localization:
     """The result of one problem. ok: more than 2.5 * 3 inliers; R, t, C: KRt_From_P of the winning model and the centre (ok only);
-    P: the solver's [R | t] (3 x 4, ok only); error_max: the a-contrario threshold in pixels; inliers: indices in ascending residual."""
+    P: the solver's [R | t] (3 x 4, ok only); error_max: the a-contrario threshold in pixels; inliers: indices in ascending residual (localize) or ascending index (localize_bounded)."""
 
     def __init__(self, ok, pose, P, error_max, min_nfa, inliers):
         self.ok = bool(ok)
@@ -45,13 +47,8 @@ class Localization:
 TRACE_RECORD = 10   # words of a trace record: iteration | k | the first 8 indices of the sorted list
 
 
-def localize(start, x2d, X3d, intr_model, intrinsics, solver="ding", max_iteration=4096, error_max=math.inf, device=-1, waves_ahead=0,
-             global_above=0, trace_events=0):
-    """Problem p owns the correspondences [start[p], start[p + 1]) of x2d (pixels, distortion already removed) and X3d; intr_model[p] and
-    intrinsics[p] (8 values, the BA scenes' layout) are its camera. Returns (list of Localization, _capi.ResectionStats).
-    waves_ahead / global_above: test hooks that select the kernel's form; they do not change any result. trace_events > 0 (test hook
-    mvgx_resection_debug_trace): every Localization also gets .better = [(iteration, k, head of the sorted list)] for the first
-    trace_events iterations that found a better model."""
+def _call(entry, device, start, x2d, X3d, intr_model, intrinsics, opt, trace_events=0):
+    """the arrays of one call of either entry; returns (list of Localization, stats)"""
     start = np.ascontiguousarray(start, np.uint64).reshape(-1)
     if len(start) < 1:
         raise ValueError("start needs n_problems + 1 entries")
@@ -64,8 +61,6 @@ def localize(start, x2d, X3d, intr_model, intrinsics, solver="ding", max_iterati
     intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, _capi.MVGX_BA_MAX_INTR_PARAMS)
     if len(intr_model) != n_problems or len(intrinsics) != n_problems:
         raise ValueError("one camera model and one intrinsics row per problem")
-    opt = default_options(solver=SOLVERS.get(solver, solver), max_iteration=int(max_iteration), error_max=float(error_max),
-                          waves_ahead=int(waves_ahead), global_above=int(global_above))
     ok = np.zeros(n_problems, np.uint8)
     pose = np.zeros((n_problems, 15))
     P = np.zeros((n_problems, 12))
@@ -81,7 +76,7 @@ def localize(start, x2d, X3d, intr_model, intrinsics, solver="ding", max_iterati
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.c_uint32]
         _capi.check(fn(trace.ctypes.data, int(trace_events)))
-    _capi.check(_capi.lib().mvgx_resection_localize(
+    _capi.check(getattr(_capi.lib(), entry)(
         int(device), n_problems, start.ctypes.data, x2d.ctypes.data, X3d.ctypes.data, intr_model.ctypes.data, intrinsics.ctypes.data, C.byref(opt),
         ok.ctypes.data, pose.ctypes.data, P.ctypes.data, err.ctypes.data, nfa.ctypes.data, inl_start.ctypes.data, inl.ctypes.data, C.byref(stats)))
     out = [Localization(ok[p], pose[p], P[p], err[p], nfa[p], inl[int(inl_start[p]):int(inl_start[p + 1])].copy()) for p in range(n_problems)]
@@ -91,6 +86,32 @@ def localize(start, x2d, X3d, intr_model, intrinsics, solver="ding", max_iterati
             loc.better = [(int(r[0]), int(r[1]), [int(v) for v in r[2:2 + min(int(r[1]), TRACE_RECORD - 2)]]) for r in recs]
             loc.better_count = int(trace[p, 0])
     return out, stats
+
+
+def _options(solver, max_iteration, error_max, waves_ahead, global_above):
+    return default_options(solver=SOLVERS.get(solver, solver), max_iteration=int(max_iteration), error_max=float(error_max),
+                          waves_ahead=int(waves_ahead), global_above=int(global_above))
+
+
+def localize(start, x2d, X3d, intr_model, intrinsics, solver="ding", max_iteration=4096, error_max=math.inf, device=-1, waves_ahead=0,
+             global_above=0, trace_events=0):
+    """Problem p owns the correspondences [start[p], start[p + 1]) of x2d (pixels, distortion already removed) and X3d; intr_model[p] and
+    intrinsics[p] (8 values, the BA scenes' layout) are its camera. Returns (list of Localization, _capi.ResectionStats).
+    error_max must be infinity here (the exhaustive NFA); a finite bound is localize_bounded's.
+    waves_ahead / global_above: test hooks that select the kernel's form; they do not change any result. trace_events > 0 (test hook
+    mvgx_resection_debug_trace): every Localization also gets .better = [(iteration, k, head of the sorted list)] for the first
+    trace_events iterations that found a better model."""
+    return _call("mvgx_resection_localize", device, start, x2d, X3d, intr_model, intrinsics,
+                 _options(solver, max_iteration, error_max, waves_ahead, global_above), trace_events)
+
+
+def localize_bounded(start, x2d, X3d, intr_model, intrinsics, error_max, solver="ding", max_iteration=4096, device=-1, waves_ahead=0, global_above=0):
+    """SfM_Localizer::Localize with a finite error_max (mvgx_resection_localize_bounded): the bound in pixels, finite and > 0. AC-RANSAC
+    reads the NFA off a 20-bin histogram below the bound, warms up as a max-consensus loop and gives up early when no model has more than
+    2.5 * 3 residuals inside the bound. Arguments and return value as localize's; Localization.error_max is the threshold found (one of
+    19 steps of the bound) and Localization.inliers are in ascending index order."""
+    return _call("mvgx_resection_localize_bounded", device, start, x2d, X3d, intr_model, intrinsics,
+                 _options(solver, max_iteration, error_max, waves_ahead, global_above))
 
 
 def p3p(solver, bearings, X):

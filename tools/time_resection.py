@@ -1,6 +1,8 @@
 """Times mvgx_resection_localize on the MI355X: 1 / 16 / 256 problems of 100 / 1 000 / 10 000 correspondences, 30 % outliers.
 
-  python tools/time_resection.py [--repeat 3] [--solver ding] [--max-iteration 4096]
+  python tools/time_resection.py [--repeat 3] [--solver ding] [--max-iteration 4096] [--error-max PX]
+
+--error-max PX (finite): the bounded form, mvgx_resection_localize_bounded, on the same problems.
 
 Prints one JSON line per (problems, correspondences): kernel_ms = HIP events around the prepare pass and the a-contrario kernels
 (mvgx_resection_stats), total_ms = the whole call with uploads, downloads, KRt_From_P on the host; medians over --repeat calls after one
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--solver", default="ding")
     ap.add_argument("--max-iteration", type=int, default=4096)
+    ap.add_argument("--error-max", type=float, default=float("inf"), help="a finite bound in pixels times the bounded form")
     ap.add_argument("--problems", type=int, nargs="*", default=[1, 16, 256])
     ap.add_argument("--sizes", type=int, nargs="*", default=[100, 1000, 10000])
     a = ap.parse_args()
@@ -49,14 +52,16 @@ def main():
         for n_problems in a.problems:
             args, poses = make_problems(n_problems, n)
             kw = dict(solver=a.solver, max_iteration=a.max_iteration)
-            resection.localize(*args, **kw)   # warm-up: code objects, the stream, the slab caches
+            bounded = np.isfinite(a.error_max)
+            run = (lambda *p, **k: resection.localize_bounded(*p, a.error_max, **k)) if bounded else resection.localize
+            run(*args, **kw)   # warm-up: code objects, the stream, the slab caches
             kernel, total = [], []
             for _ in range(a.repeat):
-                out, st = resection.localize(*args, **kw)
+                out, st = run(*args, **kw)
                 kernel.append(st.kernel_ms); total.append(st.total_ms)
             err = [float(np.abs(o.R - R).max()) for o, (R, _) in zip(out, poses) if o.ok]
             print(json.dumps(dict(problems=n_problems, correspondences=n, solver=a.solver, max_iteration=a.max_iteration,
-                                  kernel_ms_median=float(np.median(kernel)), kernel_ms_min=float(min(kernel)), kernel_ms_max=float(max(kernel)),
+                                  error_max=a.error_max if bounded else None, kernel_ms_median=float(np.median(kernel)), kernel_ms_min=float(min(kernel)), kernel_ms_max=float(max(kernel)),
                                   total_ms_median=float(np.median(total)), iterations=int(st.n_iterations), models=int(st.n_models),
                                   ok=int(sum(o.ok for o in out)), largest_rotation_error=max(err) if err else None)), flush=True)
 
