@@ -90,7 +90,14 @@ int mvgx_match_destroy(mvgx_match_ctx* ctx);
  * "pinned_stream" (default 1: the batch buffers of mvgx_match_run_stream are pinned; 0: plain memory, for one-shot use).
  * "stream_reserve" (uint32 words per buffer): page-locks the stream's host buffers ahead of the run - callable from another thread
  *   while mvgx_match_set_regions uploads (pinning ~100 MB takes tens of milliseconds the first batches would otherwise wait for).
- * "batch_pairs" (default 32 768): image pairs per device batch.
+ * "batch_pairs" (default 32 768): image pairs per device batch - the cap B of a batch.
+ * "batch_ramp" (default 1024; 0: off): the floor, in pairs, of the ramps at the two ends of a run. A run of at least 4 B pairs whose
+ *   B / 8 is not below the floor starts on batches of B/8, B/4, B/2 pairs and ends on B/2, B/4, B/8 (each once per device), with
+ *   equal batches of at most B between them: the work around the first and the last batch of a run, which no kernel hides, shrinks
+ *   with them. Any other run is cut into steps of exactly B. The lists do not depend on it; mvgx_match_batch_schedule tells the cut.
+ * "record_order" (default 1; 0: off): the default filter's work records are ordered by query image inside each XCD's share of a
+ *   batch, so that the workgroups resident together read the same query tiles. The lists do not depend on it.
+ *   "record_chunk_tiles" (default 256 = 1 MiB): the granule of that order in dense query tiles of 32 rows; for tests on small images.
  * Kernel selection (cross-checks and A/B runs; every combination returns the same lists): "variant" 0 = one thread per query, 1 / 2 / 3 =
  *   the exact top-2 kernel with the database window staged through registers / LDS-DMA builtin / LDS-DMA asm, 4 (default) = filter +
  *   verify. Under 4 only: "stage" 1 / 2 / 3 (default 3) = the same three staging modes, "filter_shape" 16 (default; 16x16x64 MFMA), 17
@@ -137,6 +144,12 @@ typedef int (*mvgx_match_batch_sink)(void* user, uint64_t first_pair, uint32_t n
                                      const uint32_t* ij);
 int mvgx_match_run_stream(mvgx_match_ctx* ctx, const uint32_t* pairs_IJ, uint64_t n_pairs, float ratio_sq,
                           mvgx_match_batch_sink sink, void* user, mvgx_match_stats* stats /* may be NULL */);
+
+/* The batches a run over n_pairs pairs is cut into with the context's present options ("batch_pairs", "batch_ramp") and regions:
+ * *n_batches receives their number, and the first min(capacity, *n_batches) entries of first_pair[] / batch_pairs[] the batches in
+ * ascending order (both may be NULL with capacity 0). What a sink of mvgx_match_run_stream sees, e.g. to size its own buffers. */
+int mvgx_match_batch_schedule(mvgx_match_ctx* ctx, uint64_t n_pairs, uint64_t* first_pair, uint32_t* batch_pairs, uint64_t capacity,
+                              uint64_t* n_batches);
 
 /* Host view of the last run: offsets[n_pairs+1] into ij (in units of matches); ij = 2 uint32 per match. */
 int mvgx_match_results(mvgx_match_ctx* ctx, const uint64_t** offsets, const uint32_t** ij);

@@ -169,6 +169,7 @@ PROTOTYPES = {
     "mvgx_match_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(MatchStats)]),
     "mvgx_match_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, MATCH_BATCH_SINK, C.c_void_p,
                                         C.POINTER(MatchStats)]),
+    "mvgx_match_batch_schedule": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mvgx_match_results": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32))]),
     "mvgx_match_pairs_u8_l2": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p,
                                           C.c_uint64, C.c_float, C.c_int, MATCH_SINK, C.c_void_p]),

@@ -1486,6 +1486,10 @@ __global__ __launch_bounds__(256) void l2_top2_ratio_naive_kernel(MatchParams p)
 
 }  // namespace
 
+#ifndef MVGX_MATCH_RECORD_ORDER   // the default of the option "record_order" (measurement builds set the other one)
+#define MVGX_MATCH_RECORD_ORDER 1
+#endif
+
 struct mvgx_match_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -1499,6 +1503,10 @@ struct mvgx_match_ctx {
                             // (how the four options combine: the table above resolve_form)
   int profile = 0;
   int64_t batch_pairs = 1 << 15;   // 16 batches on the 1k-image set: short pipeline fill/drain, 262k workgroups per filter launch
+  int64_t batch_ramp = 1024;       // floor of the ramps at the two ends of a run, in pairs (mvgx_records::batch_schedule); 0: every batch has batch_pairs
+  int record_order = MVGX_MATCH_RECORD_ORDER;   // 1: the records of an XCD's slice are ordered by query chunk (mvgx_records::order_records)
+  int record_chunk_tiles = mvgx_records::kOrderChunkTiles;   // dense query tiles per chunk (an option for tests: their images are small)
+  std::vector<uint32_t> h_rec_tmp, h_rec_count;   // ... built here first, counting-sort scratch
   int keep_host_results = 1;
   int overlap = 1;   // 1: batch b's filter runs beside batch b-1's verify/scan/compaction/copies (two slots)
   int verify_alone = 0;   // 1: the next filter kernel also waits for this batch's verify kernel (the two never share the device)
@@ -1534,7 +1542,7 @@ struct mvgx_match_ctx {
     PinnedBuf<uint4> hp_work8, hp_work8h;
     PinnedBuf<uint32_t> hp_offsets;
     uint64_t p0 = 0;
-    uint32_t nb = 0;
+    uint32_t nb = 0, cap = 0;         // the batch in flight; the pairs its buffers were sized for (>= nb)
     // stream mode (mvgx_match_run_stream): the lists of the slot's finished batch wait here for the sink
     // Two sets of host buffers per slot, used alternately: with the option "stream_hold" the lists handed to the sink stay
     // valid until two further sink calls have returned (a caller can turn them into its own data structures on other threads
@@ -1652,10 +1660,10 @@ uint32_t build_records(const mvgx_match_ctx* c, const uint32_t* ij, uint32_t nb,
   return mvgx_records::build_block_records(im, ij, nb, reinterpret_cast<uint32_t*>(out));
 }
 
-// host list -> device, n elements (the device buffer exists even for an empty list)
+// host list -> device, n elements (the device buffer exists even for an empty list, and holds at least `reserve` elements)
 template <typename T>
-int upload_list(DevBuf<T>& d, const PinnedBuf<T>& h, size_t n, hipStream_t stream) {
-  const int rc = d.ensure(std::max<size_t>(n, 1));
+int upload_list(DevBuf<T>& d, const PinnedBuf<T>& h, size_t n, hipStream_t stream, size_t reserve = 0) {
+  const int rc = d.ensure(std::max<size_t>(std::max(n, reserve), 1));
   if (rc) return rc;
   if (n) MVGX_HIP(hipMemcpyAsync(d.p, h.p, n * sizeof(T), hipMemcpyHostToDevice, stream));
   return MVGX_OK;
@@ -1881,6 +1889,15 @@ int mvgx_match_set_option(mvgx_match_ctx* c, const char* key, int64_t value) {
   } else if (!strcmp(key, "batch_pairs")) {
     MVGX_REQUIRE(value >= 1 && value <= (1 << 20), MVGX_ERR_ARG, "batch_pairs must be in [1, 2^20]");
     c->batch_pairs = value;
+  } else if (!strcmp(key, "batch_ramp")) {
+    MVGX_REQUIRE(value >= 0 && value <= (1 << 20), MVGX_ERR_ARG, "batch_ramp must be in [0, 2^20] (pairs; 0: no ramps)");
+    c->batch_ramp = value;
+  } else if (!strcmp(key, "record_order")) {
+    MVGX_REQUIRE(value == 0 || value == 1, MVGX_ERR_ARG, "record_order must be 0 or 1");
+    c->record_order = (int)value;
+  } else if (!strcmp(key, "record_chunk_tiles")) {
+    MVGX_REQUIRE(value >= 1 && value <= (1 << 20), MVGX_ERR_ARG, "record_chunk_tiles must be in [1, 2^20]");
+    c->record_chunk_tiles = (int)value;
   } else if (!strcmp(key, "keep_host_results")) {
     c->keep_host_results = value != 0;
   } else if (!strcmp(key, "overlap")) {
@@ -1986,16 +2003,23 @@ namespace {
 
 // The pair list of one run, cut into batches that the devices of the context take one after the other (a single device: in
 // order; several: whoever is free - the lists of a batch do not depend on which device computed them).
+// The cut is mvgx_records::batch_schedule: small batches at the two ends of a long run, batches of B between them.
 struct BatchFeed {
   const uint32_t* pairs_IJ = nullptr;
-  uint64_t n_pairs = 0, B = 1;
+  std::vector<mvgx_records::BatchSpan> batches;
+  uint32_t reserve_nb = 0;    // a ramped schedule: its largest batch, which the first batch of a slot sizes the slot's buffers for; else 0
   std::atomic<uint64_t> next{0};
   std::atomic<int> stop{0};   // a sink asked to cancel, or a device failed
+  BatchFeed(const uint32_t* pairs, uint64_t n_pairs, uint64_t B, size_t nd, int64_t ramp_min) : pairs_IJ(pairs) {
+    batches = mvgx_records::batch_schedule(n_pairs, B, (uint32_t)std::max<size_t>(nd, 1), (uint64_t)ramp_min);
+    if (mvgx_records::batch_ramp_active(n_pairs, B, (uint64_t)ramp_min))
+      for (const auto& b : batches) reserve_nb = std::max(reserve_nb, b.nb);
+  }
   bool take(uint64_t& p0, uint32_t& nb) {
     if (stop.load(std::memory_order_relaxed)) return false;
-    p0 = next.fetch_add(B);
-    if (p0 >= n_pairs) return false;
-    nb = (uint32_t)std::min<uint64_t>(B, n_pairs - p0);
+    const uint64_t k = next.fetch_add(1);
+    if (k >= batches.size()) return false;
+    p0 = batches[k].p0; nb = batches[k].nb;
     return true;
   }
 };
@@ -2020,12 +2044,13 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
 
   const KernelForm form = resolve_form(c);
   // Stage 1 of a batch on its slot's stream: work list -> filter (+ verify) -> per-pair counts -> exclusive scan -> offsets to host
-  auto issue = [&](mvgx_match_ctx::Slot& sl, mvgx_match_ctx::Slot* prev, uint64_t p0, uint32_t nb) -> int {
+  // (`cap` >= nb pairs: what the slot's buffers are sized for - a slot's first batch of a ramped run is small, its later ones are not)
+  auto issue = [&](mvgx_match_ctx::Slot& sl, mvgx_match_ctx::Slot* prev, uint64_t p0, uint32_t nb, uint32_t cap) -> int {
     int rc;
     hipStream_t stream = sl.stream;
-    sl.p0 = p0; sl.nb = nb;
+    sl.p0 = p0; sl.nb = nb; sl.cap = cap;
     const uint32_t* ij = pairs_IJ + 2 * p0;
-    if ((rc = sl.hp_pairs.ensure(nb))) return rc;
+    if ((rc = sl.hp_pairs.ensure(cap))) return rc;
     for (uint32_t k = 0; k < nb; ++k) {
       const uint32_t I = ij[2 * k], J = ij[2 * k + 1];
       sl.hp_pairs.p[k] = make_uint2(I, J);
@@ -2034,7 +2059,7 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
       st.n_desc_pairs += (uint64_t)c->h_n[I] * c->h_n[J];
     }
     // the lists the form's kernels walk; worst case ceil(max tiles / 16) 16-tile items per pair, two 8-tile items or one record for each
-    const size_t max_items16 = (size_t)nb * std::max<uint32_t>(1, (c->max_tiles_pad + kBlockQTiles - 1) / kBlockQTiles);
+    const size_t max_items16 = (size_t)cap * std::max<uint32_t>(1, (c->max_tiles_pad + kBlockQTiles - 1) / kBlockQTiles);
     uint32_t n_list[3] = {0, 0, 0};   // entries per WorkList
     if (form.reads(kListItems16)) {
       if ((rc = sl.hp_work.ensure(max_items16))) return rc;
@@ -2046,19 +2071,27 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     }
     if (form.reads(kListRecords)) {
       if ((rc = sl.hp_work8.ensure(max_items16 * kRecQuads))) return rc;
-      n_list[kListRecords] = build_records(c, ij, nb, sl.hp_work8.p);
+      if (c->record_order) {   // built in plain memory, ordered into the upload buffer
+        c->h_rec_tmp.resize(std::max(c->h_rec_tmp.size(), max_items16 * kRecQuads * 4));
+        n_list[kListRecords] = build_records(c, ij, nb, reinterpret_cast<uint4*>(c->h_rec_tmp.data()));
+        mvgx_records::order_records(c->h_qtile_off.data(), (uint32_t)c->record_chunk_tiles, ij, c->h_rec_tmp.data(), n_list[kListRecords],
+                                    reinterpret_cast<uint32_t*>(sl.hp_work8.p), c->h_rec_count);
+      } else {
+        n_list[kListRecords] = build_records(c, ij, nb, sl.hp_work8.p);
+      }
     }
     const uint32_t n_filter = n_list[form.list], n_verify = n_list[form.verify_list];   // grids
-    if ((rc = sl.d_pairs.ensure(nb))) return rc;
-    if ((rc = sl.d_best.ensure((size_t)nb * c->qstride))) return rc;
-    if (form.verify && (rc = sl.d_cd.ensure((size_t)nb * c->qstride))) return rc;
-    if ((rc = sl.d_count.ensure(nb))) return rc;
-    if ((rc = sl.d_offsets.ensure((size_t)nb + 1))) return rc;
-    if ((rc = sl.hp_offsets.ensure((size_t)nb + 1))) return rc;
+    if ((rc = sl.d_pairs.ensure(cap))) return rc;
+    if ((rc = sl.d_best.ensure((size_t)cap * c->qstride))) return rc;
+    if (form.verify && (rc = sl.d_cd.ensure((size_t)cap * c->qstride))) return rc;
+    if ((rc = sl.d_count.ensure(cap))) return rc;
+    if ((rc = sl.d_offsets.ensure((size_t)cap + 1))) return rc;
+    if ((rc = sl.hp_offsets.ensure((size_t)cap + 1))) return rc;
     MVGX_HIP(hipMemcpyAsync(sl.d_pairs.p, sl.hp_pairs.p, nb * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    if (form.reads(kListItems16) && (rc = upload_list(sl.d_work, sl.hp_work, n_list[kListItems16], stream))) return rc;
-    if (form.reads(kListItems8h) && (rc = upload_list(sl.d_work8h, sl.hp_work8h, (size_t)n_list[kListItems8h] * 2, stream))) return rc;
-    if (form.reads(kListRecords) && (rc = upload_list(sl.d_work8, sl.hp_work8, (size_t)n_list[kListRecords] * kRecQuads, stream))) return rc;
+    const size_t res16 = cap > nb ? max_items16 : 0;   // device lists follow their length, except under a small first batch
+    if (form.reads(kListItems16) && (rc = upload_list(sl.d_work, sl.hp_work, n_list[kListItems16], stream, res16))) return rc;
+    if (form.reads(kListItems8h) && (rc = upload_list(sl.d_work8h, sl.hp_work8h, (size_t)n_list[kListItems8h] * 2, stream, res16 * 4))) return rc;
+    if (form.reads(kListRecords) && (rc = upload_list(sl.d_work8, sl.hp_work8, (size_t)n_list[kListRecords] * kRecQuads, stream, res16 * kRecQuads))) return rc;
     MVGX_HIP(hipMemsetAsync(sl.d_count.p, 0, nb * sizeof(uint32_t), stream));
 
     MatchParams mp;
@@ -2126,7 +2159,10 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
     sl.out_p0 = p0; sl.out_nb = nb;
     st.n_matches += total;
     if (total) {
-      if ((rc = sl.d_ij.ensure(total))) return rc;
+      // a small first batch of a ramped run: what grows here grows for the matches of a full batch at once (sl.cap pairs at this
+      // batch's matches per pair), not batch by batch up the ramp - re-pinning ~100 MB costs tens of milliseconds, a hipFree a device sync
+      const size_t total_cap = (size_t)((uint64_t)total * sl.cap / nb);
+      if (total > sl.d_ij.cap && (rc = sl.d_ij.ensure(total_cap))) return rc;
       hipStream_t stream = sl.stream;
       const uint32_t *d_best = sl.d_best.p, *d_offsets = sl.d_offsets.p;
       const uint2* d_pairs = sl.d_pairs.p;
@@ -2138,13 +2174,13 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
         PinnedBuf<uint32_t>& hb = sl.hp_ij[sl.out_set];
         if (!hb.p) hb.pageable = !c->pinned_stream;
         // batch sizes vary: grow with headroom (re-pinning ~100 MB costs tens of milliseconds); nothing of the old content is kept
-        if ((size_t)total * 2 > hb.cap) { hb.release(); if ((rc = hb.grow_keep(std::max<size_t>((size_t)total * 3, 4u << 20), 0))) return rc; }
+        if ((size_t)total * 2 > hb.cap) { hb.release(); if ((rc = hb.grow_keep(std::max<size_t>(total_cap * 3, 4u << 20), 0))) return rc; }
         MVGX_HIP(hipMemcpyAsync(hb.p, sl.d_ij.p, (size_t)total * sizeof(uint2), hipMemcpyDeviceToHost, sl.stream));
       } else if (c->keep_host_results) {
         const size_t old = res.ij_n;
         if (old + (size_t)total * 2 > res.ij.cap)   // growth moves the lists: no copy into them may be in flight
           for (auto& o : c->slot) MVGX_HIP(hipStreamSynchronize(o.stream));
-        if ((rc = res.ij.grow_keep(old + (size_t)total * 2, old))) return rc;
+        if ((rc = res.ij.grow_keep(old + (old + (size_t)total * 2 > res.ij.cap ? total_cap : total) * 2, old))) return rc;
         res.ij_n = old + (size_t)total * 2;
         MVGX_HIP(hipMemcpyAsync(res.ij.p + old, sl.d_ij.p, (size_t)total * sizeof(uint2),
                                 hipMemcpyDeviceToHost, sl.stream));   // completes before the run returns
@@ -2163,17 +2199,18 @@ int run_device(mvgx_match_ctx* c, BatchFeed& feed, float ratio_sq, const BatchSi
   // software pipeline over the batches this device takes: issue(b) | finish(b-1) | deliver(b-2)
   uint64_t nbatch = 0, p0 = 0;
   uint32_t nb = 0;
+  auto slot_cap = [&](uint32_t nb) { return nbatch < 2 ? std::max(nb, feed.reserve_nb) : nb; };   // the first batch of either slot
   while (feed.take(p0, nb)) {
     mvgx_match_ctx::Slot& cur = c->slot[nbatch & 1];
     mvgx_match_ctx::Slot* prev = nbatch ? &c->slot[(nbatch - 1) & 1] : nullptr;
     if (!c->overlap) {
-      if ((rc = issue(cur, nullptr, p0, nb)) || (rc = finish(cur))) return rc;
+      if ((rc = issue(cur, nullptr, p0, nb, slot_cap(nb))) || (rc = finish(cur))) return rc;
       MVGX_HIP(hipStreamSynchronize(cur.stream));
       if (sink && (rc = deliver(cur))) return rc;
       ++nbatch;
       continue;
     }
-    if ((rc = issue(cur, prev, p0, nb))) return rc;   // batch b: filter on the device ...
+    if ((rc = issue(cur, prev, p0, nb, slot_cap(nb)))) return rc;   // batch b: filter on the device ...
     if (prev && (rc = finish(*prev))) return rc;      // ... while batch b-1 is compacted and copied out ...
     if (sink && nbatch >= 2 && (rc = deliver(cur))) return rc;   // ... and batch b-2 (this slot's previous one) is consumed
     // (deliver(cur) reads the slot's HOST buffers of batch b-2; the device side of the slot already works on batch b)
@@ -2310,8 +2347,7 @@ int mvgx_match_run(mvgx_match_ctx* c, const uint32_t* pairs_IJ, uint64_t n_pairs
   mvgx_match_ctx::Results& res = c->results[c->cur];
   res.offsets.assign(n_pairs + 1, 0);
   res.ij_n = 0;
-  BatchFeed feed;
-  feed.pairs_IJ = pairs_IJ; feed.n_pairs = n_pairs; feed.B = batch_size(c);
+  BatchFeed feed(pairs_IJ, n_pairs, batch_size(c), c->children.size(), c->batch_ramp);
   mvgx_match_stats st;
   if (c->children.empty()) {
     rc = run_device(c, feed, ratio_sq, nullptr, st);
@@ -2343,8 +2379,7 @@ int mvgx_match_run_stream(mvgx_match_ctx* c, const uint32_t* pairs_IJ, uint64_t 
   int rc = check_run_args(c, pairs_IJ, n_pairs, ratio_sq, "mvgx_match_run_stream");
   if (rc) return rc;
   MVGX_REQUIRE(sink != nullptr, MVGX_ERR_ARG, "mvgx_match_run_stream: sink is NULL");
-  BatchFeed feed;
-  feed.pairs_IJ = pairs_IJ; feed.n_pairs = n_pairs; feed.B = batch_size(c);
+  BatchFeed feed(pairs_IJ, n_pairs, batch_size(c), c->children.size(), c->batch_ramp);
   BatchSink fn = [&](uint64_t p0, uint32_t nb, const uint32_t* offsets, const uint32_t* ij) -> int {
     return sink(user, p0, nb, offsets, ij);
   };
@@ -2352,6 +2387,18 @@ int mvgx_match_run_stream(mvgx_match_ctx* c, const uint32_t* pairs_IJ, uint64_t 
   rc = c->children.empty() ? run_device(c, feed, ratio_sq, &fn, st) : run_multi(c, feed, ratio_sq, fn, st);
   if (rc == MVGX_OK && stats) *stats = st;
   return rc;
+}
+
+int mvgx_match_batch_schedule(mvgx_match_ctx* c, uint64_t n_pairs, uint64_t* first_pair, uint32_t* batch_pairs, uint64_t capacity,
+                              uint64_t* n_batches) {
+  MVGX_REQUIRE(c && n_batches && ((first_pair && batch_pairs) || capacity == 0), MVGX_ERR_ARG, "mvgx_match_batch_schedule: NULL argument");
+  const BatchFeed feed(nullptr, n_pairs, batch_size(c), c->children.size(), c->batch_ramp);
+  *n_batches = feed.batches.size();
+  for (uint64_t k = 0; k < std::min<uint64_t>(capacity, feed.batches.size()); ++k) {
+    first_pair[k] = feed.batches[k].p0;
+    batch_pairs[k] = feed.batches[k].nb;
+  }
+  return MVGX_OK;
 }
 
 int mvgx_match_results(mvgx_match_ctx* c, const uint64_t** offsets, const uint32_t** ij) {

@@ -1,8 +1,11 @@
 // What every matcher's batch loop shares (mvgx_match.hip, mvgx_bruteforce.hip): the no-match sentinel of best[], the two kernels that
-// turn best[] + per-pair counts into ordered match lists, the pairs-per-batch rule and the argument checks of a run.
+// turn best[] + per-pair counts into ordered match lists, the pairs-per-batch rule and the argument checks of a run. In front of them,
+// in plain C++: the work records of mvgx_match.hip's default filter, their order inside an XCD's slice and the batch schedule of its runs.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
+#include <vector>
 
 // ------------------------------------------------------------------------------------------------
 // The block-granular records of l2_filter16_kernel and the two kernels that walk the same units (MatchParams::work8).
@@ -69,6 +72,95 @@ inline uint32_t build_block_records(const ImageTables& im, const uint32_t* ij, u
     }
   }
   return n_rec;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The batches of a run. A run pipelines issue(b) | finish(b-1) | deliver(b-2); the host work and the upload of its
+// first batch and the verify, scan, compaction and copy-out of its last one have no filter kernel to hide behind, and both grow with
+// the size of that batch. So a run that is long enough starts and ends on small batches:
+//   head    B/8, B/4, B/2, each `rep` times (one per device: every device has a pipeline of its own to fill)
+//   middle  ceil(mid / B) batches whose sizes differ by at most 1 - no stub batch
+//   tail    B/2, B/4, B/8, each `rep` times
+// The ramp is active iff ramp_min > 0, B / 8 >= ramp_min and n_pairs >= 4 B; otherwise the steps are exactly B, the last one shorter.
+// rep = nd where the run has room for it: the two ramps of one device take 2 (B/8 + B/4 + B/2) <= 1.75 B pairs, and at least B pairs
+// are left to the middle, which keeps every middle batch at B / 2 or above. (n_pairs >= 4 B leaves room for one repetition; a run on eight
+// devices needs 15 B pairs for all eight and gets fewer below that.)
+// Every nb <= B, every pair is in exactly one batch, p0 increases, and no batch of an active schedule is below ramp_min.
+// ------------------------------------------------------------------------------------------------
+struct BatchSpan { uint64_t p0; uint32_t nb; };
+
+inline bool batch_ramp_active(uint64_t n_pairs, uint64_t B, uint64_t ramp_min) {
+  return ramp_min > 0 && B / 8 >= ramp_min && n_pairs >= 4 * B;
+}
+
+inline std::vector<BatchSpan> batch_schedule(uint64_t n_pairs, uint64_t B, uint32_t nd, uint64_t ramp_min) {
+  std::vector<BatchSpan> out;
+  if (B == 0) B = 1;
+  uint64_t p0 = 0;
+  auto put = [&](uint64_t nb) { out.push_back(BatchSpan{p0, (uint32_t)nb}); p0 += nb; };
+  if (!batch_ramp_active(n_pairs, B, ramp_min)) {
+    while (p0 < n_pairs) put(B < n_pairs - p0 ? B : n_pairs - p0);
+    return out;
+  }
+  const uint64_t steps[3] = {B / 8, B / 4, B / 2};
+  const uint64_t ramp = steps[0] + steps[1] + steps[2];
+  uint64_t rep = (n_pairs - B) / (2 * ramp);   // >= 1: n_pairs - B >= 3 B > 2 ramp
+  if (rep > nd) rep = nd ? nd : 1;
+  const uint64_t mid = n_pairs - 2 * rep * ramp, n_mid = (mid + B - 1) / B;   // mid >= B
+  for (int s = 0; s < 3; ++s)
+    for (uint64_t r = 0; r < rep; ++r) put(steps[s]);
+  for (uint64_t k = 0; k < n_mid; ++k) put(mid / n_mid + (k < mid % n_mid ? 1 : 0));
+  for (int s = 2; s >= 0; --s)
+    for (uint64_t r = 0; r < rep; ++r) put(steps[s]);
+  return out;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Record order inside an XCD's slice. The kernels give XCD x the x-th of eight contiguous slices of the record list
+// (xcd_remap: q = n >> 3 records each, one more in the first n & 7). The list is I-major, so a slice walks its database images one
+// after the other and a query image comes back only with the next database image, thousands of records later. Ordered by the CHUNK of
+// the query image instead - chunks cut the images at every kOrderChunkTiles dense query tiles - the workgroups resident together on an
+// XCD read the same query tiles for all the database images of the slice. A stable counting sort per slice: records are independent, so
+// any permutation gives the same lists; a slice of one database image is left as it is (its records already ascend in J when the pairs do).
+// The key of a record is the chunk of ij[2 * pair A + 1] of wave 0 (a record always has that segment).
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kOrderChunkTiles = 256;   // 1 MiB of dense query tiles (32 rows x 128 B each)
+
+inline void xcd_slice(uint32_t n_rec, uint32_t xcd, uint32_t& first, uint32_t& count) {   // the records xcd_remap gives XCD `xcd`
+  const uint32_t q = n_rec >> 3, r = n_rec & 7u;
+  first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  count = q + (xcd < r ? 1 : 0);
+}
+
+inline uint32_t record_order_key(const uint32_t* qtile_off, uint32_t chunk_tiles, const uint32_t* ij, const uint32_t* rec) {
+  return qtile_off[ij[2 * rec[4] + 1]] / chunk_tiles;
+}
+
+// `src` -> `dst` (n_rec records each, not overlapping); chunk_tiles > 0: kOrderChunkTiles outside tests; `count` is scratch that the
+// function sizes itself
+inline void order_records(const uint32_t* qtile_off, uint32_t chunk_tiles, const uint32_t* ij, const uint32_t* src, uint32_t n_rec, uint32_t* dst,
+                          std::vector<uint32_t>& count) {
+  constexpr size_t kWords = (size_t)4 * kRecQuads;
+  for (uint32_t xcd = 0; xcd < 8; ++xcd) {
+    uint32_t first, n;
+    xcd_slice(n_rec, xcd, first, n);
+    if (!n) continue;
+    const uint32_t* s = src + kWords * first;
+    uint32_t* d = dst + kWords * first;
+    bool one_image = true;
+    uint32_t key_max = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      one_image = one_image && s[kWords * k] == s[0];   // quad 0 word 0: the database image's first tile, distinct per image
+      const uint32_t key = record_order_key(qtile_off, chunk_tiles, ij, s + kWords * k);
+      key_max = key > key_max ? key : key_max;
+    }
+    if (one_image) { std::memcpy(d, s, kWords * n * sizeof(uint32_t)); continue; }
+    count.assign((size_t)key_max + 2, 0);
+    for (uint32_t k = 0; k < n; ++k) ++count[record_order_key(qtile_off, chunk_tiles, ij, s + kWords * k) + 1];
+    for (uint32_t c = 0; c <= key_max; ++c) count[c + 1] += count[c];
+    for (uint32_t k = 0; k < n; ++k)
+      std::memcpy(d + kWords * count[record_order_key(qtile_off, chunk_tiles, ij, s + kWords * k)]++, s + kWords * k, kWords * sizeof(uint32_t));
+  }
 }
 
 }  // namespace mvgx_records

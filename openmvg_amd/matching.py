@@ -217,6 +217,14 @@ class MatchContext:
             raise err[0]
         return st
 
+    def batch_schedule(self, n_pairs):
+        """mvgx_match_batch_schedule: the batches [(first pair, pairs), ...] a run over n_pairs pairs is cut into with the present options"""
+        n = C.c_uint64(0)
+        _capi.check(_capi.lib().mvgx_match_batch_schedule(self._h, int(n_pairs), None, None, 0, C.byref(n)))
+        first, nb = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+        _capi.check(_capi.lib().mvgx_match_batch_schedule(self._h, int(n_pairs), first.ctypes.data, nb.ctypes.data, n.value, C.byref(n)))
+        return [(int(a), int(b)) for a, b in zip(first, nb)]
+
     def run_collect_stream(self, pairs, ratio_sq):
         """run_stream assembled into the (stats, offsets, ij) shape of run(): for tests of the streaming path."""
         pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
