@@ -1273,41 +1273,19 @@ template <bool kWaveUnits>
 __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  uint32_t pair, qt0, I, tileI0, tileJ0, qend;   // qend: query slots of J in the layout of the filter that ran
-  // kWaveUnits: the two segments of the wave's unit and the original rows of their query images (query slot = row). A lane's block is
-  // part * 4 + lane / 16; pair, rows and nJ are those of the block's segment.
-  uint4 wa = make_uint4(0, 0, 0, 0), wb = wa;
-  const uint8_t *rowsJA = nullptr, *rowsJB = nullptr;
-  if constexpr (kWaveUnits) {
-    const uint4* rec = p.work8 + (size_t)kRecQuads * blockIdx.x;
-    const int wu = __builtin_amdgcn_readfirstlane(wave);   // wave-uniform: the unit stays in scalar registers
-    wa = rec[1 + 2 * wu]; wb = rec[2 + 2 * wu];           // an absent segment (nJ = 0) reads no slot below
-    tileI0 = rec[0].x;
-    const uint2 ijA = p.pairs[wa.x], ijB = p.pairs[wb.x];  // both pairs of a unit have the record's database image
-    I = ijA.x;
-    rowsJA = p.rows_u8 + p.img_row_off[ijA.y] * kDim;
-    rowsJB = p.rows_u8 + p.img_row_off[ijB.y] * kDim;
-    pair = 0; qt0 = 0; tileJ0 = 0; qend = 0;
-  } else {
-    const uint2 wk = p.work[blockIdx.x];
-    const uint2 ij = p.pairs[wk.x];
-    pair = wk.x; qt0 = wk.y + (uint32_t)wave * kNQ;
-    I = ij.x;
-    tileI0 = p.img_tile_off[I]; tileJ0 = p.img_tile_off[ij.y];
-    qend = (p.img_tile_off[ij.y + 1] - tileJ0) * kTileRows;
-  }
+  static_assert(!kWaveUnits, "the form after l2_filter16_kernel is the specialisation below");
+  const uint2 wk = p.work[blockIdx.x];
+  const uint2 ij = p.pairs[wk.x];
+  const uint32_t pair = wk.x, qt0 = wk.y + (uint32_t)wave * kNQ, I = ij.x;
+  const uint32_t tileI0 = p.img_tile_off[I], tileJ0 = p.img_tile_off[ij.y];
+  const uint32_t qend = (p.img_tile_off[ij.y + 1] - tileJ0) * kTileRows;   // query slots of J in the layout of the filter that ran
   const uint32_t nEvenI = p.img_neven[I], nOddI = p.img_n[I] - nEvenI;
   const int l16 = lane & 15, sub = lane >> 4;
-  uint32_t accepted = 0, acceptedB = 0;   // of the work item's pair, or of segment A's / of segment B's
+  uint32_t accepted = 0;   // of the work item's pair
   for (int part = 0; part < 2; ++part) {
     const uint32_t q0 = qt0 * kTileRows + (uint32_t)part * 64;
-    uint32_t q = q0 + lane, qpair = pair;
-    bool inb = q < qend;
-    if constexpr (kWaveUnits) {
-      const UnitBlock ub = unit_block(wa, wb, (uint32_t)(part * 4 + sub));
-      q = ub.row0 + (uint32_t)l16; qpair = ub.pair; inb = q < ub.nJ;
-    }
-    const uint32_t code = inb ? p.best[(size_t)qpair * p.qstride + q] : kNoMatch;
+    const uint32_t q = q0 + lane;
+    const uint32_t code = q < qend ? p.best[(size_t)pair * p.qstride + q] : kNoMatch;
     unsigned long long todo = __ballot(code != kNoMatch);
     while (todo) {
       // the sub-th pending candidate of this round goes to lane group `sub`
@@ -1317,15 +1295,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
       const int src = active ? __builtin_ctzll(m) : 0;
       for (int i = 0; i < 4; ++i) todo &= todo - 1;
       const uint32_t cc = (uint32_t)__shfl((int)code, src);
-      uint32_t qs = q0 + (uint32_t)src, cpair = pair;              // query slot and pair of the candidate
-      bool inA = true;
-      const uint8_t* rowsJ = nullptr;
-      if constexpr (kWaveUnits) {                                  // ... of the block of lane src
-        const uint32_t cb = (uint32_t)(part * 4 + (src >> 4));
-        const UnitBlock ub = unit_block(wa, wb, cb);
-        qs = ub.row0 + (uint32_t)(src & 15); cpair = ub.pair; inA = cb < wb.z;
-        rowsJ = inA ? rowsJA : rowsJB;
-      }
+      const uint32_t qs = q0 + (uint32_t)src;                      // query slot of the candidate
       const int s1 = cc & 7, hw = (cc >> 3) & 1, g1 = (int)(cc >> 4);
       // Row rho (0..15) of the cell sits in tile g1*8 + (rho >> 1), in-tile row slot_row(2*s1 + (rho & 1), hw); rows
       // 2c and 2c+1 are adjacent slots = 256 contiguous bytes of rows_slot. Load c (0..7) of the group therefore reads
@@ -1335,7 +1305,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
       const int mrow = slot_row(2 * s1 + rsel, hw);
       const size_t slot0 = (size_t)tileI0 * kTileRows + (active ? (size_t)g1 * kWinTiles * kTileRows + mrow : 0);
       const size_t slotQ = (size_t)tileJ0 * kTileRows + (active ? qs : 0);
-      const size_t o = (size_t)cpair * p.qstride + (active ? qs : 0);
+      const size_t o = (size_t)pair * p.qstride + (active ? qs : 0);
       // the row this lane finally owns: rho = 2 * (l16 & 7) + (l16 >> 3)  (a permutation of 0..15)
       const uint32_t tt = (uint32_t)g1 * kWinTiles + (uint32_t)piece;
       const size_t slotI = active ? slot0 + (size_t)piece * kTileRows : slot0;
@@ -1345,13 +1315,7 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
 #pragma unroll
       for (int c = 0; c < 8; ++c)
         va[c] = *reinterpret_cast<const int4*>(p.rows_slot + (slot0 + (active ? (size_t)c * kTileRows : 0)) * kDim + piece * 16);
-      int4 vb;
-      if constexpr (kWaveUnits) {   // the dense query slot is the original row: its uint8 bytes, centred here
-        vb = *reinterpret_cast<const int4*>(rowsJ + (size_t)(active ? qs : 0) * kDim + piece * 16);
-        vb.x ^= (int)0x80808080u; vb.y ^= (int)0x80808080u; vb.z ^= (int)0x80808080u; vb.w ^= (int)0x80808080u;
-      } else {
-        vb = *reinterpret_cast<const int4*>(p.rows_slot + slotQ * kDim + piece * 16);
-      }
+      const int4 vb = *reinterpret_cast<const int4*>(p.rows_slot + slotQ * kDim + piece * 16);
       const int2 f = p.cd[o];
       const int f_d0 = f.x, f_d1 = f.y;
       // |b'|^2 from the query piece itself (sum over the 8 lanes holding its pieces)
@@ -1389,17 +1353,207 @@ __global__ __launch_bounds__(256) void l2_verify_kernel(MatchParams p) {
         ok = __int2float_rn(dbest) < __fmul_rn(p.ratio_sq, __int2float_rn(d1));
         p.best[o] = ok ? p.perm[slotI] : kNoMatch;
       }
-      accepted += (uint32_t)__popcll(__ballot(ok && inA));
-      if constexpr (kWaveUnits) acceptedB += (uint32_t)__popcll(__ballot(ok && !inA));
+      accepted += (uint32_t)__popcll(__ballot(ok));
     }
   }
-  if constexpr (kWaveUnits) {   // up to two pairs per wave
-    if (lane == 0 && accepted) atomicAdd(&p.count[wa.x], accepted);
-    if (lane == 0 && acceptedB) atomicAdd(&p.count[wb.x], acceptedB);
-  } else {
-    if (lane == 0 && accepted) atomicAdd(&p.count[pair], accepted);
-  }
+  if (lane == 0 && accepted) atomicAdd(&p.count[pair], accepted);
 }
+
+// ------------------------------------------------------------------------------------------------
+// l2_verify_kernel<true>: the form that runs after l2_filter16_kernel, one WAVE per unit of a block-granular record. Same loads of data,
+// same distances, same test and the same best[] / cd[] / count[] / errflag semantics as the primary template; what differs is how many
+// vector instructions a candidate costs, for the primary template's stream is bound by vector issue (4 cycles x its
+// instructions per SIMD are its busy cycles), on the port the filter's MFMA stream shares with it:
+//   - a lane's pieces of |a'|^2 - 2 a'.b' of the eight rows it reads are reduced TRANSPOSED over the eight lanes of a row of the cell:
+//     4 + 2 + 1 exchanges, after which every lane holds the one sum it owns, instead of sixteen three-step butterflies that give every
+//     sum to every lane;
+//   - everything that depends on the candidate alone (cell, valid rows, segment) is worked out ONCE in the lane that holds its code word,
+//     and the candidates of both 64-slot parts are compacted in rank order (ballot, prefix count, one scatter); round k hands candidate
+//     4 k + sub to lane group `sub` with one gather. No per-lane loop over a ballot, and part 0's last round is no longer half empty;
+//   - the database image and the lists are addressed as a wave-uniform base plus one 32-bit byte offset per lane. Such an offset stays
+//     below 4 GiB: an image holds fewer than 2^32 / kDim slots, and a batch's best[] at most 2^29 words (mvgx_records::batch_size).
+// A lane group past the last candidate repeats the last one and stores nothing, so no address needs a guard.
+// ------------------------------------------------------------------------------------------------
+// the value of every lane sent to the lane it names (dst: a permutation of 0..63) / fetched from the lane it names
+__device__ __forceinline__ int lane_scatter(int v, int dst) {
+#ifdef MVGX_GLDS_SBASE
+  return __builtin_amdgcn_ds_permute(dst << 2, v);
+#else   // (a build without the staging statements, as stage_window16: the same exchange from shuffles)
+  const int lane = threadIdx.x & 63;
+  int out = 0;
+  for (int l = 0; l < 64; ++l) {
+    const int d = __shfl(dst, l), x = __shfl(v, l);
+    out = d == lane ? x : out;
+  }
+  return out;
+#endif
+}
+__device__ __forceinline__ int lane_gather(int v, int src) {
+#ifdef MVGX_GLDS_SBASE
+  return __builtin_amdgcn_ds_bpermute(src << 2, v);
+#else
+  return __shfl(v, src & 63);
+#endif
+}
+// a dot product that starts a sum: the three-source form with the constant 0 (the compiler picks the accumulate-in-place form and moves a
+// zero into its destination first)
+__device__ __forceinline__ int dot4_first(int a, int b) {
+#ifdef MVGX_GLDS_SBASE
+  int r;
+  asm("v_dot4_i32_i8 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+#else
+  return __builtin_amdgcn_sdot4(a, b, 0, false);
+#endif
+}
+// one step of the transposed reduction: the lane keeps the half of the values that `upper` says and adds its partner's same half
+#define MVGX_TSUM(KEEP_LO, KEEP_HI, CTRL) \
+  ((upper ? (KEEP_HI) : (KEEP_LO)) + __builtin_amdgcn_update_dpp(0, upper ? (KEEP_LO) : (KEEP_HI), (CTRL), 0xF, 0xF, true))
+
+template <>
+__global__ __launch_bounds__(256) void l2_verify_kernel<true>(MatchParams p) {
+  const int lane = threadIdx.x & 63;
+  const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the unit stays in scalar registers
+  const int l16 = lane & 15, sub = lane >> 4;
+  // Row rho (0..15) of a cell sits in tile g1*8 + (rho >> 1), in-tile row slot_row(2*s1 + (rho & 1), hw); rows 2c and 2c+1 are adjacent
+  // slots = 256 contiguous bytes of rows_slot. Load c (0..7) of the group reads exactly those two rows, lane l16 taking 16-byte piece
+  // (l16 & 7) of row 2c + (l16 >> 3): 2-4 cache lines per group and instruction. Each lane needs only ONE piece of the query. The row a
+  // lane finally owns is rho = 2 * (l16 & 7) + (l16 >> 3)  (a permutation of 0..15).
+  const int piece = l16 & 7, rsel = l16 >> 3;
+  const uint4* rec = p.work8 + (size_t)kRecQuads * blockIdx.x;
+  const uint4 wsh = rec[0], wa = rec[1 + 2 * wu], wb = rec[2 + 2 * wu];   // an absent segment (nJ = 0) holds no candidate
+  const uint2 ijA = p.pairs[wa.x], ijB = p.pairs[wb.x];                   // both pairs of a unit have the record's database image
+  // (first rows of the query images: a set whose rows fit the device's memory has far fewer than 2^32 of them)
+  const uint32_t rowA = (uint32_t)p.img_row_off[ijA.y], rowB = (uint32_t)p.img_row_off[ijB.y];
+  const uint32_t nEvenI = p.img_neven[ijA.x], nOddI = p.img_n[ijA.x] - nEvenI;
+  const uint32_t baseA = wa.x * p.qstride, baseB = wb.x * p.qstride;
+
+  // the code words of the unit's 128 query slots: both loads in flight before either is looked at (slot 0 of best[] stands in for a
+  // slot past the rows of its segment)
+  uint32_t code[2], row[2];
+  bool segA[2];
+#pragma unroll
+  for (int part = 0; part < 2; ++part) {
+    const uint32_t blk = (uint32_t)(part * 4 + sub);
+    const UnitBlock ub = unit_block(wa, wb, blk);
+    row[part] = ub.row0 + (uint32_t)l16;
+    segA[part] = blk < wb.z;
+    const bool inb = row[part] < ub.nJ;
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(p.best) +
+                                                          (inb ? (ub.pair * p.qstride + row[part]) * 4u : 0u));
+    code[part] = inb ? w : kNoMatch;
+  }
+  const unsigned long long m0 = __ballot(code[0] != kNoMatch), m1 = __ballot(code[1] != kNoMatch);
+  const int n0 = __popcll(m0), total = n0 + __popcll(m1);
+  if (total == 0) return;   // (uniform)
+
+  // Candidate of rank r (part 0's in lane order, then part 1's) -> lane r & 63 of word set r >> 6. Each part is one permutation of the
+  // lanes: its candidates to their ranks, the other lanes behind them (never read: no round asks for a rank >= total).
+  //   X = (first slot of the cell's rows 0 / 1 within the image) << 9 | (valid rows of the cell's parity half from this cell on, <= 128) << 1
+  //       | (segment A);   Y = the query row.
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int PX[2], PY[2];
+#pragma unroll
+  for (int part = 0; part < 2; ++part) {
+    const uint32_t cc = code[part];
+    const int s1 = cc & 7, hw = (cc >> 3) & 1, g1 = (int)(cc >> 4);
+    const int slotbase = g1 * (kWinTiles * kTileRows) + slot_row(2 * s1, hw);   // slot_row(2*s1 + 1, hw) is the slot after it
+    // slots of a parity half are filled in rank order: slot (tile tt, j) holds rank 16*tt + j; the cell starts at rank 128*g1 + 2*s1
+    const int left = (int)(hw ? nOddI : nEvenI) - (g1 * (kWinTiles * 16) + 2 * s1);
+    const int X = (slotbase << 9) | (min(max(left, 0), 128) << 1) | (segA[part] ? 1 : 0);
+    const bool cand = cc != kNoMatch;
+    const int r = __popcll((part ? m1 : m0) & below);
+    const int first = part ? n0 : 0, behind = part ? total : n0;
+    const int dst = (cand ? first + r : behind + (lane - r)) & 63;
+    PX[part] = lane_scatter(X, dst);
+    PY[part] = lane_scatter((int)row[part], dst);
+  }
+  const int D0X = lane < n0 ? PX[0] : PX[1], D0Y = lane < n0 ? PY[0] : PY[1];   // ranks 0..63; ranks 64.. are PX[1] / PY[1] as they lie
+
+  // wave-uniform bases of the database image: one per tile of a cell (kept apart, so that the eight loads of a round share ONE offset register)
+  const char __attribute__((address_space(1)))* rowsI[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    rowsI[c] = (const char __attribute__((address_space(1)))*)(p.rows_slot + ((size_t)wsh.x + c) * kTileRows * kDim);
+    asm volatile("" : "+s"(rowsI[c]));
+  }
+  const uint32_t* permI = p.perm + (size_t)wsh.x * kTileRows;
+  const uint32_t lane_bytes = (uint32_t)(rsel * kDim + piece * 16);   // the lane's piece within the 256 bytes of rows 2c, 2c+1
+  const uint32_t lane_slot = (uint32_t)(rsel + piece * kTileRows);   // the slot of the row the lane owns, from the cell's first
+  const int lane_rank = piece * 16 + rsel;                          // ... and its rank from the cell's first
+  uint32_t accepted = 0, acceptedB = 0;   // of segment A's / of segment B's pair
+  for (int k = 0; 4 * k < total; ++k) {
+    const int want = 4 * k + sub;
+    const bool active = want < total;
+    const int src = min(want, total - 1);   // (same word set as rank 4 k: 4 k <= total - 1)
+    const int X = lane_gather(k < 16 ? D0X : PX[1], src), Y = lane_gather(k < 16 ? D0Y : PY[1], src);
+    const uint32_t slotbase = (uint32_t)X >> 9, qs = (uint32_t)Y;
+    const bool inA = X & 1;
+    const bool valid = lane_rank < ((X >> 1) & 0xFF);
+    const uint32_t voff = slotbase * kDim + lane_bytes;
+    v4i va[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) va[c] = *(const v4i __attribute__((address_space(1)))*)(rowsI[c] + voff);
+    // the dense query slot is the original row: its uint8 bytes, centred here
+    const uint32_t grow = (inA ? rowA : rowB) + qs;
+    int4 vb = *reinterpret_cast<const int4*>(p.rows_u8 + (size_t)grow * kDim + piece * 16);
+    vb.x ^= (int)0x80808080u; vb.y ^= (int)0x80808080u; vb.z ^= (int)0x80808080u; vb.w ^= (int)0x80808080u;
+    const uint32_t o = (inA ? baseA : baseB) + qs;
+    const int2 f = *reinterpret_cast<const int2*>(reinterpret_cast<const char*>(p.cd) + o * 8u);
+    int f_d0 = f.x, f_d1 = f.y;
+    // |b'|^2 from the query piece itself (sum over the 8 lanes holding its pieces), and per row c the lane's piece of |a'|^2 - 2 a'.b'.
+    // Both norms are in tables (qnorm, qtnorm), and reading them there was built and measured: the 16 slots of a cell lie in 8 tiles, so
+    // one dword per lane touches 32 cache lines per round where the rows themselves touch 64, and the kernel, then far from bound by
+    // vector issue, takes as long as before. The rows are in registers anyway.
+    int nb = dot4_first(vb.x, vb.x);
+    nb = __builtin_amdgcn_sdot4(vb.y, vb.y, nb, false);
+    nb = __builtin_amdgcn_sdot4(vb.z, vb.z, nb, false);
+    nb = __builtin_amdgcn_sdot4(vb.w, vb.w, nb, false);
+    nb = sum8_dpp(nb);
+    int part[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      int ab = dot4_first(va[c].x, vb.x), aa = dot4_first(va[c].x, va[c].x);
+      ab = __builtin_amdgcn_sdot4(va[c].y, vb.y, ab, false); aa = __builtin_amdgcn_sdot4(va[c].y, va[c].y, aa, false);
+      ab = __builtin_amdgcn_sdot4(va[c].z, vb.z, ab, false); aa = __builtin_amdgcn_sdot4(va[c].z, va[c].z, aa, false);
+      ab = __builtin_amdgcn_sdot4(va[c].w, vb.w, ab, false); aa = __builtin_amdgcn_sdot4(va[c].w, va[c].w, aa, false);
+      part[c] = aa - 2 * ab;
+    }
+    // part[c] summed over the 8 lanes holding the 8 pieces of row c, for c = piece only: halve the values and double the lanes summed,
+    // by bit 2 (half-row mirror), bit 1 (xor 2) and bit 0 (xor 1) of the piece index. The four / two sums of a step are independent.
+    int own_row;   // |a'|^2 - 2 a'.b' of the row the lane owns
+    {
+      int t[4], u[2];
+      bool upper = piece & 4;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) t[i] = MVGX_TSUM(part[i], part[4 + i], 0x141);
+      upper = piece & 2;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) u[i] = MVGX_TSUM(t[i], t[2 + i], 0x4E);
+      upper = piece & 1;
+      own_row = MVGX_TSUM(u[0], u[1], 0xB1);
+    }
+    const int d = valid ? own_row + nb : INT_MAX;
+    asm volatile("" : "+v"(f_d0), "+v"(f_d1));   // (the filter's pair is fetched with the rows, not behind the winner's branch)
+    // best of the cell (key = distance, lane) and runner-up over the 16 lanes of the group
+    const int key = min16_dpp(valid ? ((d << 4) | l16) : INT_MAX);
+    const int wl = key & 15, dbest = key >> 4;
+    const int second = min16_dpp((l16 == wl) ? INT_MAX : d);
+    bool ok = false;
+    if (active && l16 == wl) {   // the winner's lane finishes the test and translates its slot to the original row
+      if (key == INT_MAX || dbest != f_d0) atomicAdd(p.errflag, 1u);
+      const int d1 = min(f_d1, second);
+      ok = __int2float_rn(dbest) < __fmul_rn(p.ratio_sq, __int2float_rn(d1));
+      const uint32_t orig = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(permI) + (slotbase + lane_slot) * 4u);
+      *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(p.best) + o * 4u) = ok ? orig : kNoMatch;
+    }
+    accepted += (uint32_t)__popcll(__ballot(ok && inA));
+    acceptedB += (uint32_t)__popcll(__ballot(ok && !inA));
+  }
+  if (lane == 0 && accepted) atomicAdd(&p.count[wa.x], accepted);   // up to two pairs per wave
+  if (lane == 0 && acceptedB) atomicAdd(&p.count[wb.x], acceptedB);
+}
+#undef MVGX_TSUM
 
 // statistics (profile mode only): candidates the filter hands to the verify stage. One atomic per 16 K slots — a single
 // counter word saturates at ~90 atomics/us on this chip, which is why the verify kernel itself does not count.
