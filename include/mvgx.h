@@ -709,6 +709,32 @@ int mvgx_resection_localize_bounded(int device, uint32_t n_problems, const uint6
                                     uint64_t* out_inlier_start /* n_problems + 1 */, uint32_t* out_inliers,
                                     mvgx_resection_stats* stats /* may be NULL */);
 
+/* Resection of a view WITHOUT intrinsics (no ABI bump: detect it by the symbol): what SfM_Localizer::Localize runs when the sequential
+ * engine passes resection::SolverType::DLT_6POINTS for a view that has no intrinsic group yet (sequential_SfM.cpp:937,
+ * sequential_SfM2.cpp:400), with error_max = infinity -
+ *   sfm/pipelines/localization/SfM_Localizer.cpp:134-161, :321-331   the DLT_6POINTS branch
+ *   robust_estimation/robust_estimator_ACRansacKernelAdaptator.hpp:203-288   ACKernelAdaptorResection<SixPointResectionSolver, ...>
+ *   multiview/solver_resection_kernel.cpp:29-136, multiview/conditioning.cpp:54-77   the solver, the normalisation by the image size
+ * Batch layout, options struct, stats and inlier lists are those of mvgx_resection_localize. What differs: x2d holds the pixels AS
+ * MEASURED (there is no intrinsic to undistort with), image_wh + 2 p is the view's (ui_width, ui_height), and K is an output.
+ * Outputs per problem: out_ok = more than 2.5 * 6 inliers (15 are not enough, 16 are); then out_P + 12 p = the UNNORMALISED projection
+ * matrix N1^-1 P (row-major 3 x 4, scaled as the solver leaves it: what resection_data.projection_matrix gets), out_pose + 15 p = R | t
+ * of KRt_From_P(out_P) followed by C = -R^T t, out_K + 9 p = the K of the same decomposition (K / K(2,2), row-major; the engine seeds
+ * the new intrinsic group with focal = (K(0,0) + K(1,1)) / 2 and the principal point K(0,2), K(1,2): sequential_SfM.cpp:986-987).
+ * out_error_max: sqrt(errorMax) / N1(0,0) in pixels. A problem of six or fewer correspondences: not ok, zeros, nothing else written.
+ * MVGX_ERR_ARG: opt->solver != MVGX_RESECTION_DLT_6POINTS (the calibrated solvers are mvgx_resection_localize's), a zero width or height
+ * (or a product beyond int), NULL arrays, a start that decreases, more than 65 536 correspondences in one problem. MVGX_ERR_UNSUPPORTED: a
+ * finite opt->error_max (the quantified form of the six-point loop has no device path).
+ * Parity: decisions, sample sequence and inlier order as the reference's, numbers to rounding ("Resection without
+ * intrinsics"). Deliberate differences: a model with a non-finite entry is skipped; a sample whose singular value iteration has not
+ * converged after 30 sweeps yields no model (none does: the fixture's samples need at most 10). */
+#define MVGX_RESECTION_DLT_6POINTS 0   /* resection::SolverType::DLT_6POINTS */
+int mvgx_resection_localize_uncalibrated(int device, uint32_t n_problems, const uint64_t* start /* n_problems + 1 */, const double* x2d, const double* X3d,
+                                         const uint32_t* image_wh /* n_problems x 2 */, const mvgx_resection_options* opt, uint8_t* out_ok,
+                                         double* out_pose /* n_problems x 15 */, double* out_P /* n_problems x 12 */, double* out_K /* n_problems x 9 */,
+                                         double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start /* n_problems + 1 */, uint32_t* out_inliers,
+                                         mvgx_resection_stats* stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

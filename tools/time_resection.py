@@ -1,8 +1,11 @@
 """Times mvgx_resection_localize on the MI355X: 1 / 16 / 256 problems of 100 / 1 000 / 10 000 correspondences, 30 % outliers.
 
-  python tools/time_resection.py [--repeat 3] [--solver ding] [--max-iteration 4096] [--error-max PX]
+  python tools/time_resection.py [--repeat 3] [--solver ding] [--max-iteration 4096] [--error-max PX] [--uncalibrated]
 
 --error-max PX (finite): the bounded form, mvgx_resection_localize_bounded, on the same problems.
+--uncalibrated: mvgx_resection_localize_uncalibrated (the six-point DLT loop of a view without intrinsics) on the same problems, the
+image size 1280 x 960 in place of the intrinsics. With --max-iteration 1 every problem runs one solve, one sort and one NFA scan: the
+fixed part that the solver's share of the kernel time is read against (models / iterations of the full run are printed for it).
 
 Prints one JSON line per (problems, correspondences): kernel_ms = HIP events around the prepare pass and the a-contrario kernels
 (mvgx_resection_stats), total_ms = the whole call with uploads, downloads, KRt_From_P on the host; medians over --repeat calls after one
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--solver", default="ding")
     ap.add_argument("--max-iteration", type=int, default=4096)
     ap.add_argument("--error-max", type=float, default=float("inf"), help="a finite bound in pixels times the bounded form")
+    ap.add_argument("--uncalibrated", action="store_true", help="times mvgx_resection_localize_uncalibrated (six-point DLT, no intrinsics)")
     ap.add_argument("--problems", type=int, nargs="*", default=[1, 16, 256])
     ap.add_argument("--sizes", type=int, nargs="*", default=[100, 1000, 10000])
     a = ap.parse_args()
@@ -54,13 +58,19 @@ def main():
             kw = dict(solver=a.solver, max_iteration=a.max_iteration)
             bounded = np.isfinite(a.error_max)
             run = (lambda *p, **k: resection.localize_bounded(*p, a.error_max, **k)) if bounded else resection.localize
+            if a.uncalibrated:
+                if bounded:
+                    raise SystemExit("the six-point loop has no bounded form")
+                args = args[:3] + ([(1280, 960)] * n_problems,)
+                kw = dict(max_iteration=a.max_iteration)
+                run = resection.localize_uncalibrated
             run(*args, **kw)   # warm-up: code objects, the stream, the slab caches
             kernel, total = [], []
             for _ in range(a.repeat):
                 out, st = run(*args, **kw)
                 kernel.append(st.kernel_ms); total.append(st.total_ms)
             err = [float(np.abs(o.R - R).max()) for o, (R, _) in zip(out, poses) if o.ok]
-            print(json.dumps(dict(problems=n_problems, correspondences=n, solver=a.solver, max_iteration=a.max_iteration,
+            print(json.dumps(dict(problems=n_problems, correspondences=n, solver="dlt6" if a.uncalibrated else a.solver, max_iteration=a.max_iteration,
                                   error_max=a.error_max if bounded else None, kernel_ms_median=float(np.median(kernel)), kernel_ms_min=float(min(kernel)), kernel_ms_max=float(max(kernel)),
                                   total_ms_median=float(np.median(total)), iterations=int(st.n_iterations), models=int(st.n_models),
                                   ok=int(sum(o.ok for o in out)), largest_rotation_error=max(err) if err else None)), flush=True)
