@@ -318,6 +318,7 @@ __device__ __forceinline__ void stage_window_glds_asm(char* buf, const int8_t* _
 // per window, plus one 32-bit offset per lane that never changes (lane * 16 + wave * 1024; a quarter of it for the constants) - no 64-bit
 // vector add per piece. M0, the statement's shape and the wait in front of the barrier are those of glds16_asm.
 #define MVGX_GLDS_SBASE 1   // (a build that replaces this block of staging statements by copies defines none: see stage_window16)
+#define MVGX_LANE_SWAP 1    // likewise: v_permlane16_swap_b32 / v_permlane32_swap_b32 in swap_rows16 / swap_halves32, shuffles and a select without
 __device__ __forceinline__ void glds16_sasm(const void* sbase, unsigned voff, unsigned lds_dst) {
   unsigned keep;
   asm volatile(
@@ -937,39 +938,66 @@ __device__ __forceinline__ UnitBlock unit_block(const uint4& a, const uint4& b, 
   return UnitBlock{inA ? a.x : b.x, inA ? a.y : b.y, (inA ? a.z + n : n - b.z) * 16u, inA ? a.w : b.w};
 }
 
-// MVGX_FINISH16 with the same two-instruction top-2 over the lane's four classes (p2 <= p1 throughout, as in fold_window16), for query
-// block N of the wave's unit: lane l < 16 owns row ub.row0 + l of the block's own pair
-#define MVGX_FINISH16_MED3(N, INB, VALID)                                                                                                 \
+// The finish of l2_filter16_kernel, TRANSPOSED: the merge of the four lane groups that share a query column is a reduction, and every lane
+// group takes a quarter of its eight instances instead of all four groups computing all eight and three of them throwing the result away.
+//   MVGX_TRIPLE16_MED3(N)   per lane, for every block: the triple (W1, V2, code) of MVGX_FINISH16 with the two-instruction top-2 over the
+//                           lane's four classes (p2 <= p1 throughout, as in fold_window16);
+//   swap_rows16             groups g <-> g ^ 1 exchange HALVES of the work: for the pair (block n, block n + 4) the even group hands over
+//                           its triple of block n + 4 and receives the odd group's of block n. Afterwards x is group (g & 2)'s value and y
+//                           group (g | 1)'s in BOTH groups - of block n in the even one, of block n + 4 in the odd one;
+//   swap_halves32           the same across g <-> g ^ 2 for the pair (merged block k, merged block k + 2): x is the lower half's value and
+//                           y the upper half's, of block k in lanes 0..31 and of block k + 2 in lanes 32..63;
+//   merge_groups16          MVGX_FINISH16's merge step with x in the role "mine" and y in the role of the exchanged value. It is not
+//                           symmetric under ties (W1 > o1 is strict), so the roles are those lane group 0 had when it alone stored:
+//                           (g0 + g1) + (g2 + g3), left operand "mine" - best[] and cd[] are what they were, byte for byte.
+// After 4 + 2 merges lane group g owns blocks own0 + {0, 1}, own0 = 4 (g & 1) + 2 (g >> 1), and finishes them on its 16 lanes.
+#define MVGX_TRIPLE16_MED3(N)                                                                                                              \
   {                                                                                                                                       \
-    int p1 = kNegInit, p2 = kNegInit, pc = 0;   /* best / second-best P-class of this lane */                                             \
-    _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                                                       \
+    /* best / second-best P-class of this lane. Classes 0 and 1 start the scan: no TP is below kNegInit (each starts there and only */   \
+    /* grows), so the two steps from (kNegInit, kNegInit, 0) over TP[N][0] and TP[N][1] give exactly this */                              \
+    int p1 = max(TP[N][0], TP[N][1]), p2 = min(TP[N][0], TP[N][1]), pc = TP[N][1] > TP[N][0] ? 1 : 0;                                     \
+    _Pragma("unroll") for (int c = 2; c < 4; ++c) {                                                                                       \
       const int v = TP[N][c];                                                                                                             \
       pc = v > p1 ? c : pc;                                                                                                               \
       p2 = med3i(p1, v, p2);                                                                                                              \
       p1 = max(p1, v);                                                                                                                    \
     }                                                                                                                                     \
-    /* exact w = |b'|^2 - d of the lane's best row; V2: its runner-up outside the best row's (class, window) cell */                      \
-    int W1 = 2 * p1 - par, V2 = max(2 * p2 - par, 2 * Q2[N] - par);                                                                       \
-    int code = (4 * (pc >> 1) + 2 * (g4 >> 1) + (pc & 1)) | (par << 3) | (Qg[N] << 4);   /* (s1, half, window) of the 32x32 kernel's cells */ \
-    /* the merge of the four lane groups that share the query column: as in MVGX_FINISH16 */                                              \
-    _Pragma("unroll") for (int x = 16; x <= 32; x <<= 1) {                                                                                \
-      const int o1 = __shfl_xor(W1, x), o2 = __shfl_xor(V2, x), oc = __shfl_xor(code, x);                                                 \
-      const bool mine = W1 > o1;                                                                                                          \
-      V2 = mine ? max(V2, o1) : max(o2, W1);                                                                                              \
-      code = mine ? code : oc;                                                                                                            \
-      W1 = mine ? W1 : o1;                                                                                                                \
-    }                                                                                                                                     \
-    const UnitBlock ub = unit_block(wa, wb, (uint32_t)(N));   /* wave-uniform: the block's segment says pair, rows and nJ */               \
-    const uint32_t q = ub.row0 + (uint32_t)(lane & 15);                                                                                   \
-    if (lane < 16 && (INB)) {                                                                                                             \
-      const int nq = qn[N];                                                                                                               \
-      const int d0 = nq - W1, d1ub = nq - V2;                                                                                             \
-      const bool cand = (VALID) && (__int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub)));                                    \
-      const size_t o = (size_t)ub.pair * p.qstride + q;                                                                                   \
-      p.best[o] = cand ? (uint32_t)code : kNoMatch;                                                                                       \
-      if (cand) p.cd[o] = make_int2(d0, d1ub);                                                                                            \
-    }                                                                                                                                     \
+    /* exact w = |b'|^2 - d of the lane's best row; V2: its runner-up outside the best row's (class, window) cell, the larger of */       \
+    /* 2 p2 - par and 2 Q2 - par (one doubling for both: every value here is within +-2^28) */                                            \
+    W1[N] = 2 * p1 - par;                                                                                                                 \
+    V2[N] = 2 * max(p2, Q2[N]) - par;                                                                                                     \
+    code[N] = (4 * (pc >> 1) + 2 * (g4 >> 1) + (pc & 1)) | (par << 3) | (Qg[N] << 4);   /* (s1, half, window) of the 32x32 kernel's cells */ \
   }
+__device__ __forceinline__ void swap_rows16(int& x, int& y) {
+#ifdef MVGX_LANE_SWAP
+  const auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)y, false, false);   // odd rows of x <-> even rows of y
+  x = (int)r[0]; y = (int)r[1];
+#else   // (a build without the staging statements, as stage_window16: the same exchange from shuffles)
+  const bool odd = (threadIdx.x >> 4) & 1;
+  const int ox = __shfl_xor(x, 16), oy = __shfl_xor(y, 16);
+  x = odd ? oy : x;
+  y = odd ? y : ox;
+#endif
+}
+__device__ __forceinline__ void swap_halves32(int& x, int& y) {
+#ifdef MVGX_LANE_SWAP
+  const auto r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)y, false, false);   // lanes 32..63 of x <-> lanes 0..31 of y
+  x = (int)r[0]; y = (int)r[1];
+#else
+  const bool upper = (threadIdx.x >> 5) & 1;
+  const int ox = __shfl_xor(x, 32), oy = __shfl_xor(y, 32);
+  x = upper ? oy : x;
+  y = upper ? y : ox;
+#endif
+}
+// (groups g and g ^ 2 have the same parity, so their best values can be equal: then V2 >= W1, d1_ub <= d0 and the query is rejected, as
+// the reference rejects a tie for the first place)
+__device__ __forceinline__ void merge_groups16(int& W1, int& V2, int& code, int o1, int o2, int oc) {
+  const bool mine = W1 > o1;
+  V2 = mine ? max(V2, o1) : max(o2, W1);
+  code = mine ? code : oc;
+  W1 = mine ? W1 : o1;
+}
 
 __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x kStageBytes
@@ -1006,14 +1034,15 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   const int8_t* gI = p.tiles + (size_t)tileI0 * kTileBytes;
   const int* gC = p.cinit + (size_t)tileI0 * kTileRows;
 
-  // squared norm of the lane's eight query slots: fetched now, used after the last window (they used to be loaded there, one more trip
-  // to memory at the end of every workgroup). A dense slot is valid iff it is below the nJ of its block's segment: no table says so.
-  int qn[kNB16];
+  // squared norm of the two query slots the lane will finish (the transposed merge hands blocks own0 and own0 + 1 to its lane group):
+  // fetched now, used after the last window. A dense slot is valid iff it is below the nJ of its block's segment: no table says so.
+  const uint32_t own0 = (uint32_t)(4 * par + 2 * (g4 >> 1));
+  int qn[2];
 #pragma unroll
-  for (int n = 0; n < kNB16; ++n) {
-    const UnitBlock ub = unit_block(wa, wb, (uint32_t)n);
+  for (int k = 0; k < 2; ++k) {
+    const UnitBlock ub = unit_block(wa, wb, own0 + (uint32_t)k);   // the lane's own block, as the verify stage calls it
     const uint32_t q = ub.row0 + (uint32_t)(lane & 15);
-    qn[n] = (lane < 16 && q < ub.nJ) ? p.qtnorm[(size_t)ub.tileJ0 * kTileRows + q] : 0;
+    qn[k] = q < ub.nJ ? p.qtnorm[(size_t)ub.tileJ0 * kTileRows + q] : 0;
   }
 
   int TP[kNB16][4];                         // P-class maxima of the run
@@ -1033,8 +1062,8 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
   for (int n = 0; n < kNB16; ++n) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) asm volatile("" : "+v"(b[n][ks]));
-    asm volatile("" : "+v"(qn[n]));
   }
+  asm volatile("" : "+v"(qn[0]), "+v"(qn[1]));
 
   for (int win = 0; win < nwin; ++win) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1120,8 +1149,34 @@ __global__ __launch_bounds__(256, 2) void l2_filter16_kernel(MatchParams p) {
     for (int n = 0; n < kNB16; ++n) fold_window16(TW[n], TP[n], Q1[n], Q2[n], Qg[n], win);
   }
 
+  int W1[kNB16], V2[kNB16], code[kNB16];
 #pragma unroll
-  for (int n = 0; n < kNB16; ++n) MVGX_FINISH16_MED3(n, q < ub.nJ, true)   // a dense slot is a row of its segment's J: every one below nJ holds a row
+  for (int n = 0; n < kNB16; ++n) MVGX_TRIPLE16_MED3(n)
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {   // g <-> g ^ 1: even groups go on with blocks 0..3, odd groups with blocks 4..7
+    swap_rows16(W1[n], W1[n + 4]); swap_rows16(V2[n], V2[n + 4]); swap_rows16(code[n], code[n + 4]);
+    merge_groups16(W1[n], V2[n], code[n], W1[n + 4], V2[n + 4], code[n + 4]);
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {   // g <-> g ^ 2: lanes 0..31 go on with the first two of their four blocks, lanes 32..63 with the other two
+    swap_halves32(W1[k], W1[k + 2]); swap_halves32(V2[k], V2[k + 2]); swap_halves32(code[k], code[k + 2]);
+    merge_groups16(W1[k], V2[k], code[k], W1[k + 2], V2[k + 2], code[k + 2]);
+  }
+  // the fp32 pre-test and the stores, on all 64 lanes: lane l owns row ub.row0 + (l & 15) of blocks own0 and own0 + 1 of the wave's unit,
+  // each in its own segment's pair. A dense slot is a row of its segment's J: every one below nJ holds a row
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const UnitBlock ub = unit_block(wa, wb, own0 + (uint32_t)k);
+    const uint32_t q = ub.row0 + (uint32_t)(lane & 15);
+    if (q < ub.nJ) {
+      const int nq = qn[k];
+      const int d0 = nq - W1[k], d1ub = nq - V2[k];
+      const bool cand = __int2float_rn(d0) < __fmul_rn(p.ratio_sq, __int2float_rn(d1ub));
+      const size_t o = (size_t)ub.pair * p.qstride + q;
+      p.best[o] = cand ? (uint32_t)code[k] : kNoMatch;
+      if (cand) p.cd[o] = make_int2(d0, d1ub);
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
