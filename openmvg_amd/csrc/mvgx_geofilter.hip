@@ -1695,6 +1695,7 @@ int mvgx_debug_five_point4(const double* b1, const double* b2, double* Es_out, i
 
 }  // extern "C"
 
-// LAST in this file: the header switches FMA contraction off at file scope, which holds for everything after it in the translation unit
-#include "mvgx_resection.h"   // robust resection: uses this unit's generator, bounded draw, logcombi and un-contracted operations
-#include "mvgx_resection_dlt.h"   // ... and its form for a view without intrinsics (six-point DLT), under the same pragma
+// LAST in this file: the first header switches FMA contraction off at file scope, which holds for everything after it in the translation unit
+#include "mvgx_resection_loop.h"   // robust resection, the a-contrario loop: uses this unit's generator, bounded draw, logcombi and un-contracted operations
+#include "mvgx_resection.h"        // ... its P3P forms (exhaustive and bounded) and the host side, under the same pragma
+#include "mvgx_resection_dlt.h"    // ... and its form for a view without intrinsics (six-point DLT)

@@ -1,44 +1,23 @@
 // mvgx_resection.h - robust camera resection on the device: AC-RANSAC over a P3P solver, a batch of independent problems per call, in
 // the reference's two forms: the exhaustive NFA of an unbounded precision (mvgx_resection_localize) and the quantified NFA with the
-// max-consensus warm-up of a bounded one (mvgx_resection_localize_bounded). Included at the end of mvgx_geofilter.hip: it uses that
-// unit's std::mt19937, bounded draw, logcombi, histogram scan and un-contracted mul_rn / add_rn, and ba_math.h for the camera models.
-// What is restated (paths under src/openMVG of the reference):
+// max-consensus warm-up of a bounded one (mvgx_resection_localize_bounded). Included at the end of mvgx_geofilter.hip, after
+// mvgx_resection_loop.h and under that header's `#pragma clang fp contract(off)`: the a-contrario loop, its storage, its sampling and
+// the exhaustive kernel are that header's. Here: the two P3P solvers, the form they give the exhaustive loop (ResP3PForm), the bounded
+// loop, and the host side of all three entries (ResCall and the res_* stages; mvgx_resection_dlt.h calls them with its own record).
+// What is restated here (paths under src/openMVG of the reference; the loop's own list is in mvgx_resection_loop.h):
 //   sfm/pipelines/localization/SfM_Localizer.cpp:31-343          ACKernelAdaptorResection_Intrinsics, SfM_Localizer::Localize
-//   robust_estimation/robust_estimator_ACRansac.hpp:257-304      the exhaustive NFA of one model
 //   robust_estimation/robust_estimator_ACRansac.hpp:205-256      the quantified NFA of one model (third_party/histogram/histogram.hpp)
-//   robust_estimation/robust_estimator_ACRansac.hpp:326-489      the a-contrario loop, its warm-up and early exit
-//   robust_estimation/rand_sampling.hpp:71-100                   UniformSample on the pool (three Fisher-Yates swaps at its head)
+//   robust_estimation/robust_estimator_ACRansac.hpp:326-489      the bounded loop's warm-up and early exit
 //   robust_estimation/rand_sampling.hpp:36-58                    UniformSample(3, nData, ...) of the warm-up (rejection)
 //   multiview/solver_resection_p3p_ding.cpp:33-325               P3PSolver_Ding
 //   multiview/solver_resection_p3p_nordberg.cpp:31-454           P3PSolver_Nordberg
 //   multiview/projection.cpp:40-132                              KRt_From_P (host)
-// Mapping ("Resection"): one workgroup runs one problem from start to end; each of its kResWaves waves evaluates one
-// iteration of a block of consecutive iterations ahead, under the pool and minNFA the block started with; the verdicts are read in
-// iteration order, the first event is applied and what was drawn after it is drawn again. No workgroup waits for another.
 #pragma once
-#include "ba_math.h"
-
-// The reference's build has no fused multiply-add. The solvers are ill-conditioned on some samples (a sample of the fixture moves by
-// 7e-11 under contraction, 20 times the distance between reference and restatement there), and the order of near-equal residuals
-// follows the last bits: everything in this file is compiled as separate products and sums. (Division and square root of doubles round
-// correctly on the device; cbrt, acos, cos and log10 are OCML's, within an ulp or two of glibc's.)
-// (A file-scope pragma holds to the end of the translation unit: this header is the last thing mvgx_geofilter.hip includes. In the
-// emulation's single unit the files included after it are compiled for a host without fused multiply-add, where it changes nothing.)
-#pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kResWaves = 8;                  // W: waves (= iterations evaluated ahead) per workgroup
 constexpr uint32_t kResLdsMaxN = 1024;        // largest n whose sort slices and tables live in LDS (DESIGN.md derives it)
-constexpr uint32_t kResMaxN = 65536;          // largest supported n
-constexpr int kResVerdict = 18;               // doubles per wave: better | nfa | k | error | P[12] | models evaluated | unused
 constexpr int kResSolverNordberg = 3, kResSolverDing = 4;   // resection::SolverType (multiview/solver_resection.hpp:15-24)
-constexpr double kResFltEps = 1.1920928955078125e-07;       // std::numeric_limits<float>::epsilon()
-constexpr int kResTraceRecord = 10;           // words of a trace record (test hook): iteration | k | the first 8 sorted indices
-__host__ __device__ constexpr uint32_t res_trace_words(uint32_t events) { return 1 + kResTraceRecord * events; }   // per problem: count | records
-// Test hook (mvgx_resection_debug_trace): where the next call leaves, per problem, the iterations that found a better model
-uint32_t* g_res_trace = nullptr;
-uint32_t g_res_trace_events = 0;
 
 struct ResProblem {       // per problem, prepared on the host (glibc's log10: the reference's value)
   uint64_t start;         // first correspondence, counted from the first problem's
@@ -46,11 +25,6 @@ struct ResProblem {       // per problem, prepared on the host (glibc's log10: t
   uint32_t n, model;
   double intr[8];
   double n1, loge0;       // imagePlane_toCameraPlaneError(1), log10(MAX_MODELS (n - 3))
-};
-struct ResResult {
-  double P[12];           // best model [R | t], row-major; valid if n_inliers > 0
-  double error_max, min_nfa;   // normalised squared residual at the chosen k; minNFA
-  uint32_t n_inliers, n_iterations, n_models, pad_;
 };
 
 struct ResV3 { double x, y, z; };
@@ -395,296 +369,62 @@ __global__ __launch_bounds__(256) void resection_bearing_kernel(const ResProblem
                                                                 const double* __restrict__ x2d, double* __restrict__ bear) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_total) return;
-  uint32_t lo = 0, hi = n_problems - 1;   // the last problem that starts at or before i and is not empty there
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) / 2;
-    if (problems[mid].start <= i) lo = mid; else hi = mid - 1;
-  }
-  const ResProblem& P = problems[lo];
+  const ResProblem& P = res_problem_of(problems, n_problems, i);
   double b[3];
   mvgx_ba::camera_bearing((int)P.model, P.intr, x2d + 2 * i, /*undistort=*/false, b);
   bear[3 * i] = b[0]; bear[3 * i + 1] = b[1]; bear[3 * i + 2] = b[2];
 }
 
-// ---- the loop ----
-// words of LDS a workgroup needs: generator | its copy | verdicts | models | samples, swaps, counts | best model | (LDS form) pool, inliers, logc_n, logc_k, slices
-__host__ __device__ constexpr uint32_t res_fixed_words() { return 2 * kMtN + 2 * kResWaves * kResVerdict + 2 * kResWaves * 48 + 8 * kResWaves + 24; }
-__host__ __device__ constexpr uint32_t res_table_words(uint32_t n) { return 4 * (n + 1); }    // pool, inliers, logc_n, logc_k (n + 1 each)
-__host__ __device__ constexpr uint32_t res_slice_words(uint32_t p2) { return 3 * p2; }         // keys (64 bit) | indices
-__host__ __device__ inline uint32_t res_pow2(uint32_t n) { uint32_t p = 64; while (p < n) p <<= 1; return p; }   // the sort's length: n padded with +inf
-inline size_t res_scratch_bytes(uint32_t n) { return ((size_t)4 * (res_table_words(n) + kResWaves * res_slice_words(res_pow2(n))) + 255) / 256 * 256; }
-inline uint32_t res_lds_bytes(uint32_t n_lds_max) { return 4 * (res_fixed_words() + (n_lds_max ? res_table_words(n_lds_max) + kResWaves * res_slice_words(res_pow2(n_lds_max)) : 0)); }
-
-struct ResKeyIdx { uint64_t key; uint32_t idx; };
-// (residual bits, index) ascending: residuals are non-negative or +inf, so the bit patterns order as the values do
-__device__ __forceinline__ bool res_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
-  return ka < kb || (ka == kb && ia < ib);
-}
-
-// bitonic sort of p2 (a power of two >= 64) records by one wave; every stage ends with the wave's writes visible to its lanes. In the
-// global form the slice is global memory: wave_sync's wavefront-scope fence covers every address space (the compiler waits for the
-// stores), and a CU's vector memory path serves one wave's accesses to an address in order, so the next stage's loads see them.
-__device__ __forceinline__ void res_sort(uint64_t* keys, uint32_t* idx, uint32_t p2, int lane) {
-  for (uint32_t k = 2; k <= p2; k <<= 1) {
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = lane; t < p2 / 2; t += 64) {
-        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const uint64_t ki = keys[i], kl = keys[l];
-        const uint32_t ii = idx[i], il = idx[l];
-        const bool up = (i & k) == 0;
-        if (res_less(kl, il, ki, ii) == up) { keys[i] = kl; keys[l] = ki; idx[i] = il; idx[l] = ii; }
-      }
-      wave_sync();
+// ---- what the P3P solvers give the loop (both the exhaustive kernel of mvgx_resection_loop.h and the bounded one below) ----
+struct ResP3PForm {
+  using Problem = ResProblem;
+  using Layout = ResLayout<3, kResVerdict, 48, 0, true>;   // a wave's work: up to four [R | t]
+  static constexpr int kSample = 3, kMaxModels = 4, kModelAt = 0;
+  const double2* px;
+  const double *pX, *pb, *intr;
+  double n1norm;
+  int res_model, solver;
+  __device__ __forceinline__ ResP3PForm(const ResProblem& P, const double* __restrict__ x2d, const double* __restrict__ X3d, const double* __restrict__ bear, int solver_)
+      : px(reinterpret_cast<const double2*>(x2d) + P.start), pX(X3d + 3 * P.start), pb(bear + 3 * P.start), intr(P.intr), n1norm(P.n1),
+        res_model(P.model == (uint32_t)mvgx_ba::kCamSpherical ? mvgx_ba::kCamSpherical : mvgx_ba::kCamPinhole),   // ignore_distortion
+        solver(solver_) {}
+  // the sample's vectors go to the wave's verdict slot (its first 18 doubles), read by lane 0's solve before the verdict is written
+  __device__ __forceinline__ void load_sample(const uint32_t* sample, double*, double* verdict, int lane) const {
+    if (lane < 3) {
+      const uint32_t s = sample[lane];
+      verdict[3 * lane] = pb[3 * s]; verdict[3 * lane + 1] = pb[3 * s + 1]; verdict[3 * lane + 2] = pb[3 * s + 2];
+      verdict[9 + 3 * lane] = pX[3 * s]; verdict[9 + 3 * lane + 1] = pX[3 * s + 1]; verdict[9 + 3 * lane + 2] = pX[3 * s + 2];
     }
   }
-}
-
-template <bool kGlobal>
-__global__ __launch_bounds__(64 * kResWaves) void resection_acransac_kernel(const ResProblem* __restrict__ problems, const uint32_t* __restrict__ order, uint32_t n_work,
-                                                                            const double* __restrict__ x2d, const double* __restrict__ X3d, const double* __restrict__ bear,
-                                                                            const float* __restrict__ l10, const uint32_t* __restrict__ mt_init, uint32_t max_iteration,
-                                                                            int solver, uint32_t waves_ahead, uint32_t n_lds_max, unsigned char* __restrict__ scratch,
-                                                                            ResResult* __restrict__ results, uint32_t* __restrict__ inliers_out, uint32_t* __restrict__ trace, uint32_t trace_events) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_u32[];
-  if (blockIdx.x >= n_work) return;
-  const uint32_t pi = order[blockIdx.x];
-  const ResProblem& P = problems[pi];
-  const uint32_t n = P.n, p2 = res_pow2(n);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n_threads = 64 * kResWaves;
-
-  uint32_t* const mt = lds_u32;
-  uint32_t* const mt_saved = mt + kMtN;
-  double* const verdicts = reinterpret_cast<double*>(mt_saved + kMtN);
-  double* const models = verdicts + kResWaves * kResVerdict;        // 48 doubles per wave
-  uint32_t* const samples = reinterpret_cast<uint32_t*>(models + kResWaves * 48);   // 3 per wave | swap partners, 3 per wave | models per wave
-  uint32_t* const swaps = samples + 3 * kResWaves;
-  uint32_t* const n_mod = swaps + 3 * kResWaves;
-  double* const best_model = reinterpret_cast<double*>(samples + 8 * kResWaves);   // the winning [R | t] (thread 0 writes and reads it)
-  uint32_t* const tables = kGlobal ? reinterpret_cast<uint32_t*>(scratch + P.scratch) : lds_u32 + res_fixed_words();
-  const uint32_t n1 = n + 1;
-  uint32_t* const pool = tables;
-  uint32_t* const inliers = pool + n1;
-  float* const logc_n = reinterpret_cast<float*>(inliers + n1);
-  float* const logc_k = logc_n + n1;
-  uint32_t* const slices = tables + res_table_words(kGlobal ? n : n_lds_max);
-  const uint32_t slice_words = res_slice_words(kGlobal ? p2 : res_pow2(n_lds_max));   // LDS form: every wave's slice is sized for the launch's largest problem
-  uint64_t* const my_keys = reinterpret_cast<uint64_t*>(slices + (size_t)wave * slice_words);
-  uint32_t* const my_idx = reinterpret_cast<uint32_t*>(my_keys + p2);
-
-  const double2* const px = reinterpret_cast<const double2*>(x2d) + P.start;
-  const double* const pX = X3d + 3 * P.start;
-  const double* const pb = bear + 3 * P.start;
-  const double n1norm = P.n1, loge0 = P.loge0;
-  const double logalpha0 = 0.49714987269413385;   // log10(M_PI)
-  const int res_model = P.model == (uint32_t)mvgx_ba::kCamSpherical ? mvgx_ba::kCamSpherical : mvgx_ba::kCamPinhole;   // ignore_distortion
-
-  // tables and generator
-  for (uint32_t k = tid; k <= n; k += n_threads) {
-    pool[k] = k;
-    logc_k[k] = logcombi(3, k, l10);
+  __device__ __forceinline__ int solve(double* work, const double* verdict, uint32_t* count, int lane) const {
+    if (lane == 0) *count = (uint32_t)res_solve(solver, verdict, verdict + 9, work);
+    wave_sync();
+    return (int)*count;
   }
-  // logc_n[k] = logcombi(k, n) is the running float sum of min(k, n - k) terms that do not depend on k: one pass of n / 2 dependent
-  // additions by one thread (the sum's order is the reference's; n calls of logcombi would be n^2 / 4 additions), then the mirror
-  if (tid == 0) {
-    float r = 0.f;
-    logc_n[0] = 0.f;
-    for (uint32_t i = 1; i <= n / 2; ++i) { r += l10[n - i + 1] - l10[i]; logc_n[i] = r; }
+  // the normalised squared residual of correspondence i under M (every pass of both loops goes through here, so a residual has the
+  // same bits wherever it is compared)
+  __device__ __forceinline__ double residual(const ResRt& M, uint32_t i) const {
+    const double X = pX[3 * i], Y = pX[3 * i + 1], Z = pX[3 * i + 2];
+    const double pc[3] = {M.m0 * X + M.m1 * Y + M.m2 * Z + M.m3, M.m4 * X + M.m5 * Y + M.m6 * Z + M.m7, M.m8 * X + M.m9 * Y + M.m10 * Z + M.m11};
+    const double2 obs = px[i];
+    const double ob[2] = {obs.x, obs.y};
+    double r[2];
+    mvgx_ba::project_residual(res_model, intr, pc, ob, r);
+    const double rx = mul_rn(r[0], n1norm), ry = mul_rn(r[1], n1norm);
+    return add_rn(mul_rn(rx, rx), mul_rn(ry, ry));
   }
-  __syncthreads();
-  for (uint32_t k = n / 2 + 1 + tid; k <= n; k += n_threads) logc_n[k] = k >= n ? 0.f : logc_n[n - k];
-  for (int i = tid; i < kMtN; i += n_threads) mt[i] = mt_init[i];
-  int mt_idx = kMtN, mt_idx_saved = kMtN;   // (tracked by wave 0 alone)
-  __syncthreads();
-
-  const uint32_t Wa = waves_ahead ? waves_ahead : (uint32_t)kResWaves;
-  double minNFA = INFINITY, errorMax = INFINITY;
-  if (tid == 0)
-    for (int e = 0; e < 12; ++e) best_model[e] = 0.0;
-  uint32_t n_inl = 0, pool_n = n;
-  int nIterReserve = (int)(max_iteration / 10);
-  uint32_t nIter = max_iteration - (uint32_t)nIterReserve;
-  uint32_t iter = 0, n_models_total = 0;
-
-  while (iter < nIter && iter < max_iteration) {
-    const uint32_t nb = min(Wa, min(nIter - iter, max_iteration - iter));
-    // ---- the samples of the block, drawn in iteration order from the one generator (wave 0) ----
-    if (wave == 0) {
-      for (int i = lane; i < kMtN; i += 64) mt_saved[i] = mt[i];   // (a twist cannot be taken back: the state before the block is kept)
-      wave_sync();
-      mt_idx_saved = mt_idx;
-      for (uint32_t j = 0; j < nb; ++j) {
-        for (uint32_t i = 0; i < 3; ++i) {
-          const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
-          if (lane == 0) {   // (lane 0 alone reads and writes the pool here)
-            const uint32_t a = pool[i], b = pool[r];
-            pool[i] = b; pool[r] = a;
-            swaps[3 * j + i] = r;
-          }
-        }
-        if (lane == 0) { samples[3 * j] = pool[0]; samples[3 * j + 1] = pool[1]; samples[3 * j + 2] = pool[2]; }
-      }
-    }
-    __syncthreads();
-
-    // ---- one wave, one iteration ----
-    if ((uint32_t)wave < nb) {
-      double* const my_models = models + 48 * wave;
-      // the sample's vectors in the wave's verdict slot (18 doubles), read by lane 0's solve before the verdict is written
-      double* const my_verdict = verdicts + kResVerdict * wave;
-      if (lane < 3) {
-        const uint32_t s = samples[3 * wave + lane];
-        my_verdict[3 * lane] = pb[3 * s]; my_verdict[3 * lane + 1] = pb[3 * s + 1]; my_verdict[3 * lane + 2] = pb[3 * s + 2];
-        my_verdict[9 + 3 * lane] = pX[3 * s]; my_verdict[9 + 3 * lane + 1] = pX[3 * s + 1]; my_verdict[9 + 3 * lane + 2] = pX[3 * s + 2];
-      }
-      wave_sync();
-      if (lane == 0) n_mod[wave] = (uint32_t)res_solve(solver, my_verdict, my_verdict + 9, my_models);
-      wave_sync();
-      const int nm = (int)n_mod[wave];
-      double run_min = minNFA, win_err = 0.0;
-      int winner = -1, sorted = -1;
-      uint32_t win_k = 0, evaluated = 0;
-      for (int m = 0; m <= nm; ++m) {
-        // m == nm: the winner's order once more, if a later model of the iteration was sorted over it
-        const int mm = m < nm ? m : winner;
-        if (m == nm && (winner < 0 || winner == sorted)) break;
-        const double* const M = my_models + 12 * mm;
-        const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5], m6 = M[6], m7 = M[7], m8 = M[8], m9 = M[9], m10 = M[10], m11 = M[11];
-        // a model with a non-finite entry is skipped (the reference would sort NaNs: undefined)
-        const double probe = m0 + m1 + m2 + m3 + m4 + m5 + m6 + m7 + m8 + m9 + m10 + m11;
-        if (!(fabs(probe) < INFINITY)) continue;
-        for (uint32_t i = lane; i < p2; i += 64) {
-          double e = INFINITY;
-          if (i < n) {
-            const double X = pX[3 * i], Y = pX[3 * i + 1], Z = pX[3 * i + 2];
-            const double pc[3] = {m0 * X + m1 * Y + m2 * Z + m3, m4 * X + m5 * Y + m6 * Z + m7, m8 * X + m9 * Y + m10 * Z + m11};
-            const double2 obs = px[i];
-            const double ob[2] = {obs.x, obs.y};
-            double r[2];
-            mvgx_ba::project_residual(res_model, P.intr, pc, ob, r);
-            const double rx = mul_rn(r[0], n1norm), ry = mul_rn(r[1], n1norm);
-            e = add_rn(mul_rn(rx, rx), mul_rn(ry, ry));
-            if (!(e < INFINITY)) e = INFINITY;   // NaN too
-          }
-          my_keys[i] = (uint64_t)__double_as_longlong(e);
-          my_idx[i] = i;
-        }
-        wave_sync();
-        res_sort(my_keys, my_idx, p2, lane);
-        sorted = mm;
-        if (m == nm) break;
-        ++evaluated;
-        // NFA(k) for every k in [4, n]: the smallest, the lowest k among equals
-        double best = INFINITY;
-        uint32_t best_k = 3;
-        for (uint32_t k = 4 + lane; k <= n; k += 64) {
-          const double r = __longlong_as_double((long long)my_keys[k - 1]);
-          const double logalpha = add_rn(logalpha0, log10(add_rn(r, kResFltEps)));
-          const double nfa = add_rn(add_rn(add_rn(loge0, mul_rn(logalpha, (double)(k - 3))), (double)logc_n[k]), (double)logc_k[k]);
-          if (nfa < best) { best = nfa; best_k = k; }
-        }
-        for (int d = 32; d > 0; d >>= 1) {
-          const double o = __shfl_xor(best, d);
-          const uint32_t ok = (uint32_t)__shfl_xor((int)best_k, d);
-          if (o < best || (o == best && ok < best_k)) { best = o; best_k = ok; }
-        }
-        if (best < run_min) {
-          run_min = best; winner = mm; win_k = best_k;
-          win_err = __longlong_as_double((long long)my_keys[best_k - 1]);
-        }
-      }
-      wave_sync();   // every lane has read the sample's vectors and the keys before the verdict overwrites the slot
-      if (lane == 0) {
-        my_verdict[0] = winner >= 0 ? 1.0 : 0.0;
-        my_verdict[1] = run_min; my_verdict[2] = (double)win_k; my_verdict[3] = win_err;
-        const double* const M = my_models + 12 * (winner >= 0 ? winner : 0);
-        for (int e = 0; e < 12; ++e) my_verdict[4 + e] = M[e];
-        my_verdict[16] = (double)evaluated;
-      }
-    }
-    __syncthreads();
-
-    // ---- the verdicts in iteration order: the first event is applied, what follows it is void ----
-    uint32_t done = nb;
-    bool event = false;
-    for (uint32_t j = 0; j < nb && !event; ++j) {
-      const double* const v = verdicts + kResVerdict * j;
-      n_models_total += (uint32_t)v[16];
-      const bool better = v[0] != 0.0;   // (evaluated under the block's minNFA, which no earlier verdict of the block has changed)
-      if (better) {
-        minNFA = v[1]; errorMax = v[3]; n_inl = (uint32_t)v[2];
-        if (tid == 0)
-          for (int e = 0; e < 12; ++e) best_model[e] = v[4 + e];
-        const uint32_t* const src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint64_t*>(slices + (size_t)j * slice_words) + p2);
-        for (uint32_t i = tid; i < n_inl; i += n_threads) inliers[i] = src[i];
-        if (trace && tid == 0) {   // test hook: iteration | k | the head of the sorted list, one record per iteration that found a better model
-          uint32_t* const T = trace + (size_t)pi * res_trace_words(trace_events);
-          const uint32_t at = T[0];
-          if (at < trace_events) {
-            uint32_t* const rec = T + 1 + (size_t)kResTraceRecord * at;
-            rec[0] = iter + j; rec[1] = n_inl;
-            for (uint32_t i = 0; i < (uint32_t)kResTraceRecord - 2; ++i) rec[2 + i] = i < n_inl ? src[i] : 0xffffffffu;
-          }
-          T[0] = at + 1;
-        }
-      }
-      const bool branch = (better && minNFA < 0) || ((iter + j + 1) == nIter && nIterReserve > 0);
-      bool take_pool = false;
-      if (branch) {
-        if (n_inl == 0) { ++nIter; --nIterReserve; }
-        else {
-          take_pool = true;
-          if (nIterReserve) { nIter = iter + j + 1 + (uint32_t)nIterReserve; nIterReserve = 0; }
-        }
-      }
-      if (better || branch) {
-        event = true;
-        done = j + 1;
-        __syncthreads();   // the inlier list is complete; wave 0 may touch the pool
-        if (done < nb && wave == 0) {
-          // the generator and the pool as they stood after iteration j: undo the block's swaps, restore the state, draw j + 1 again
-          if (lane == 0)
-            for (int s = 3 * (int)nb - 1; s >= 0; --s) {
-              const uint32_t i = (uint32_t)s % 3, r = swaps[s];
-              const uint32_t a = pool[i], b = pool[r];
-              pool[i] = b; pool[r] = a;
-            }
-          for (int i = lane; i < kMtN; i += 64) mt[i] = mt_saved[i];
-          wave_sync();
-          mt_idx = mt_idx_saved;
-          for (uint32_t jj = 0; jj < done; ++jj)
-            for (uint32_t i = 0; i < 3; ++i) {
-              const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
-              if (lane == 0) { const uint32_t a = pool[i], b = pool[r]; pool[i] = b; pool[r] = a; }
-            }
-        }
-        __syncthreads();
-        if (take_pool) {   // vec_index = vec_inliers: in sorted order
-          for (uint32_t i = tid; i < n_inl; i += n_threads) pool[i] = inliers[i];
-          pool_n = n_inl;
-        }
-      }
-    }
-    iter += done;
-    __syncthreads();
-  }
-
-  if (minNFA >= 0) n_inl = 0;   // no meaningful model
-  for (uint32_t i = tid; i < n_inl; i += n_threads) inliers_out[P.start + i] = inliers[i];
-  if (tid == 0) {
-    ResResult& R = results[pi];
-    for (int e = 0; e < 12; ++e) R.P[e] = best_model[e];
-    R.error_max = errorMax; R.min_nfa = minNFA; R.n_inliers = n_inl; R.n_iterations = iter; R.n_models = n_models_total; R.pad_ = 0;
-  }
-}
+};
+static_assert(4 * ResP3PForm::Layout::words(kResLdsMaxN) <= 160 * 1024, "the LDS form must fit a workgroup's 160 KiB");
 
 // ---- the bounded form (mvgx_resection_localize_bounded): a finite precision ----
 // robust_estimator_ACRansac.hpp:205-256 (the NFA read off a 20-bin histogram), :351-358, :375, :386-389 (the warm-up's rejection sampler,
 // rand_sampling.hpp:36-58), :402-413 (max-consensus until a model has more than 2.5 x 3 residuals inside the bound), :446-452 (the early
 // exit). No sort: per model n residuals, 20 counters and, for a model that lowers minNFA, one list in index order. The mapping is the
-// loop's above - one workgroup per problem, one wave per iteration evaluated ahead - with two more kinds of event: the switch to the
-// a-contrario mode, and a list that was rebuilt but came out too short to count as a better model (:243-255).
-// Deliberate differences: a model with a non-finite entry is skipped (as above); an adopted pool of fewer than three entries stops the
+// exhaustive loop's - one workgroup per problem, one wave per iteration evaluated ahead - and the kernel is built from the pieces of
+// mvgx_resection_loop.h (layout, tables, draw and rewind, budget, result) and ResP3PForm's sample, solver and residual. Its own: the
+// verdicts, with two more kinds of event - the switch to the a-contrario mode, and a list that was rebuilt but came out too short to
+// count as a better model (:243-255) -, the warm-up's sampler and the early exit.
+// Deliberate differences: a model with a non-finite entry is skipped (as in the exhaustive loop); an adopted pool of fewer than three entries stops the
 // problem with its current result (the reference's sampler returns false there, unchecked, and the stale sample is evaluated again).
 constexpr uint32_t kResBLdsMaxN = 8192;       // largest n whose four tables live in LDS (DESIGN.md derives it)
 constexpr int kResBVerdict = 32;              // doubles per wave: flags | nfa | threshold | unused | P[12] | models evaluated | list threshold | list P[12] | unused
@@ -694,28 +434,10 @@ struct ResBound {         // per problem, prepared on the host (glibc's log10)
   double bin_value[kBins];                  // (max_threshold / 19) b: histogram.hpp:105-112, not the bins' edges
   double logalpha_bin[kBins];               // logalpha0 + log10(bin_value + FLT_EPSILON)
 };
-// words of LDS: generator | its copy | verdicts | models | samples, swaps, counts | histograms | compaction counts (two sets) | best model | (LDS form) tables
-__host__ __device__ constexpr uint32_t resb_fixed_words() {
-  return 2 * kMtN + 2 * kResWaves * kResBVerdict + 2 * kResWaves * 48 + 8 * kResWaves + kResWaves * kBins + 2 * kResWaves + 24;
-}
-inline size_t resb_scratch_bytes(uint32_t n) { return ((size_t)4 * res_table_words(n) + 255) / 256 * 256; }
-inline uint32_t resb_lds_bytes(uint32_t n_lds_max) { return 4 * (resb_fixed_words() + (n_lds_max ? res_table_words(n_lds_max) : 0)); }
+// the layout's extra words: histograms (kBins counters per wave) | resb_rebuild_list's counts (two sets); no sort slices
+using ResBLayout = ResLayout<3, kResBVerdict, 48, kResWaves * kBins + 2 * kResWaves, false>;
+static_assert(4 * ResBLayout::words(kResBLdsMaxN) <= 160 * 1024, "the LDS form must fit a workgroup's 160 KiB");
 
-struct ResRt { double m0, m1, m2, m3, m4, m5, m6, m7, m8, m9, m10, m11; };
-__device__ __forceinline__ ResRt res_rt_load(const double* __restrict__ M) { return {M[0], M[1], M[2], M[3], M[4], M[5], M[6], M[7], M[8], M[9], M[10], M[11]}; }
-// the residual of correspondence i under M: the expression of the loop above, term for term (every pass of the bounded form goes
-// through here, so a residual has the same bits wherever it is compared)
-__device__ __forceinline__ double res_error_of(const ResRt& M, int res_model, const double* __restrict__ intr, double n1norm, const double* __restrict__ pX,
-                                               const double2* __restrict__ px, uint32_t i) {
-  const double X = pX[3 * i], Y = pX[3 * i + 1], Z = pX[3 * i + 2];
-  const double pc[3] = {M.m0 * X + M.m1 * Y + M.m2 * Z + M.m3, M.m4 * X + M.m5 * Y + M.m6 * Z + M.m7, M.m8 * X + M.m9 * Y + M.m10 * Z + M.m11};
-  const double2 obs = px[i];
-  const double ob[2] = {obs.x, obs.y};
-  double r[2];
-  mvgx_ba::project_residual(res_model, intr, pc, ob, r);
-  const double rx = mul_rn(r[0], n1norm), ry = mul_rn(r[1], n1norm);
-  return add_rn(mul_rn(rx, rx), mul_rn(ry, ry));
-}
 // UniformSample(3, nData, ...) (rand_sampling.hpp:36-58): three distinct indices of [0, n - 1], a repeated one drawn again (n > 3 here)
 __device__ __forceinline__ void resb_draw_distinct(uint32_t* mt, int& mt_idx, int lane, uint32_t n, uint32_t& c0, uint32_t& c1, uint32_t& c2) {
   c0 = uniform_u32(mt, mt_idx, lane, 0, n - 1);
@@ -724,13 +446,12 @@ __device__ __forceinline__ void resb_draw_distinct(uint32_t* mt, int& mt_idx, in
 }
 // the inlier list of (M, thr) by the whole workgroup: the indices with e <= thr in index order. 512 consecutive indices per round: a
 // ballot and a count per wave, the prefix over the eight waves' counts (two sets of counts: one barrier per round). Returns the length.
-__device__ __forceinline__ uint32_t resb_rebuild_list(const ResRt& M, double thr, int res_model, const double* __restrict__ intr, double n1norm, const double* __restrict__ pX,
-                                                      const double2* __restrict__ px, uint32_t n, uint32_t* inliers, uint32_t* wcount, int tid) {
+__device__ __forceinline__ uint32_t resb_rebuild_list(const ResP3PForm& F, const ResRt& M, double thr, uint32_t n, uint32_t* inliers, uint32_t* wcount, int tid) {
   const int lane = tid & 63, wave = tid >> 6;
   uint32_t total = 0, set = 0;
   for (uint32_t base = 0; base < n; base += 64 * kResWaves, set ^= (uint32_t)kResWaves) {
     const uint32_t i = base + (uint32_t)tid;
-    const bool in = i < n && res_error_of(M, res_model, intr, n1norm, pX, px, i) <= thr;   // (a NaN is no inlier)
+    const bool in = i < n && F.residual(M, i) <= thr;   // (a NaN is no inlier)
     const unsigned long long bal = __ballot(in);
     if (lane == 0) wcount[set + wave] = (uint32_t)__popcll(bal);
     __syncthreads();
@@ -748,98 +469,60 @@ __device__ __forceinline__ uint32_t resb_rebuild_list(const ResRt& M, double thr
   return total;
 }
 
+// (n_lds_max is not read: without slices nothing is sized for the launch's largest problem; the launcher passes it to every loop kernel)
 template <bool kGlobal>
-__global__ __launch_bounds__(64 * kResWaves) void resection_acransac_bounded_kernel(const ResProblem* __restrict__ problems, const ResBound* __restrict__ bounds,
-                                                                                    const uint32_t* __restrict__ order, uint32_t n_work, const double* __restrict__ x2d,
-                                                                                    const double* __restrict__ X3d, const double* __restrict__ bear, const float* __restrict__ l10,
-                                                                                    const uint32_t* __restrict__ mt_init, uint32_t max_iteration, int solver, uint32_t waves_ahead,
-                                                                                    unsigned char* __restrict__ scratch, ResResult* __restrict__ results, uint32_t* __restrict__ inliers_out) {
+__global__ __launch_bounds__(64 * kResWaves) void resection_acransac_bounded_kernel(const uint32_t* __restrict__ order, uint32_t n_work, uint32_t /*n_lds_max*/,
+                                                                                    const ResProblem* __restrict__ problems, const ResBound* __restrict__ bounds,
+                                                                                    const double* __restrict__ x2d, const double* __restrict__ X3d, const double* __restrict__ bear,
+                                                                                    const float* __restrict__ l10, const uint32_t* __restrict__ mt_init, uint32_t max_iteration, int solver,
+                                                                                    uint32_t waves_ahead, unsigned char* __restrict__ scratch, ResResult* __restrict__ results,
+                                                                                    uint32_t* __restrict__ inliers_out) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_u32[];
   if (blockIdx.x >= n_work) return;
+  using L = ResBLayout;
   const uint32_t pi = order[blockIdx.x];
   const ResProblem& P = problems[pi];
   const ResBound& B = bounds[pi];
   const uint32_t n = P.n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n_threads = 64 * kResWaves;
 
-  uint32_t* const mt = lds_u32;
-  uint32_t* const mt_saved = mt + kMtN;
-  double* const verdicts = reinterpret_cast<double*>(mt_saved + kMtN);
-  double* const models = verdicts + kResWaves * kResBVerdict;       // 48 doubles per wave
-  uint32_t* const samples = reinterpret_cast<uint32_t*>(models + kResWaves * 48);   // 3 per wave | swap partners, 3 per wave | models per wave
-  uint32_t* const swaps = samples + 3 * kResWaves;
-  uint32_t* const n_mod = swaps + 3 * kResWaves;
-  uint32_t* const hists = samples + 8 * kResWaves;                  // kBins counters per wave
-  uint32_t* const wcount = hists + kResWaves * kBins;               // resb_rebuild_list's counts
-  double* const best_model = reinterpret_cast<double*>(wcount + 2 * kResWaves);   // the winning [R | t] (thread 0 writes and reads it)
-  uint32_t* const tables = kGlobal ? reinterpret_cast<uint32_t*>(scratch + P.scratch) : lds_u32 + resb_fixed_words();
-  const uint32_t n1 = n + 1;
-  uint32_t* const pool = tables;
-  uint32_t* const inliers = pool + n1;
-  float* const logc_n = reinterpret_cast<float*>(inliers + n1);
-  float* const logc_k = logc_n + n1;
+  const L lds(lds_u32);
+  const ResTables T = res_tables(kGlobal ? reinterpret_cast<uint32_t*>(scratch + P.scratch) : lds.tables, n, n, L::kHasSlices);
+  uint32_t* const hists = lds.extra;                          // kBins counters per wave
+  uint32_t* const wcount = hists + kResWaves * kBins;         // resb_rebuild_list's counts
   uint32_t* const my_hist = hists + kBins * wave;
 
-  const double2* const px = reinterpret_cast<const double2*>(x2d) + P.start;
-  const double* const pX = X3d + 3 * P.start;
-  const double* const pb = bear + 3 * P.start;
-  const double n1norm = P.n1, loge0 = P.loge0;
+  const ResP3PForm F(P, x2d, X3d, bear, solver);   // the exhaustive loop's sample, solver and residual
+  const double loge0 = P.loge0;
   const double max_threshold = B.max_threshold, bins_by_interval = B.bins_by_interval;
   const double my_bin_value = lane < kBins ? B.bin_value[lane] : 0.0, my_logalpha = lane < kBins ? B.logalpha_bin[lane] : 0.0;
-  const int res_model = P.model == (uint32_t)mvgx_ba::kCamSpherical ? mvgx_ba::kCamSpherical : mvgx_ba::kCamPinhole;   // ignore_distortion
 
-  // tables and generator (as above)
-  for (uint32_t k = tid; k <= n; k += n_threads) {
-    pool[k] = k;
-    logc_k[k] = logcombi(3, k, l10);
-  }
-  if (tid == 0) {
-    float r = 0.f;
-    logc_n[0] = 0.f;
-    for (uint32_t i = 1; i <= n / 2; ++i) { r += l10[n - i + 1] - l10[i]; logc_n[i] = r; }
-  }
-  __syncthreads();
-  for (uint32_t k = n / 2 + 1 + tid; k <= n; k += n_threads) logc_n[k] = k >= n ? 0.f : logc_n[n - k];
-  for (int i = tid; i < kMtN; i += n_threads) mt[i] = mt_init[i];
-  int mt_idx = kMtN, mt_idx_saved = kMtN;   // (tracked by wave 0 alone)
-  __syncthreads();
+  ResGen gen{lds.mt, lds.mt_saved, kMtN, kMtN};
+  res_tables_init<3>(T, gen, mt_init, l10, n, tid);
 
   const uint32_t Wa = waves_ahead ? waves_ahead : (uint32_t)kResWaves;
   double minNFA = INFINITY, errorMax = INFINITY;
   if (tid == 0)
-    for (int e = 0; e < 12; ++e) best_model[e] = 0.0;
+    for (int e = 0; e < 12; ++e) lds.best_model[e] = 0.0;
   bool ac = false, stop = false;   // bACRansacMode; an adopted pool was too small to sample from
   uint32_t n_inl = 0, pool_n = n;  // the length of vec_inliers, of vec_index
-  int nIterReserve = (int)(max_iteration / 10);
-  uint32_t nIter = max_iteration - (uint32_t)nIterReserve;
-  uint32_t iter = 0, n_models_total = 0;
+  uint32_t n_models_total = 0;
+  ResBudget it(max_iteration);
 
-  while (!stop && iter < nIter && iter < max_iteration) {
-    uint32_t nb = min(Wa, min(nIter - iter, max_iteration - iter));
+  while (!stop && it.running()) {
+    uint32_t nb = it.block(Wa);
     // the warm-up gives up after iteration 2 nIterReserve + 1 (:448): nothing is evaluated ahead past it
-    if (!ac) nb = min(nb, 2u * (uint32_t)nIterReserve + 2u - iter);
+    if (!ac) nb = min(nb, 2u * (uint32_t)it.nIterReserve + 2u - it.iter);
     const bool ac_at_start = ac;
     // ---- the samples of the block, drawn in iteration order from the one generator (wave 0), in the block's mode ----
     if (wave == 0) {
-      for (int i = lane; i < kMtN; i += 64) mt_saved[i] = mt[i];
-      wave_sync();
-      mt_idx_saved = mt_idx;
-      for (uint32_t j = 0; j < nb; ++j) {
-        if (ac) {
-          for (uint32_t i = 0; i < 3; ++i) {
-            const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
-            if (lane == 0) {   // (lane 0 alone reads and writes the pool here)
-              const uint32_t a = pool[i], b = pool[r];
-              pool[i] = b; pool[r] = a;
-              swaps[3 * j + i] = r;
-            }
-          }
-          if (lane == 0) { samples[3 * j] = pool[0]; samples[3 * j + 1] = pool[1]; samples[3 * j + 2] = pool[2]; }
-        } else {   // the warm-up never touches the pool
+      if (ac) res_draw_block<3>(gen, T.pool, pool_n, lds.swaps, lds.samples, nb, lane);
+      else {   // the warm-up never touches the pool
+        gen.save(lane);
+        for (uint32_t j = 0; j < nb; ++j) {
           uint32_t c0, c1, c2;
-          resb_draw_distinct(mt, mt_idx, lane, n, c0, c1, c2);
-          if (lane == 0) { samples[3 * j] = c0; samples[3 * j + 1] = c1; samples[3 * j + 2] = c2; }
+          resb_draw_distinct(gen.mt, gen.idx, lane, n, c0, c1, c2);
+          if (lane == 0) { lds.samples[3 * j] = c0; lds.samples[3 * j + 1] = c1; lds.samples[3 * j + 2] = c2; }
         }
       }
     }
@@ -847,34 +530,25 @@ __global__ __launch_bounds__(64 * kResWaves) void resection_acransac_bounded_ker
 
     // ---- one wave, one iteration ----
     if ((uint32_t)wave < nb) {
-      double* const my_models = models + 48 * wave;
-      // the sample's vectors in the wave's verdict slot, read by lane 0's solve before the verdict is written
-      double* const my_verdict = verdicts + kResBVerdict * wave;
-      if (lane < 3) {
-        const uint32_t s = samples[3 * wave + lane];
-        my_verdict[3 * lane] = pb[3 * s]; my_verdict[3 * lane + 1] = pb[3 * s + 1]; my_verdict[3 * lane + 2] = pb[3 * s + 2];
-        my_verdict[9 + 3 * lane] = pX[3 * s]; my_verdict[9 + 3 * lane + 1] = pX[3 * s + 1]; my_verdict[9 + 3 * lane + 2] = pX[3 * s + 2];
-      }
+      double* const my_models = lds.works + L::kWork * wave;
+      double* const my_verdict = lds.verdicts + L::kVerdict * wave;
+      F.load_sample(lds.samples + 3 * wave, my_models, my_verdict, lane);
       wave_sync();
-      if (lane == 0) n_mod[wave] = (uint32_t)res_solve(solver, my_verdict, my_verdict + 9, my_models);
-      wave_sync();
-      const int nm = (int)n_mod[wave];
+      const int nm = F.solve(my_models, my_verdict, lds.n_mod + wave, lane);
       bool my_ac = ac;
       double run_min = minNFA, win_thr = 0.0, list_thr = 0.0;
       int winner = -1, lister = -1;
       uint32_t evaluated = 0, flags = 0;
       for (int m = 0; m < nm; ++m) {
         const ResRt M = res_rt_load(my_models + 12 * m);
-        // a model with a non-finite entry is skipped
-        const double probe = M.m0 + M.m1 + M.m2 + M.m3 + M.m4 + M.m5 + M.m6 + M.m7 + M.m8 + M.m9 + M.m10 + M.m11;
-        if (!(fabs(probe) < INFINITY)) continue;
+        if (!res_rt_finite(M)) continue;
         ++evaluated;
         if (lane < kBins) my_hist[lane] = 0;
         wave_sync();
         uint32_t n_le = 0;
         for (uint32_t base = 0; base < n; base += 64) {
           const uint32_t i = base + lane;
-          const double e = i < n ? res_error_of(M, res_model, P.intr, n1norm, pX, px, i) : INFINITY;
+          const double e = i < n ? F.residual(M, i) : INFINITY;
           if (!my_ac) n_le += (uint32_t)__popcll(__ballot(i < n && e <= max_threshold));
           // Histogram::Add (histogram.hpp:74-86): a NaN or a huge value ends in no bin, like the cast to size_t on x86-64
           const double t = mul_rn(e, bins_by_interval);
@@ -894,7 +568,7 @@ __global__ __launch_bounds__(64 * kResWaves) void resection_acransac_bounded_ker
           }
           double cur = INFINITY;
           if (lane < kBins && cum > 3u && my_bin_value > kResFltEps) {
-            cur = add_rn(add_rn(add_rn(loge0, mul_rn(my_logalpha, (double)(cum - 3u))), (double)logc_n[cum]), (double)logc_k[cum]);
+            cur = add_rn(add_rn(add_rn(loge0, mul_rn(my_logalpha, (double)(cum - 3u))), (double)T.logc_n[cum]), (double)T.logc_k[cum]);
             if (!(cur < 0)) cur = INFINITY;
           }
           // the first bin of strictly smallest NFA among the negative ones: wave maxima of an order-reversing key of the value's bits
@@ -919,7 +593,7 @@ __global__ __launch_bounds__(64 * kResWaves) void resection_acransac_bounded_ker
             uint32_t cnt = 0;
             for (uint32_t base = 0; base < n; base += 64) {
               const uint32_t i = base + lane;
-              cnt += (uint32_t)__popcll(__ballot(i < n && res_error_of(M, res_model, P.intr, n1norm, pX, px, i) <= cb_thr));
+              cnt += (uint32_t)__popcll(__ballot(i < n && F.residual(M, i) <= cb_thr));
             }
             lister = m; list_thr = cb_thr; flags |= (uint32_t)kResBRebuilt;
             if (cnt > 3u) { run_min = cb_nfa; winner = m; win_thr = cb_thr; flags |= (uint32_t)kResBBetter; }
@@ -943,77 +617,49 @@ __global__ __launch_bounds__(64 * kResWaves) void resection_acransac_bounded_ker
     uint32_t done = nb;
     bool event = false;
     for (uint32_t j = 0; j < nb && !event; ++j) {
-      const double* const v = verdicts + kResBVerdict * j;
+      const double* const v = lds.verdicts + L::kVerdict * j;
       n_models_total += (uint32_t)v[16];
       const uint32_t flags = (uint32_t)v[0];
       const bool better = (flags & (uint32_t)kResBBetter) != 0, rebuilt = (flags & (uint32_t)kResBRebuilt) != 0;
       if (flags & (uint32_t)kResBSwitched) ac = true;
       if (rebuilt) {   // vec_inliers of the iteration's last rebuild; a better model's is the last one or the size test failed after it
-        n_inl = resb_rebuild_list(res_rt_load(v + 18), v[17], res_model, P.intr, n1norm, pX, px, n, inliers, wcount, tid);
+        n_inl = resb_rebuild_list(F, res_rt_load(v + 18), v[17], n, T.inliers, wcount, tid);
         if (better) {
           minNFA = v[1]; errorMax = v[2];
-          if (tid == 0)
-            for (int e = 0; e < 12; ++e) best_model[e] = v[4 + e];
+          res_keep_model(lds.best_model, v + 4, tid);
         }
       }
       // loop control (:446-474)
       bool take_pool = false, branch = false, early = false;
-      if (!ac && (iter + j) > (uint32_t)(nIterReserve * 2)) { nIter = 0; early = true; }
-      else if (ac && ((better && minNFA < 0) || ((iter + j + 1) == nIter && nIterReserve > 0))) {
-        branch = true;
-        if (n_inl == 0) { ++nIter; --nIterReserve; }
-        else {
-          take_pool = true;
-          if (nIterReserve) { nIter = iter + j + 1 + (uint32_t)nIterReserve; nIterReserve = 0; }
-        }
-      }
+      if (!ac && (it.iter + j) > (uint32_t)(it.nIterReserve * 2)) { it.nIter = 0; early = true; }
+      else if (ac) branch = it.reserve_event(better && minNFA < 0, j, n_inl, take_pool);
       if (rebuilt || ac != ac_at_start || branch || early) {
         event = true;
         done = j + 1;
         __syncthreads();   // the inlier list is complete; wave 0 may touch the pool
         if (done < nb && !early && wave == 0) {
-          // the generator and the pool as they stood after iteration j: undo the block's swaps, restore the state, draw j + 1 again - in the
-          // mode the block was drawn in (a switch voids what was drawn ahead in the warm-up's mode)
-          if (ac_at_start && lane == 0)
-            for (int s = 3 * (int)nb - 1; s >= 0; --s) {
-              const uint32_t i = (uint32_t)s % 3, r = swaps[s];
-              const uint32_t a = pool[i], b = pool[r];
-              pool[i] = b; pool[r] = a;
-            }
-          for (int i = lane; i < kMtN; i += 64) mt[i] = mt_saved[i];
-          wave_sync();
-          mt_idx = mt_idx_saved;
-          for (uint32_t jj = 0; jj < done; ++jj) {
-            if (ac_at_start) {
-              for (uint32_t i = 0; i < 3; ++i) {
-                const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
-                if (lane == 0) { const uint32_t a = pool[i], b = pool[r]; pool[i] = b; pool[r] = a; }
-              }
-            } else {
+          // the generator and the pool as they stood after iteration j, in the mode the block was drawn in (a switch voids what was
+          // drawn ahead in the warm-up's mode)
+          if (ac_at_start) res_rewind_block<3>(gen, T.pool, pool_n, lds.swaps, nb, done, lane);
+          else {
+            gen.restore(lane);
+            for (uint32_t jj = 0; jj < done; ++jj) {
               uint32_t c0, c1, c2;
-              resb_draw_distinct(mt, mt_idx, lane, n, c0, c1, c2);
+              resb_draw_distinct(gen.mt, gen.idx, lane, n, c0, c1, c2);
             }
           }
         }
         __syncthreads();
-        if (take_pool) {   // vec_index = vec_inliers: in index order
-          for (uint32_t i = tid; i < n_inl; i += n_threads) pool[i] = inliers[i];
-          pool_n = n_inl;
+        if (take_pool) {   // (in index order)
+          res_adopt_pool(T.pool, T.inliers, n_inl, pool_n, tid);
           if (pool_n < 3) stop = true;
         }
       }
     }
-    iter += done;
+    it.iter += done;
     __syncthreads();
   }
-
-  if (minNFA >= 0) n_inl = 0;   // no meaningful model
-  for (uint32_t i = tid; i < n_inl; i += n_threads) inliers_out[P.start + i] = inliers[i];
-  if (tid == 0) {
-    ResResult& R = results[pi];
-    for (int e = 0; e < 12; ++e) R.P[e] = best_model[e];
-    R.error_max = errorMax; R.min_nfa = minNFA; R.n_inliers = n_inl; R.n_iterations = iter; R.n_models = n_models_total; R.pad_ = 0;
-  }
+  res_write_result(results[pi], inliers_out + P.start, T.inliers, lds.best_model, minNFA, errorMax, n_inl, it.iter, n_models_total, tid);
 }
 
 // ---- host ----
@@ -1095,26 +741,27 @@ inline void res_krt_from_p(const double* P, double* K, double* R, double* t) {
   for (int e = 0; e < 9; ++e) K[e] /= k22;
 }
 
-// What mvgx_resection_localize and mvgx_resection_localize_bounded share: argument checks, problem table, staging, the bearing pass and
-// the unpacking of the results. The buffers of one call; on scope exit the stream is drained and handed back before any of them is freed.
+// What the three entries (mvgx_resection_localize, _bounded, _uncalibrated) share: the checks of a batch, the problem table and the
+// staging, the uploads, the trace, the launches and the unpacking of the results. The buffers of one call; on scope exit the stream is
+// drained and handed back before any of them is freed.
 struct ResCall {
   const char* entry = "";
-  bool bounded = false;
-  uint32_t n_problems = 0, n_max = 0;
+  uint32_t n_problems = 0, n_max = 0, n_lds_max = 0;   // n_lds_max: the largest problem of the LDS form
   uint64_t base = 0, n_total = 0;
-  std::vector<uint32_t> in_lds, in_global;   // problems that reach the loop (n > 3), the largest first; the two storage forms
+  std::vector<uint32_t> in_lds, in_global;   // problems that reach the loop (n > the minimum sample), the largest first; the two storage forms
   // one page-locked staging buffer: problems | (bounded) bounds | launch lists | log10 table | generator state
   mvgx::PinnedBuf<uint64_t> stage;
   size_t stage_words = 0, prob_words = 0, bound_words = 0, n_lists = 0, l10_n = 0, scratch_bytes = 0;
-  ResProblem* hp = nullptr;
-  ResBound* h_bound = nullptr;
   uint32_t* h_lists = nullptr;
   mvgx::DevBuf<uint64_t> d_stage;
-  mvgx::DevBuf<double> d_x2d, d_X, d_bear;
+  mvgx::DevBuf<double> d_x2d, d_X, d_bear;   // d_bear: what the prepare pass writes (bearings, or the normalised pixels in 2 of its 3 doubles)
   mvgx::DevBuf<unsigned char> d_scratch;
   mvgx::DevBuf<ResResult> d_res;
   mvgx::DevBuf<uint32_t> d_inl, d_trace;
   mvgx::PinnedBuf<ResResult> h_res;
+  uint32_t* host_trace = nullptr;            // test hook: where this call's trace goes, its events per problem, its words
+  uint32_t trace_events = 0;
+  size_t trace_words = 0;
   hipStream_t stream = nullptr;
   int stream_device = 0;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1126,30 +773,22 @@ struct ResCall {
     if (e1) (void)hipEventDestroy(e1);
     if (stream) { (void)hipStreamSynchronize(stream); mvgx::release_stream(stream_device, stream); }
   }
+  template <class Problem> Problem* h_prob() { return reinterpret_cast<Problem*>(stage.p); }
+  template <class T> T* h_bound() { return reinterpret_cast<T*>(reinterpret_cast<uint32_t*>(stage.p) + prob_words); }
   // (launch arguments are plain pointers and counts: the test-suite's emulation captures them by value)
-  const ResProblem* p_prob() const { return reinterpret_cast<const ResProblem*>(d_stage.p); }
-  const ResBound* p_bound() const { return reinterpret_cast<const ResBound*>(reinterpret_cast<const uint32_t*>(d_stage.p) + prob_words); }
+  template <class Problem> const Problem* p_prob() const { return reinterpret_cast<const Problem*>(d_stage.p); }
+  template <class T> const T* p_bound() const { return reinterpret_cast<const T*>(reinterpret_cast<const uint32_t*>(d_stage.p) + prob_words); }
   const uint32_t* p_lists() const { return reinterpret_cast<const uint32_t*>(d_stage.p) + prob_words + bound_words; }
   const float* p_l10() const { return reinterpret_cast<const float*>(p_lists() + n_lists); }
   const uint32_t* p_mt() const { return reinterpret_cast<const uint32_t*>(p_l10() + l10_n); }
+  uint32_t* p_trace() const { return host_trace ? d_trace.p : nullptr; }
 };
 
-// The checks of both entries, in one order; sets c.n_max
-int res_check_arguments(ResCall& c, uint32_t n_problems, const uint64_t* start, const int32_t* intr_model, const double* intrinsics, const mvgx_resection_options* opt,
-                        const uint8_t* out_ok, const double* out_pose, const double* out_P, const double* out_error_max, const double* out_min_nfa,
-                        const uint64_t* out_inlier_start) {
+// The checks every entry makes of its batch, after those of its own options: waves_ahead, then per problem the start, the size and
+// check_problem(p) (returns an error code); sets c.n_problems and c.n_max
+template <class CheckProblem>
+int res_check_batch(ResCall& c, uint32_t n_problems, const uint64_t* start, const mvgx_resection_options* opt, CheckProblem check_problem) {
   const char* const fn = c.entry;
-  MVGX_REQUIRE(opt && start && out_ok && out_pose && out_P && out_error_max && out_min_nfa && out_inlier_start, MVGX_ERR_ARG, "%s: NULL argument", fn);
-  MVGX_REQUIRE(n_problems == 0 || (intr_model && intrinsics), MVGX_ERR_ARG, "%s: NULL camera arrays", fn);
-  MVGX_REQUIRE(opt->solver >= 0 && opt->solver <= 5, MVGX_ERR_ARG, "%s: solver %d is no resection::SolverType", fn, opt->solver);
-  MVGX_REQUIRE(opt->solver == MVGX_RESECTION_P3P_DING || opt->solver == MVGX_RESECTION_P3P_NORDBERG, MVGX_ERR_UNSUPPORTED,
-               "%s: solver %d has no device path (P3P_DING_CVPR23 = 4 and P3P_NORDBERG_ECCV18 = 3 have)", fn, opt->solver);
-  if (c.bounded)
-    MVGX_REQUIRE(std::isfinite(opt->error_max) && opt->error_max > 0, MVGX_ERR_ARG,
-                 "%s: error_max must be a finite bound in pixels, > 0 (infinity - the exhaustive NFA - is mvgx_resection_localize's form)", fn);
-  else
-    MVGX_REQUIRE(std::isinf(opt->error_max) && opt->error_max > 0, MVGX_ERR_UNSUPPORTED,
-                 "%s: a finite error_max selects the quantified NFA with the max-consensus early exit: that form is mvgx_resection_localize_bounded", fn);
   MVGX_REQUIRE(opt->waves_ahead <= (uint32_t)kResWaves, MVGX_ERR_ARG, "%s: waves_ahead %u exceeds the build's %d", fn, opt->waves_ahead, kResWaves);
   c.n_problems = n_problems;
   c.n_max = 0;
@@ -1157,17 +796,41 @@ int res_check_arguments(ResCall& c, uint32_t n_problems, const uint64_t* start, 
     MVGX_REQUIRE(start[p + 1] >= start[p], MVGX_ERR_ARG, "%s: start decreases at problem %u", fn, p);
     const uint64_t n = start[p + 1] - start[p];
     MVGX_REQUIRE(n <= kResMaxN, MVGX_ERR_ARG, "%s: problem %u has %llu correspondences, the supported maximum is %u", fn, p, (unsigned long long)n, kResMaxN);
-    const int m = intr_model[p];
-    MVGX_REQUIRE(mvgx_ba::intr_param_count(m) >= 0, MVGX_ERR_UNSUPPORTED, "%s: problem %u: camera model %d is not supported", fn, p, m);
+    if (const int rc = check_problem(p)) return rc;
     c.n_max = std::max(c.n_max, (uint32_t)n);
   }
   return MVGX_OK;
 }
 
-// Clears the outputs and sorts the problems into the two storage forms; *work = whether any problem reaches the loop
-int res_classify(ResCall& c, const uint64_t* start, const double* x2d, const double* X3d, const uint32_t* out_inliers, uint32_t lds_bound, uint8_t* out_ok,
-                 double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, mvgx_resection_stats* stats, bool* work) {
+// The checks of the two calibrated entries, in one order
+int res_check_arguments(ResCall& c, bool bounded, uint32_t n_problems, const uint64_t* start, const int32_t* intr_model, const double* intrinsics,
+                        const mvgx_resection_options* opt, const uint8_t* out_ok, const double* out_pose, const double* out_P, const double* out_error_max,
+                        const double* out_min_nfa, const uint64_t* out_inlier_start) {
+  const char* const fn = c.entry;
+  MVGX_REQUIRE(opt && start && out_ok && out_pose && out_P && out_error_max && out_min_nfa && out_inlier_start, MVGX_ERR_ARG, "%s: NULL argument", fn);
+  MVGX_REQUIRE(n_problems == 0 || (intr_model && intrinsics), MVGX_ERR_ARG, "%s: NULL camera arrays", fn);
+  MVGX_REQUIRE(opt->solver >= 0 && opt->solver <= 5, MVGX_ERR_ARG, "%s: solver %d is no resection::SolverType", fn, opt->solver);
+  MVGX_REQUIRE(opt->solver == MVGX_RESECTION_P3P_DING || opt->solver == MVGX_RESECTION_P3P_NORDBERG, MVGX_ERR_UNSUPPORTED,
+               "%s: solver %d has no device path (P3P_DING_CVPR23 = 4 and P3P_NORDBERG_ECCV18 = 3 have)", fn, opt->solver);
+  if (bounded)
+    MVGX_REQUIRE(std::isfinite(opt->error_max) && opt->error_max > 0, MVGX_ERR_ARG,
+                 "%s: error_max must be a finite bound in pixels, > 0 (infinity - the exhaustive NFA - is mvgx_resection_localize's form)", fn);
+  else
+    MVGX_REQUIRE(std::isinf(opt->error_max) && opt->error_max > 0, MVGX_ERR_UNSUPPORTED,
+                 "%s: a finite error_max selects the quantified NFA with the max-consensus early exit: that form is mvgx_resection_localize_bounded", fn);
+  return res_check_batch(c, n_problems, start, opt, [&](uint32_t p) -> int {
+    const int m = intr_model[p];
+    MVGX_REQUIRE(mvgx_ba::intr_param_count(m) >= 0, MVGX_ERR_UNSUPPORTED, "%s: problem %u: camera model %d is not supported", fn, p, m);
+    return MVGX_OK;
+  });
+}
+
+// Clears the outputs and sorts the problems with more than min_sample correspondences (ACRANSAC returns early below that) into the two
+// storage forms: the LDS form up to global_above, capped by lds_max_n; *work = whether any problem reaches the loop
+int res_classify(ResCall& c, uint32_t min_sample, const uint64_t* start, const double* x2d, const double* X3d, const uint32_t* out_inliers, uint32_t global_above,
+                 uint32_t lds_max_n, uint8_t* out_ok, double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, mvgx_resection_stats* stats, bool* work) {
   const uint32_t n_problems = c.n_problems;
+  const uint32_t lds_bound = global_above ? std::min(global_above, lds_max_n) : lds_max_n;
   *work = false;
   if (stats) memset(stats, 0, sizeof(*stats));
   for (uint32_t p = 0; p < n_problems; ++p) { out_ok[p] = 0; out_error_max[p] = 0.0; out_min_nfa[p] = 0.0; }
@@ -1178,60 +841,65 @@ int res_classify(ResCall& c, const uint64_t* start, const double* x2d, const dou
   MVGX_REQUIRE(c.n_total == 0 || (x2d && X3d && out_inliers), MVGX_ERR_ARG, "%s: NULL correspondence arrays", c.entry);
   for (uint32_t p = 0; p < n_problems; ++p) {
     const uint64_t n = start[p + 1] - start[p];
-    if (n > 3) (n <= lds_bound ? c.in_lds : c.in_global).push_back(p);
+    if (n > min_sample) (n <= lds_bound ? c.in_lds : c.in_global).push_back(p);
   }
   const auto by_n = [&](uint32_t a, uint32_t b) { const uint64_t na = start[a + 1] - start[a], nb = start[b + 1] - start[b]; return na != nb ? na > nb : a < b; };
   std::sort(c.in_lds.begin(), c.in_lds.end(), by_n);
   std::sort(c.in_global.begin(), c.in_global.end(), by_n);
+  c.n_lds_max = c.in_lds.empty() ? 0 : (uint32_t)(start[c.in_lds[0] + 1] - start[c.in_lds[0]]);
   *work = !(c.in_lds.empty() && c.in_global.empty());
   return MVGX_OK;
 }
 
-// The staging buffer: the problem table (and, bounded, the histogram's constants of every problem), the launch lists, the log10 table and
-// the generator's initial state. glibc's log10: the reference's values.
-int res_stage(ResCall& c, const uint64_t* start, const int32_t* intr_model, const double* intrinsics, double error_max, size_t (*scratch_bytes_of)(uint32_t)) {
+// The staging buffer: the problem table (start, n and scratch offset here, the rest by fill(p, n, record)), bound_words for a second
+// per-problem table behind it, the launch lists, the log10 table and the generator's initial state. glibc's log10: the reference's values.
+template <class Problem, class Fill>
+int res_stage(ResCall& c, const uint64_t* start, size_t bound_words, size_t (*scratch_bytes_of)(uint32_t), Fill fill) {
   const uint32_t n_problems = c.n_problems;
   int rc;
   c.n_lists = c.in_lds.size() + c.in_global.size();
-  c.prob_words = (size_t)n_problems * sizeof(ResProblem) / 4;
-  c.bound_words = c.bounded ? (size_t)n_problems * sizeof(ResBound) / 4 : 0;
+  c.prob_words = (size_t)n_problems * sizeof(Problem) / 4;
+  c.bound_words = bound_words;
   c.l10_n = (size_t)c.n_max + 2;
   c.stage_words = c.prob_words + c.bound_words + c.n_lists + c.l10_n + kMtN;
   if ((rc = c.stage.ensure((c.stage_words + 1) / 2))) return rc;
-  c.hp = reinterpret_cast<ResProblem*>(c.stage.p);
-  c.h_bound = reinterpret_cast<ResBound*>(reinterpret_cast<uint32_t*>(c.stage.p) + c.prob_words);
+  Problem* const hp = c.h_prob<Problem>();
   c.h_lists = reinterpret_cast<uint32_t*>(c.stage.p) + c.prob_words + c.bound_words;
   float* const h_l10 = reinterpret_cast<float*>(c.h_lists + c.n_lists);
   uint32_t* const h_mt = reinterpret_cast<uint32_t*>(h_l10 + c.l10_n);
   for (uint32_t p = 0; p < n_problems; ++p) {
-    ResProblem& g = c.hp[p];
-    const uint32_t n = (uint32_t)(start[p + 1] - start[p]);
-    g.start = start[p] - c.base; g.n = n; g.model = (uint32_t)intr_model[p]; g.scratch = 0;
-    memcpy(g.intr, intrinsics + 8 * (size_t)p, sizeof(g.intr));
-    // imagePlane_toCameraPlaneError(1): 1 / focal (pinhole family), 1 / max(w, h) (spherical)
-    g.n1 = intr_model[p] == mvgx_ba::kCamSpherical ? 1.0 / std::max(g.intr[0], g.intr[1]) : 1.0 / g.intr[0];
-    g.loge0 = n > 3 ? std::log10(4.0 * (double)(n - 3)) : 0.0;   // MAX_MODELS = 4, MINIMUM_SAMPLES = 3
-    if (c.bounded) {
-      // maxThreshold = precision N(0,0)^2 with precision = Square(error_max) (SfM_Localizer.cpp:125-128, robust_estimator_ACRansac.hpp:351-353);
-      // Histogram(0, maxThreshold, 20): nBins_by_interval and GetXbinsValue (histogram.hpp:49-61, :105-112); logalpha per bin value (:229-231)
-      ResBound& b = c.h_bound[p];
-      b.max_threshold = error_max * error_max * g.n1 * g.n1;
-      b.bins_by_interval = kBins / (b.max_threshold - 0.0);
-      const double val = (b.max_threshold - 0.0) / static_cast<double>(kBins - 1);
-      for (int k = 0; k < kBins; ++k) {
-        b.bin_value[k] = val * static_cast<double>(k) + 0.0;
-        b.logalpha_bin[k] = std::log10(M_PI) + 1.0 * std::log10(b.bin_value[k] + std::numeric_limits<float>::epsilon());
-      }
-    }
+    Problem& g = hp[p];
+    g.start = start[p] - c.base; g.n = (uint32_t)(start[p + 1] - start[p]); g.scratch = 0;
+    fill(p, g.n, g);
   }
   c.scratch_bytes = 0;
-  for (uint32_t p : c.in_global) { c.hp[p].scratch = c.scratch_bytes; c.scratch_bytes += scratch_bytes_of(c.hp[p].n); }
+  for (uint32_t p : c.in_global) { hp[p].scratch = c.scratch_bytes; c.scratch_bytes += scratch_bytes_of(hp[p].n); }
   if (!c.in_lds.empty()) memcpy(c.h_lists, c.in_lds.data(), c.in_lds.size() * 4);
   if (!c.in_global.empty()) memcpy(c.h_lists + c.in_lds.size(), c.in_global.data(), c.in_global.size() * 4);
   for (size_t i = 0; i < c.l10_n; ++i) h_l10[i] = (float)::log10((double)static_cast<float>(i));
   h_mt[0] = 5489u;   // std::mt19937::default_seed
   for (int i = 1; i < kMtN; ++i) h_mt[i] = 1812433253u * (h_mt[i - 1] ^ (h_mt[i - 1] >> 30)) + (uint32_t)i;
   return MVGX_OK;
+}
+// The record of a calibrated problem; bounded: the histogram constants of error_max too
+void res_fill_calibrated(ResCall& c, bool bounded, const int32_t* intr_model, const double* intrinsics, double error_max, uint32_t p, uint32_t n, ResProblem& g) {
+  g.model = (uint32_t)intr_model[p];
+  memcpy(g.intr, intrinsics + 8 * (size_t)p, sizeof(g.intr));
+  // imagePlane_toCameraPlaneError(1): 1 / focal (pinhole family), 1 / max(w, h) (spherical)
+  g.n1 = intr_model[p] == mvgx_ba::kCamSpherical ? 1.0 / std::max(g.intr[0], g.intr[1]) : 1.0 / g.intr[0];
+  g.loge0 = n > 3 ? std::log10(4.0 * (double)(n - 3)) : 0.0;   // MAX_MODELS = 4, MINIMUM_SAMPLES = 3
+  if (bounded) {
+    // maxThreshold = precision N(0,0)^2 with precision = Square(error_max) (SfM_Localizer.cpp:125-128, robust_estimator_ACRansac.hpp:351-353);
+    // Histogram(0, maxThreshold, 20): nBins_by_interval and GetXbinsValue (histogram.hpp:49-61, :105-112); logalpha per bin value (:229-231)
+    ResBound& b = c.h_bound<ResBound>()[p];
+    b.max_threshold = error_max * error_max * g.n1 * g.n1;
+    b.bins_by_interval = kBins / (b.max_threshold - 0.0);
+    const double val = (b.max_threshold - 0.0) / static_cast<double>(kBins - 1);
+    for (int k = 0; k < kBins; ++k) {
+      b.bin_value[k] = val * static_cast<double>(k) + 0.0;
+      b.logalpha_bin[k] = std::log10(M_PI) + 1.0 * std::log10(b.bin_value[k] + std::numeric_limits<float>::epsilon());
+    }
+  }
 }
 
 // Stream, events and device buffers; the uploads
@@ -1252,52 +920,86 @@ int res_upload(ResCall& c, const double* x2d, const double* X3d) {
   MVGX_HIP(hipMemsetAsync(c.d_res.p, 0, (size_t)c.n_problems * sizeof(ResResult), c.stream));
   return MVGX_OK;
 }
-// The first event, then the bearing pass
-int res_bear(ResCall& c) {
-  const ResProblem* const p_prob = c.p_prob();
+// Test hook: this call takes the trace that mvgx_resection_debug_trace asked for (one call only)
+int res_trace_setup(ResCall& c) {
+  c.host_trace = g_res_trace;
+  c.trace_events = c.host_trace ? g_res_trace_events : 0;
+  g_res_trace = nullptr;
+  c.trace_words = (size_t)c.n_problems * res_trace_words(c.trace_events);
+  if (c.host_trace) {
+    int rc;
+    if ((rc = c.d_trace.ensure(c.trace_words))) return rc;
+    MVGX_HIP(hipMemsetAsync(c.d_trace.p, 0, c.trace_words * sizeof(uint32_t), c.stream));
+  }
+  return MVGX_OK;
+}
+// The first event, then the prepare pass: one thread per correspondence, from x2d into d_bear
+template <class Problem>
+int res_prepare(ResCall& c, void (*kernel)(const Problem*, uint32_t, uint64_t, const double*, double*)) {
+  const Problem* const p_prob = c.p_prob<Problem>();
   const double* const p_x2d = c.d_x2d.p;
-  double* const p_bear = c.d_bear.p;
+  double* const p_out = c.d_bear.p;
   const uint32_t n_problems = c.n_problems;
   const uint64_t n_total = c.n_total;
   MVGX_HIP(hipEventRecord(c.e0, c.stream));
-  hipLaunchKernelGGL(resection_bearing_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c.stream, p_prob, n_problems, n_total, p_x2d, p_bear);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c.stream, p_prob, n_problems, n_total, p_x2d, p_out);
   MVGX_HIP(hipGetLastError());
   return MVGX_OK;
 }
 
-// After the loop kernels: the second event, the results and the inlier lists back, KRt_From_P of every problem with enough inliers
-int res_finish(ResCall& c, uint32_t* host_trace, size_t trace_words, uint8_t* out_ok, double* out_pose, double* out_P, double* out_error_max, double* out_min_nfa,
-               uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats, std::chrono::steady_clock::time_point t_begin) {
+// A loop kernel's two launches: the problems of the LDS form, every workgroup with the LDS of the largest of them, then those of the
+// global form. The kernels take (order, n_work, n_lds_max, args...).
+template <class... Params, class... Args>
+int res_launch_one(void (*kernel)(Params...), uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, Args... args) {
+  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL(kernel, dim3(n_work), dim3(64 * kResWaves), lds_bytes, stream, args...);
+  MVGX_HIP(hipGetLastError());
+  return MVGX_OK;
+}
+template <class... Params, class... Args>
+int res_launch(ResCall& c, void (*kernel_lds)(Params...), void (*kernel_global)(Params...), uint32_t (*lds_bytes_of)(uint32_t), Args... args) {
+  const uint32_t n_lds = (uint32_t)c.in_lds.size(), n_global = (uint32_t)c.in_global.size();
+  int rc;
+  if (n_lds && (rc = res_launch_one(kernel_lds, n_lds, lds_bytes_of(c.n_lds_max), c.stream, c.p_lists(), n_lds, c.n_lds_max, args...))) return rc;
+  if (n_global && (rc = res_launch_one(kernel_global, n_global, lds_bytes_of(0), c.stream, c.p_lists() + n_lds, n_global, 0u, args...))) return rc;
+  return MVGX_OK;
+}
+
+// R, t and the centre C = -R^T t into a problem's 15 doubles of out_pose
+inline void res_write_pose(const double* R, const double* t, double* pose) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) pose[4 * i + j] = R[3 * i + j];
+    pose[4 * i + 3] = t[i];
+    pose[12 + i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
+  }
+}
+// After the loop kernels: the second event, the results and the inlier lists back; per problem with more than 2.5 min_sample inliers
+// write_model(p, record, result) leaves pose, P (and K). scale: the record's member that unormalizeError divides by.
+template <class Problem, class WriteModel>
+int res_finish(ResCall& c, uint32_t min_sample, double Problem::*scale, uint8_t* out_ok, double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start,
+               uint32_t* out_inliers, mvgx_resection_stats* stats, std::chrono::steady_clock::time_point t_begin, WriteModel write_model) {
   const uint32_t n_problems = c.n_problems;
+  const Problem* const hp = c.h_prob<Problem>();
   MVGX_HIP(hipEventRecord(c.e1, c.stream));
   MVGX_HIP(hipMemcpyAsync(c.h_res.p, c.d_res.p, (size_t)n_problems * sizeof(ResResult), hipMemcpyDeviceToHost, c.stream));
   // the inlier lists come back in place (one list per problem at its start), then are packed
   std::vector<uint32_t> inl(c.n_total);
   MVGX_HIP(hipMemcpyAsync(inl.data(), c.d_inl.p, c.n_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-  if (host_trace) MVGX_HIP(hipMemcpyAsync(host_trace, c.d_trace.p, trace_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+  if (c.host_trace) MVGX_HIP(hipMemcpyAsync(c.host_trace, c.d_trace.p, c.trace_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
   MVGX_HIP(hipStreamSynchronize(c.stream));
 
   uint64_t at = 0, iterations = 0, n_models = 0;
   for (uint32_t p = 0; p < n_problems; ++p) {
     out_inlier_start[p] = at;
     const ResResult& r = c.h_res.p[p];
-    if (c.hp[p].n <= 3) continue;   // ACRANSAC's early return of (0, 0): nothing else is written
+    if (hp[p].n <= min_sample) continue;   // ACRANSAC's early return of (0, 0): nothing else is written
     iterations += r.n_iterations; n_models += r.n_models;
     out_min_nfa[p] = r.min_nfa;
-    const double n1 = c.hp[p].n1;
-    out_error_max[p] = r.n_inliers ? std::sqrt(r.error_max) / n1 : r.error_max;   // unormalizeError
-    if (r.n_inliers) memcpy(out_inliers + at, inl.data() + c.hp[p].start, (size_t)r.n_inliers * sizeof(uint32_t));
+    out_error_max[p] = r.n_inliers ? std::sqrt(r.error_max) / (hp[p].*scale) : r.error_max;   // unormalizeError
+    if (r.n_inliers) memcpy(out_inliers + at, inl.data() + hp[p].start, (size_t)r.n_inliers * sizeof(uint32_t));
     at += r.n_inliers;
-    if ((double)r.n_inliers > 2.5 * 3) {
-      double K[9], R[9], t[3];
-      res_krt_from_p(r.P, K, R, t);
-      double* const pose = out_pose + 15 * (size_t)p;
-      for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) pose[4 * i + j] = R[3 * i + j];
-        pose[4 * i + 3] = t[i];
-        pose[12 + i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);   // C = -R^T t
-      }
-      memcpy(out_P + 12 * (size_t)p, r.P, 12 * sizeof(double));
+    if ((double)r.n_inliers > 2.5 * min_sample) {
+      write_model(p, hp[p], r);
       out_ok[p] = 1;
     }
   }
@@ -1311,25 +1013,45 @@ int res_finish(ResCall& c, uint32_t* host_trace, size_t trace_words, uint8_t* ou
   return MVGX_OK;
 }
 
-template <bool kGlobal>
-int res_launch(uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, const ResProblem* problems, const uint32_t* order, const double* x2d, const double* X3d,
-               const double* bear, const float* l10, const uint32_t* mt_init, uint32_t max_iteration, int solver, uint32_t waves_ahead, uint32_t n_lds_max,
-               unsigned char* scratch, ResResult* results, uint32_t* inliers_out, uint32_t* trace, uint32_t trace_events) {
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resection_acransac_kernel<kGlobal>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((resection_acransac_kernel<kGlobal>), dim3(n_work), dim3(64 * kResWaves), lds_bytes, stream, problems, order, n_work, x2d, X3d, bear, l10,
-                     mt_init, max_iteration, solver, waves_ahead, n_lds_max, scratch, results, inliers_out, trace, trace_events);
-  MVGX_HIP(hipGetLastError());
-  return MVGX_OK;
-}
-template <bool kGlobal>
-int resb_launch(uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, const ResProblem* problems, const ResBound* bounds, const uint32_t* order, const double* x2d,
-                const double* X3d, const double* bear, const float* l10, const uint32_t* mt_init, uint32_t max_iteration, int solver, uint32_t waves_ahead,
-                unsigned char* scratch, ResResult* results, uint32_t* inliers_out) {
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resection_acransac_bounded_kernel<kGlobal>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((resection_acransac_bounded_kernel<kGlobal>), dim3(n_work), dim3(64 * kResWaves), lds_bytes, stream, problems, bounds, order, n_work, x2d, X3d,
-                     bear, l10, mt_init, max_iteration, solver, waves_ahead, scratch, results, inliers_out);
-  MVGX_HIP(hipGetLastError());
-  return MVGX_OK;
+// What the two calibrated entries differ in: bounded, and with it the second table, the LDS bound and the kernel
+int res_localize_calibrated(const char* entry, bool bounded, int device, uint32_t n_problems, const uint64_t* start, const double* x2d, const double* X3d,
+                            const int32_t* intr_model, const double* intrinsics, const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose, double* out_P,
+                            double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  ResCall c;
+  c.entry = entry;
+  int rc;
+  bool work = false;
+  if ((rc = res_check_arguments(c, bounded, n_problems, start, intr_model, intrinsics, opt, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start))) return rc;
+  if ((rc = res_classify(c, 3, start, x2d, X3d, out_inliers, opt->global_above, bounded ? kResBLdsMaxN : kResLdsMaxN, out_ok, out_error_max, out_min_nfa, out_inlier_start,
+                         stats, &work)))
+    return rc;
+  if (!work) return MVGX_OK;
+  if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
+  const double error_max = opt->error_max;
+  if ((rc = res_stage<ResProblem>(c, start, bounded ? (size_t)n_problems * sizeof(ResBound) / 4 : 0,
+                                  bounded ? &ResBLayout::scratch_bytes : &ResP3PForm::Layout::scratch_bytes,
+                                  [&](uint32_t p, uint32_t n, ResProblem& g) { res_fill_calibrated(c, bounded, intr_model, intrinsics, error_max, p, n, g); })))
+    return rc;
+  if ((rc = res_upload(c, x2d, X3d))) return rc;
+  if (!bounded && (rc = res_trace_setup(c))) return rc;   // (the bounded loop leaves no trace)
+  if ((rc = res_prepare<ResProblem>(c, resection_bearing_kernel))) return rc;
+  if (bounded)
+    rc = res_launch(c, resection_acransac_bounded_kernel<false>, resection_acransac_bounded_kernel<true>, &ResBLayout::lds_bytes, c.p_prob<ResProblem>(),
+                    c.p_bound<ResBound>(), c.d_x2d.p, c.d_X.p, c.d_bear.p, c.p_l10(), c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, c.d_scratch.p, c.d_res.p,
+                    c.d_inl.p);
+  else
+    rc = res_launch(c, resection_acransac_kernel<ResP3PForm, false>, resection_acransac_kernel<ResP3PForm, true>, &ResP3PForm::Layout::lds_bytes, c.p_prob<ResProblem>(),
+                    c.d_x2d.p, c.d_X.p, c.d_bear.p, c.p_l10(), c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, c.d_scratch.p, c.d_res.p, c.d_inl.p, c.p_trace(),
+                    c.trace_events);
+  if (rc) return rc;
+  return res_finish<ResProblem>(c, 3, &ResProblem::n1, out_ok, out_error_max, out_min_nfa, out_inlier_start, out_inliers, stats, t_begin,
+                                [&](uint32_t p, const ResProblem&, const ResResult& r) {
+                                  double K[9], R[9], t[3];
+                                  res_krt_from_p(r.P, K, R, t);
+                                  res_write_pose(R, t, out_pose + 15 * (size_t)p);
+                                  memcpy(out_P + 12 * (size_t)p, r.P, 12 * sizeof(double));
+                                });
 }
 
 }  // namespace
@@ -1346,40 +1068,8 @@ void mvgx_resection_default_options(mvgx_resection_options* o) {
 int mvgx_resection_localize(int device, uint32_t n_problems, const uint64_t* start, const double* x2d, const double* X3d, const int32_t* intr_model,
                             const double* intrinsics, const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose, double* out_P,
                             double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats) {
-  const auto t_begin = std::chrono::steady_clock::now();
-  ResCall c;
-  c.entry = __func__;
-  int rc;
-  bool work = false;
-  if ((rc = res_check_arguments(c, n_problems, start, intr_model, intrinsics, opt, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start))) return rc;
-  const uint32_t lds_bound = opt->global_above ? std::min(opt->global_above, kResLdsMaxN) : kResLdsMaxN;
-  if ((rc = res_classify(c, start, x2d, X3d, out_inliers, lds_bound, out_ok, out_error_max, out_min_nfa, out_inlier_start, stats, &work))) return rc;
-  if (!work) return MVGX_OK;
-  if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
-  if ((rc = res_stage(c, start, intr_model, intrinsics, opt->error_max, &res_scratch_bytes))) return rc;
-  if ((rc = res_upload(c, x2d, X3d))) return rc;
-  uint32_t* const host_trace = g_res_trace;   // (one call only)
-  const uint32_t trace_events = host_trace ? g_res_trace_events : 0;
-  g_res_trace = nullptr;
-  const size_t trace_words = (size_t)n_problems * res_trace_words(trace_events);
-  if (host_trace) {
-    if ((rc = c.d_trace.ensure(trace_words))) return rc;
-    MVGX_HIP(hipMemsetAsync(c.d_trace.p, 0, trace_words * sizeof(uint32_t), c.stream));
-  }
-  uint32_t* const p_trace = host_trace ? c.d_trace.p : nullptr;
-  if ((rc = res_bear(c))) return rc;
-  if (!c.in_lds.empty()) {
-    const uint32_t n_lds_max = c.hp[c.in_lds[0]].n;
-    if ((rc = res_launch<false>((uint32_t)c.in_lds.size(), res_lds_bytes(n_lds_max), c.stream, c.p_prob(), c.p_lists(), c.d_x2d.p, c.d_X.p, c.d_bear.p, c.p_l10(), c.p_mt(),
-                                opt->max_iteration, opt->solver, opt->waves_ahead, n_lds_max, c.d_scratch.p, c.d_res.p, c.d_inl.p, p_trace, trace_events)))
-      return rc;
-  }
-  if (!c.in_global.empty()) {
-    if ((rc = res_launch<true>((uint32_t)c.in_global.size(), res_lds_bytes(0), c.stream, c.p_prob(), c.p_lists() + c.in_lds.size(), c.d_x2d.p, c.d_X.p, c.d_bear.p, c.p_l10(),
-                               c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, 0, c.d_scratch.p, c.d_res.p, c.d_inl.p, p_trace, trace_events)))
-      return rc;
-  }
-  return res_finish(c, host_trace, trace_words, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start, out_inliers, stats, t_begin);
+  return res_localize_calibrated(__func__, /*bounded=*/false, device, n_problems, start, x2d, X3d, intr_model, intrinsics, opt, out_ok, out_pose, out_P, out_error_max,
+                                 out_min_nfa, out_inlier_start, out_inliers, stats);
 }
 
 // The bounded form: opt->error_max is the bound in pixels (Image_Localizer_Match_Data::error_max on entry), finite and > 0. ACRANSAC then
@@ -1389,32 +1079,8 @@ int mvgx_resection_localize(int device, uint32_t n_problems, const uint64_t* sta
 int mvgx_resection_localize_bounded(int device, uint32_t n_problems, const uint64_t* start, const double* x2d, const double* X3d, const int32_t* intr_model,
                                     const double* intrinsics, const mvgx_resection_options* opt, uint8_t* out_ok, double* out_pose, double* out_P,
                                     double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start, uint32_t* out_inliers, mvgx_resection_stats* stats) {
-  const auto t_begin = std::chrono::steady_clock::now();
-  ResCall c;
-  c.entry = __func__;
-  c.bounded = true;
-  int rc;
-  bool work = false;
-  if ((rc = res_check_arguments(c, n_problems, start, intr_model, intrinsics, opt, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start))) return rc;
-  const uint32_t lds_bound = opt->global_above ? std::min(opt->global_above, kResBLdsMaxN) : kResBLdsMaxN;
-  if ((rc = res_classify(c, start, x2d, X3d, out_inliers, lds_bound, out_ok, out_error_max, out_min_nfa, out_inlier_start, stats, &work))) return rc;
-  if (!work) return MVGX_OK;
-  if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
-  if ((rc = res_stage(c, start, intr_model, intrinsics, opt->error_max, &resb_scratch_bytes))) return rc;
-  if ((rc = res_upload(c, x2d, X3d))) return rc;
-  if ((rc = res_bear(c))) return rc;
-  if (!c.in_lds.empty()) {
-    const uint32_t n_lds_max = c.hp[c.in_lds[0]].n;   // (every workgroup of the launch gets the LDS of its largest problem)
-    if ((rc = resb_launch<false>((uint32_t)c.in_lds.size(), resb_lds_bytes(n_lds_max), c.stream, c.p_prob(), c.p_bound(), c.p_lists(), c.d_x2d.p, c.d_X.p, c.d_bear.p,
-                                 c.p_l10(), c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, c.d_scratch.p, c.d_res.p, c.d_inl.p)))
-      return rc;
-  }
-  if (!c.in_global.empty()) {
-    if ((rc = resb_launch<true>((uint32_t)c.in_global.size(), resb_lds_bytes(0), c.stream, c.p_prob(), c.p_bound(), c.p_lists() + c.in_lds.size(), c.d_x2d.p, c.d_X.p,
-                                c.d_bear.p, c.p_l10(), c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, c.d_scratch.p, c.d_res.p, c.d_inl.p)))
-      return rc;
-  }
-  return res_finish(c, nullptr, 0, out_ok, out_pose, out_P, out_error_max, out_min_nfa, out_inlier_start, out_inliers, stats, t_begin);
+  return res_localize_calibrated(__func__, /*bounded=*/true, device, n_problems, start, x2d, X3d, intr_model, intrinsics, opt, out_ok, out_pose, out_P, out_error_max,
+                                 out_min_nfa, out_inlier_start, out_inliers, stats);
 }
 
 

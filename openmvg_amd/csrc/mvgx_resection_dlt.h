@@ -1,19 +1,17 @@
 // mvgx_resection_dlt.h - robust resection of a view WITHOUT intrinsics on the device: AC-RANSAC over the six-point DLT solver, a batch
-// of independent problems per call (mvgx_resection_localize_uncalibrated). Included after mvgx_resection.h, under that header's
-// `#pragma clang fp contract(off)`: it uses its sort, table layout, verdict and trace records, result struct, KRt_From_P on the host and
-// the generator, logcombi and un-contracted mul_rn / add_rn of mvgx_geofilter.hip.
-// What is restated (paths under src/openMVG of the reference):
+// of independent problems per call (mvgx_resection_localize_uncalibrated). Included after mvgx_resection_loop.h and mvgx_resection.h,
+// under the former's `#pragma clang fp contract(off)`. The loop is resection_acransac_kernel of mvgx_resection_loop.h, the host stages
+// are the res_* functions of mvgx_resection.h; what is here is what the six-point form gives them: its problem record, its prepare
+// pass, its solver, its residual (ResDltForm) and the unnormalisation of the winning model.
+// What is restated here (paths under src/openMVG of the reference):
 //   sfm/pipelines/localization/SfM_Localizer.cpp:134-161, :321-331                 the DLT_6POINTS branch of SfM_Localizer::Localize
 //   robust_estimation/robust_estimator_ACRansacKernelAdaptator.hpp:203-288         ACKernelAdaptorResection, UnnormalizerResection
-//   robust_estimation/robust_estimator_ACRansac.hpp:257-304, :326-489              the exhaustive NFA, the a-contrario loop
-//   robust_estimation/rand_sampling.hpp:71-100                                     UniformSample on the pool (six swaps at its head)
 //   multiview/conditioning.cpp:54-77                                               NormalizePoints(points, ..., width, height)
 //   multiview/solver_resection_kernel.cpp:29-136                                   SixPointResectionSolver::Solve
 //   multiview/solver_resection_metrics.hpp:28-39                                   SquaredPixelReprojectionError
 //   multiview/projection.cpp:40-132, :192-194                                      KRt_From_P, Depth
-// Mapping: the loop's of mvgx_resection.h - one workgroup per problem, one wave per iteration evaluated ahead, verdicts read in iteration
-// order. What is new is the solver, which a wave runs as a whole: the null vector of the 12 x 12 design matrix by a one-sided (Hestenes)
-// Jacobi iteration on its columns, six column pairs per step, eight lanes per pair ("Resection without intrinsics").
+// The solver is run by a wave as a whole: the null vector of the 12 x 12 design matrix by a one-sided (Hestenes) Jacobi iteration on
+// its columns, six column pairs per step, eight lanes per pair ("Resection without intrinsics").
 #pragma once
 
 namespace {
@@ -39,12 +37,7 @@ __global__ __launch_bounds__(256) void resection_dlt_normalize_kernel(const DltP
                                                                       const double* __restrict__ x2d, double* __restrict__ xn) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_total) return;
-  uint32_t lo = 0, hi = n_problems - 1;   // the last problem that starts at or before i and is not empty there
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) / 2;
-    if (problems[mid].start <= i) lo = mid; else hi = mid - 1;
-  }
-  const DltProblem& P = problems[lo];
+  const DltProblem& P = res_problem_of(problems, n_problems, i);
   xn[2 * i] = add_rn(mul_rn(P.d_norm, x2d[2 * i]), P.off_x);
   xn[2 * i + 1] = add_rn(mul_rn(P.d_norm, x2d[2 * i + 1]), P.off_y);
 }
@@ -247,286 +240,36 @@ __global__ __launch_bounds__(64) void resection_dlt6_debug_kernel(const double* 
   if (lane == 0) n_out[i] = count;
 }
 
-// ---- the loop ----
-// words of LDS a workgroup needs: generator | its copy | verdicts | work areas | samples, swaps, counts | best model | (LDS form) pool,
-// inliers, logc_n, logc_k, slices
-__host__ __device__ constexpr uint32_t dlt_fixed_words() { return 2 * kMtN + 2 * kResWaves * kResVerdict + 2 * kResWaves * kDltWork + 16 * kResWaves + 24; }
-inline uint32_t dlt_lds_bytes(uint32_t n_lds_max) { return 4 * (dlt_fixed_words() + (n_lds_max ? res_table_words(n_lds_max) + kResWaves * res_slice_words(res_pow2(n_lds_max)) : 0)); }
-static_assert(4 * (dlt_fixed_words() + res_table_words(kDltLdsMaxN) + kResWaves * res_slice_words(kDltLdsMaxN)) <= 160 * 1024, "the LDS form must fit a workgroup's 160 KiB");
-
-template <bool kGlobal>
-__global__ __launch_bounds__(64 * kResWaves) void resection_dlt_acransac_kernel(const DltProblem* __restrict__ problems, const uint32_t* __restrict__ order, uint32_t n_work,
-                                                                                const double* __restrict__ xn, const double* __restrict__ X3d,
-                                                                                const float* __restrict__ l10, const uint32_t* __restrict__ mt_init, uint32_t max_iteration,
-                                                                                uint32_t waves_ahead, uint32_t n_lds_max, unsigned char* __restrict__ scratch,
-                                                                                ResResult* __restrict__ results, uint32_t* __restrict__ inliers_out, uint32_t* __restrict__ trace, uint32_t trace_events) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_u32[];
-  if (blockIdx.x >= n_work) return;
-  const uint32_t pi = order[blockIdx.x];
-  const DltProblem& P = problems[pi];
-  const uint32_t n = P.n, p2 = res_pow2(n);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n_threads = 64 * kResWaves;
-
-  uint32_t* const mt = lds_u32;
-  uint32_t* const mt_saved = mt + kMtN;
-  double* const verdicts = reinterpret_cast<double*>(mt_saved + kMtN);
-  double* const works = verdicts + kResWaves * kResVerdict;            // kDltWork doubles per wave
-  uint32_t* const samples = reinterpret_cast<uint32_t*>(works + kResWaves * kDltWork);   // 6 per wave | swap partners, 6 per wave | models per wave
-  uint32_t* const swaps = samples + kDltSample * kResWaves;
-  uint32_t* const n_mod = swaps + kDltSample * kResWaves;
-  double* const best_model = reinterpret_cast<double*>(samples + 16 * kResWaves);   // the winning P (thread 0 writes and reads it)
-  uint32_t* const tables = kGlobal ? reinterpret_cast<uint32_t*>(scratch + P.scratch) : lds_u32 + dlt_fixed_words();
-  const uint32_t n1 = n + 1;
-  uint32_t* const pool = tables;
-  uint32_t* const inliers = pool + n1;
-  float* const logc_n = reinterpret_cast<float*>(inliers + n1);
-  float* const logc_k = logc_n + n1;
-  uint32_t* const slices = tables + res_table_words(kGlobal ? n : n_lds_max);
-  const uint32_t slice_words = res_slice_words(kGlobal ? p2 : res_pow2(n_lds_max));   // LDS form: every wave's slice is sized for the launch's largest problem
-  uint64_t* const my_keys = reinterpret_cast<uint64_t*>(slices + (size_t)wave * slice_words);
-  uint32_t* const my_idx = reinterpret_cast<uint32_t*>(my_keys + p2);
-
-  const double2* const px = reinterpret_cast<const double2*>(xn) + P.start;
-  const double* const pX = X3d + 3 * P.start;
-  const double loge0 = P.loge0;
-  const double logalpha0 = 0.49714987269413385;   // log10(M_PI)
-
-  // tables and generator
-  for (uint32_t k = tid; k <= n; k += n_threads) {
-    pool[k] = k;
-    logc_k[k] = logcombi(kDltSample, k, l10);
-  }
-  if (tid == 0) {   // logc_n[k] = logcombi(k, n): the running float sum, then the mirror (as in the P3P loop)
-    float r = 0.f;
-    logc_n[0] = 0.f;
-    for (uint32_t i = 1; i <= n / 2; ++i) { r += l10[n - i + 1] - l10[i]; logc_n[i] = r; }
-  }
-  __syncthreads();
-  for (uint32_t k = n / 2 + 1 + tid; k <= n; k += n_threads) logc_n[k] = k >= n ? 0.f : logc_n[n - k];
-  for (int i = tid; i < kMtN; i += n_threads) mt[i] = mt_init[i];
-  int mt_idx = kMtN, mt_idx_saved = kMtN;   // (tracked by wave 0 alone)
-  __syncthreads();
-
-  const uint32_t Wa = waves_ahead ? waves_ahead : (uint32_t)kResWaves;
-  double minNFA = INFINITY, errorMax = INFINITY;
-  if (tid == 0)
-    for (int e = 0; e < 12; ++e) best_model[e] = 0.0;
-  uint32_t n_inl = 0, pool_n = n;
-  int nIterReserve = (int)(max_iteration / 10);
-  uint32_t nIter = max_iteration - (uint32_t)nIterReserve;
-  uint32_t iter = 0, n_models_total = 0;
-
-  while (iter < nIter && iter < max_iteration) {
-    const uint32_t nb = min(Wa, min(nIter - iter, max_iteration - iter));
-    // ---- the samples of the block, drawn in iteration order from the one generator (wave 0) ----
-    if (wave == 0) {
-      for (int i = lane; i < kMtN; i += 64) mt_saved[i] = mt[i];   // (a twist cannot be taken back: the state before the block is kept)
-      wave_sync();
-      mt_idx_saved = mt_idx;
-      for (uint32_t j = 0; j < nb; ++j) {
-        for (uint32_t i = 0; i < (uint32_t)kDltSample; ++i) {
-          const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
-          if (lane == 0) {   // (lane 0 alone reads and writes the pool here)
-            const uint32_t a = pool[i], b = pool[r];
-            pool[i] = b; pool[r] = a;
-            swaps[kDltSample * j + i] = r;
-          }
-        }
-        if (lane == 0)
-          for (int i = 0; i < kDltSample; ++i) samples[kDltSample * j + i] = pool[i];
-      }
+// ---- what the six-point solver gives the exhaustive loop of mvgx_resection_loop.h ----
+struct ResDltForm {
+  using Problem = DltProblem;
+  using Layout = ResLayout<kDltSample, kResVerdict, kDltWork, 0, true>;
+  static constexpr int kSample = kDltSample, kMaxModels = 1, kModelAt = kDltP;
+  const double2* px;   // the normalised pixels of the prepare pass
+  const double* pX;
+  __device__ __forceinline__ ResDltForm(const DltProblem& P, const double* __restrict__, const double* __restrict__ X3d, const double* __restrict__ xn, int)
+      : px(reinterpret_cast<const double2*>(xn) + P.start), pX(X3d + 3 * P.start) {}
+  __device__ __forceinline__ void load_sample(const uint32_t* sample, double* work, double*, int lane) const {
+    if (lane < kDltSample) {
+      const uint32_t s = sample[lane];
+      const double2 obs = px[s];
+      work[kDltPix + 2 * lane] = obs.x; work[kDltPix + 2 * lane + 1] = obs.y;
+      work[kDltPts + 3 * lane] = pX[3 * s]; work[kDltPts + 3 * lane + 1] = pX[3 * s + 1]; work[kDltPts + 3 * lane + 2] = pX[3 * s + 2];
     }
-    __syncthreads();
-
-    // ---- one wave, one iteration ----
-    if ((uint32_t)wave < nb) {
-      double* const work = works + kDltWork * wave;
-      double* const my_verdict = verdicts + kResVerdict * wave;
-      if (lane < kDltSample) {
-        const uint32_t s = samples[kDltSample * wave + lane];
-        const double2 obs = px[s];
-        work[kDltPix + 2 * lane] = obs.x; work[kDltPix + 2 * lane + 1] = obs.y;
-        work[kDltPts + 3 * lane] = pX[3 * s]; work[kDltPts + 3 * lane + 1] = pX[3 * s + 1]; work[kDltPts + 3 * lane + 2] = pX[3 * s + 2];
-      }
-      wave_sync();
-      const int nm = dlt_solve(work, lane);
-      const double* const M = work + kDltP;
-      double run_min = minNFA, win_err = 0.0;
-      bool winner = false;
-      uint32_t win_k = 0, evaluated = 0;
-      const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5], m6 = M[6], m7 = M[7], m8 = M[8], m9 = M[9], m10 = M[10], m11 = M[11];
-      // a model with a non-finite entry is skipped (the reference would sort NaNs: undefined)
-      const double probe = m0 + m1 + m2 + m3 + m4 + m5 + m6 + m7 + m8 + m9 + m10 + m11;
-      if (nm > 0 && fabs(probe) < INFINITY) {
-        for (uint32_t i = lane; i < p2; i += 64) {
-          double e = INFINITY;
-          if (i < n) {
-            // | x - hnormalized(P (X, 1)) |^2 in normalised pixels
-            const double X = pX[3 * i], Y = pX[3 * i + 1], Z = pX[3 * i + 2];
-            const double u = add_rn(add_rn(add_rn(mul_rn(m0, X), mul_rn(m1, Y)), mul_rn(m2, Z)), m3);
-            const double v = add_rn(add_rn(add_rn(mul_rn(m4, X), mul_rn(m5, Y)), mul_rn(m6, Z)), m7);
-            const double w = add_rn(add_rn(add_rn(mul_rn(m8, X), mul_rn(m9, Y)), mul_rn(m10, Z)), m11);
-            const double2 obs = px[i];
-            const double rx = add_rn(obs.x, -(u / w)), ry = add_rn(obs.y, -(v / w));
-            e = add_rn(mul_rn(rx, rx), mul_rn(ry, ry));
-            if (!(e < INFINITY)) e = INFINITY;   // NaN too
-          }
-          my_keys[i] = (uint64_t)__double_as_longlong(e);
-          my_idx[i] = i;
-        }
-        wave_sync();
-        res_sort(my_keys, my_idx, p2, lane);
-        ++evaluated;
-        // NFA(k) for every k in [7, n]: the smallest, the lowest k among equals
-        double best = INFINITY;
-        uint32_t best_k = kDltSample;
-        for (uint32_t k = kDltSample + 1 + lane; k <= n; k += 64) {
-          const double r = __longlong_as_double((long long)my_keys[k - 1]);
-          const double logalpha = add_rn(logalpha0, log10(add_rn(r, kResFltEps)));
-          const double nfa = add_rn(add_rn(add_rn(loge0, mul_rn(logalpha, (double)(k - kDltSample))), (double)logc_n[k]), (double)logc_k[k]);
-          if (nfa < best) { best = nfa; best_k = k; }
-        }
-        for (int d = 32; d > 0; d >>= 1) {
-          const double o = __shfl_xor(best, d);
-          const uint32_t ok = (uint32_t)__shfl_xor((int)best_k, d);
-          if (o < best || (o == best && ok < best_k)) { best = o; best_k = ok; }
-        }
-        if (best < run_min) {
-          run_min = best; winner = true; win_k = best_k;
-          win_err = __longlong_as_double((long long)my_keys[best_k - 1]);
-        }
-      }
-      wave_sync();
-      if (lane == 0) {
-        my_verdict[0] = winner ? 1.0 : 0.0;
-        my_verdict[1] = run_min; my_verdict[2] = (double)win_k; my_verdict[3] = win_err;
-        for (int e = 0; e < 12; ++e) my_verdict[4 + e] = M[e];
-        my_verdict[16] = (double)evaluated;
-      }
-    }
-    __syncthreads();
-
-    // ---- the verdicts in iteration order: the first event is applied, what follows it is void ----
-    uint32_t done = nb;
-    bool event = false;
-    for (uint32_t j = 0; j < nb && !event; ++j) {
-      const double* const v = verdicts + kResVerdict * j;
-      n_models_total += (uint32_t)v[16];
-      const bool better = v[0] != 0.0;   // (evaluated under the block's minNFA, which no earlier verdict of the block has changed)
-      if (better) {
-        minNFA = v[1]; errorMax = v[3]; n_inl = (uint32_t)v[2];
-        if (tid == 0)
-          for (int e = 0; e < 12; ++e) best_model[e] = v[4 + e];
-        const uint32_t* const src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint64_t*>(slices + (size_t)j * slice_words) + p2);
-        for (uint32_t i = tid; i < n_inl; i += n_threads) inliers[i] = src[i];
-        if (trace && tid == 0) {   // test hook: iteration | k | the head of the sorted list, one record per iteration that found a better model
-          uint32_t* const T = trace + (size_t)pi * res_trace_words(trace_events);
-          const uint32_t at = T[0];
-          if (at < trace_events) {
-            uint32_t* const rec = T + 1 + (size_t)kResTraceRecord * at;
-            rec[0] = iter + j; rec[1] = n_inl;
-            for (uint32_t i = 0; i < (uint32_t)kResTraceRecord - 2; ++i) rec[2 + i] = i < n_inl ? src[i] : 0xffffffffu;
-          }
-          T[0] = at + 1;
-        }
-      }
-      const bool branch = (better && minNFA < 0) || ((iter + j + 1) == nIter && nIterReserve > 0);
-      bool take_pool = false;
-      if (branch) {
-        if (n_inl == 0) { ++nIter; --nIterReserve; }
-        else {
-          take_pool = true;
-          if (nIterReserve) { nIter = iter + j + 1 + (uint32_t)nIterReserve; nIterReserve = 0; }
-        }
-      }
-      if (better || branch) {
-        event = true;
-        done = j + 1;
-        __syncthreads();   // the inlier list is complete; wave 0 may touch the pool
-        if (done < nb && wave == 0) {
-          // the generator and the pool as they stood after iteration j: undo the block's swaps, restore the state, draw j + 1 again
-          if (lane == 0)
-            for (int s = kDltSample * (int)nb - 1; s >= 0; --s) {
-              const uint32_t i = (uint32_t)s % kDltSample, r = swaps[s];
-              const uint32_t a = pool[i], b = pool[r];
-              pool[i] = b; pool[r] = a;
-            }
-          for (int i = lane; i < kMtN; i += 64) mt[i] = mt_saved[i];
-          wave_sync();
-          mt_idx = mt_idx_saved;
-          for (uint32_t jj = 0; jj < done; ++jj)
-            for (uint32_t i = 0; i < (uint32_t)kDltSample; ++i) {
-              const uint32_t r = uniform_u32(mt, mt_idx, lane, i, pool_n - 1);
-              if (lane == 0) { const uint32_t a = pool[i], b = pool[r]; pool[i] = b; pool[r] = a; }
-            }
-        }
-        __syncthreads();
-        if (take_pool) {   // vec_index = vec_inliers: in sorted order
-          for (uint32_t i = tid; i < n_inl; i += n_threads) pool[i] = inliers[i];
-          pool_n = n_inl;
-        }
-      }
-    }
-    iter += done;
-    __syncthreads();
   }
-
-  if (minNFA >= 0) n_inl = 0;   // no meaningful model
-  for (uint32_t i = tid; i < n_inl; i += n_threads) inliers_out[P.start + i] = inliers[i];
-  if (tid == 0) {
-    ResResult& R = results[pi];
-    for (int e = 0; e < 12; ++e) R.P[e] = best_model[e];
-    R.error_max = errorMax; R.min_nfa = minNFA; R.n_inliers = n_inl; R.n_iterations = iter; R.n_models = n_models_total; R.pad_ = 0;
+  __device__ __forceinline__ int solve(double* work, const double*, uint32_t*, int lane) const { return dlt_solve(work, lane); }
+  // | x - hnormalized(P (X, 1)) |^2 in normalised pixels
+  __device__ __forceinline__ double residual(const ResRt& M, uint32_t i) const {
+    const double X = pX[3 * i], Y = pX[3 * i + 1], Z = pX[3 * i + 2];
+    const double u = add_rn(add_rn(add_rn(mul_rn(M.m0, X), mul_rn(M.m1, Y)), mul_rn(M.m2, Z)), M.m3);
+    const double v = add_rn(add_rn(add_rn(mul_rn(M.m4, X), mul_rn(M.m5, Y)), mul_rn(M.m6, Z)), M.m7);
+    const double w = add_rn(add_rn(add_rn(mul_rn(M.m8, X), mul_rn(M.m9, Y)), mul_rn(M.m10, Z)), M.m11);
+    const double2 obs = px[i];
+    const double rx = add_rn(obs.x, -(u / w)), ry = add_rn(obs.y, -(v / w));
+    return add_rn(mul_rn(rx, rx), mul_rn(ry, ry));
   }
-}
-
-// ---- host ----
-template <bool kGlobal>
-int dlt_launch(uint32_t n_work, uint32_t lds_bytes, hipStream_t stream, const DltProblem* problems, const uint32_t* order, const double* xn, const double* X3d,
-               const float* l10, const uint32_t* mt_init, uint32_t max_iteration, uint32_t waves_ahead, uint32_t n_lds_max, unsigned char* scratch, ResResult* results,
-               uint32_t* inliers_out, uint32_t* trace, uint32_t trace_events) {
-  MVGX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resection_dlt_acransac_kernel<kGlobal>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((resection_dlt_acransac_kernel<kGlobal>), dim3(n_work), dim3(64 * kResWaves), lds_bytes, stream, problems, order, n_work, xn, X3d, l10, mt_init,
-                     max_iteration, waves_ahead, n_lds_max, scratch, results, inliers_out, trace, trace_events);
-  MVGX_HIP(hipGetLastError());
-  return MVGX_OK;
-}
-
-// The staging buffer of the uncalibrated entry (the layout of res_stage): problem table | launch lists | log10 table | generator state
-int dlt_stage(ResCall& c, const uint64_t* start, const uint32_t* image_wh) {
-  const uint32_t n_problems = c.n_problems;
-  int rc;
-  c.n_lists = c.in_lds.size() + c.in_global.size();
-  c.prob_words = (size_t)n_problems * sizeof(DltProblem) / 4;
-  c.bound_words = 0;
-  c.l10_n = (size_t)c.n_max + 2;
-  c.stage_words = c.prob_words + c.n_lists + c.l10_n + kMtN;
-  if ((rc = c.stage.ensure((c.stage_words + 1) / 2))) return rc;
-  DltProblem* const hp = reinterpret_cast<DltProblem*>(c.stage.p);
-  c.h_lists = reinterpret_cast<uint32_t*>(c.stage.p) + c.prob_words;
-  float* const h_l10 = reinterpret_cast<float*>(c.h_lists + c.n_lists);
-  uint32_t* const h_mt = reinterpret_cast<uint32_t*>(h_l10 + c.l10_n);
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    DltProblem& g = hp[p];
-    const uint32_t n = (uint32_t)(start[p + 1] - start[p]);
-    const int width = (int)image_wh[2 * p], height = (int)image_wh[2 * p + 1];
-    g.start = start[p] - c.base; g.n = n; g.pad_ = 0; g.scratch = 0;
-    // PreconditionerFromPoints(width, height, &T) (conditioning.cpp:54-62): the x offset goes through a float product (-.5f * width)
-    g.d_norm = 1.0 / std::sqrt(static_cast<double>(width * height));
-    g.off_x = -.5f * width * g.d_norm;
-    g.off_y = -.5 * height * g.d_norm;
-    g.loge0 = n > (uint32_t)kDltSample ? std::log10((double)(n - kDltSample)) : 0.0;   // MAX_MODELS = 1, MINIMUM_SAMPLES = 6
-  }
-  c.scratch_bytes = 0;
-  for (uint32_t p : c.in_global) { hp[p].scratch = c.scratch_bytes; c.scratch_bytes += res_scratch_bytes(hp[p].n); }
-  if (!c.in_lds.empty()) memcpy(c.h_lists, c.in_lds.data(), c.in_lds.size() * 4);
-  if (!c.in_global.empty()) memcpy(c.h_lists + c.in_lds.size(), c.in_global.data(), c.in_global.size() * 4);
-  for (size_t i = 0; i < c.l10_n; ++i) h_l10[i] = (float)::log10((double)static_cast<float>(i));
-  h_mt[0] = 5489u;   // std::mt19937::default_seed
-  for (int i = 1; i < kMtN; ++i) h_mt[i] = 1812433253u * (h_mt[i - 1] ^ (h_mt[i - 1] >> 30)) + (uint32_t)i;
-  return MVGX_OK;
-}
+};
+static_assert(4 * ResDltForm::Layout::words(kDltLdsMaxN) <= 160 * 1024, "the LDS form must fit a workgroup's 160 KiB");
 
 }  // namespace
 
@@ -541,6 +284,7 @@ int mvgx_resection_localize_uncalibrated(int device, uint32_t n_problems, const 
   ResCall c;
   c.entry = fn;
   int rc;
+  bool work = false;
   MVGX_REQUIRE(opt && start && out_ok && out_pose && out_P && out_K && out_error_max && out_min_nfa && out_inlier_start, MVGX_ERR_ARG, "%s: NULL argument", fn);
   MVGX_REQUIRE(n_problems == 0 || image_wh, MVGX_ERR_ARG, "%s: NULL image sizes", fn);
   MVGX_REQUIRE(opt->solver == MVGX_RESECTION_DLT_6POINTS, MVGX_ERR_ARG,
@@ -548,113 +292,49 @@ int mvgx_resection_localize_uncalibrated(int device, uint32_t n_problems, const 
   MVGX_REQUIRE(!std::isfinite(opt->error_max), MVGX_ERR_UNSUPPORTED,
                "%s: a finite error_max selects the quantified NFA with the max-consensus early exit, which the six-point loop has no device path for", fn);
   MVGX_REQUIRE(std::isinf(opt->error_max) && opt->error_max > 0, MVGX_ERR_ARG, "%s: error_max must be +infinity", fn);
-  MVGX_REQUIRE(opt->waves_ahead <= (uint32_t)kResWaves, MVGX_ERR_ARG, "%s: waves_ahead %u exceeds the build's %d", fn, opt->waves_ahead, kResWaves);
-  c.n_problems = n_problems;
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    MVGX_REQUIRE(start[p + 1] >= start[p], MVGX_ERR_ARG, "%s: start decreases at problem %u", fn, p);
-    const uint64_t n = start[p + 1] - start[p];
-    MVGX_REQUIRE(n <= kResMaxN, MVGX_ERR_ARG, "%s: problem %u has %llu correspondences, the supported maximum is %u", fn, p, (unsigned long long)n, kResMaxN);
-    const uint64_t w = image_wh[2 * p], h = image_wh[2 * p + 1];
-    MVGX_REQUIRE(w > 0 && h > 0 && w * h <= 0x7fffffffull, MVGX_ERR_ARG, "%s: problem %u: image size %llu x %llu (both must be > 0, their product an int)", fn, p,
-                 (unsigned long long)w, (unsigned long long)h);
-    c.n_max = std::max(c.n_max, (uint32_t)n);
-  }
-  if (stats) memset(stats, 0, sizeof(*stats));
-  for (uint32_t p = 0; p < n_problems; ++p) { out_ok[p] = 0; out_error_max[p] = 0.0; out_min_nfa[p] = 0.0; }
-  for (uint32_t p = 0; p <= n_problems; ++p) out_inlier_start[p] = 0;
-  if (!n_problems) return MVGX_OK;
-  c.base = start[0];
-  c.n_total = start[n_problems] - c.base;
-  MVGX_REQUIRE(c.n_total == 0 || (x2d && X3d && out_inliers), MVGX_ERR_ARG, "%s: NULL correspondence arrays", fn);
-  // the storage form per problem: the LDS form up to kDltLdsMaxN, global scratch above it
-  const uint32_t lds_bound = opt->global_above ? std::min(opt->global_above, kDltLdsMaxN) : kDltLdsMaxN;
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    const uint64_t n = start[p + 1] - start[p];
-    if (n > (uint64_t)kDltSample) (n <= lds_bound ? c.in_lds : c.in_global).push_back(p);   // ACRANSAC's early return below that
-  }
-  const auto by_n = [&](uint32_t a, uint32_t b) { const uint64_t na = start[a + 1] - start[a], nb = start[b + 1] - start[b]; return na != nb ? na > nb : a < b; };
-  std::sort(c.in_lds.begin(), c.in_lds.end(), by_n);
-  std::sort(c.in_global.begin(), c.in_global.end(), by_n);
-  if (c.in_lds.empty() && c.in_global.empty()) return MVGX_OK;
+  if ((rc = res_check_batch(c, n_problems, start, opt, [&](uint32_t p) -> int {
+         const uint64_t w = image_wh[2 * p], h = image_wh[2 * p + 1];
+         MVGX_REQUIRE(w > 0 && h > 0 && w * h <= 0x7fffffffull, MVGX_ERR_ARG, "%s: problem %u: image size %llu x %llu (both must be > 0, their product an int)", fn, p,
+                      (unsigned long long)w, (unsigned long long)h);
+         return MVGX_OK;
+       })))
+    return rc;
+  if ((rc = res_classify(c, kDltSample, start, x2d, X3d, out_inliers, opt->global_above, kDltLdsMaxN, out_ok, out_error_max, out_min_nfa, out_inlier_start, stats, &work)))
+    return rc;
+  if (!work) return MVGX_OK;
   if ((rc = mvgx::select_device(device < 0 ? -1 : device))) return rc;
-  if ((rc = dlt_stage(c, start, image_wh))) return rc;
+  if ((rc = res_stage<DltProblem>(c, start, 0, &ResDltForm::Layout::scratch_bytes, [&](uint32_t p, uint32_t n, DltProblem& g) {
+         const int width = (int)image_wh[2 * p], height = (int)image_wh[2 * p + 1];
+         g.pad_ = 0;
+         // PreconditionerFromPoints(width, height, &T) (conditioning.cpp:54-62): the x offset goes through a float product (-.5f * width)
+         g.d_norm = 1.0 / std::sqrt(static_cast<double>(width * height));
+         g.off_x = -.5f * width * g.d_norm;
+         g.off_y = -.5 * height * g.d_norm;
+         g.loge0 = n > (uint32_t)kDltSample ? std::log10((double)(n - kDltSample)) : 0.0;   // MAX_MODELS = 1, MINIMUM_SAMPLES = 6
+       })))
+    return rc;
   if ((rc = res_upload(c, x2d, X3d))) return rc;
-  uint32_t* const host_trace = g_res_trace;   // (one call only)
-  const uint32_t trace_events = host_trace ? g_res_trace_events : 0;
-  g_res_trace = nullptr;
-  const size_t trace_words = (size_t)n_problems * res_trace_words(trace_events);
-  if (host_trace) {
-    if ((rc = c.d_trace.ensure(trace_words))) return rc;
-    MVGX_HIP(hipMemsetAsync(c.d_trace.p, 0, trace_words * sizeof(uint32_t), c.stream));
-  }
-  uint32_t* const p_trace = host_trace ? c.d_trace.p : nullptr;
-  const DltProblem* const hp = reinterpret_cast<const DltProblem*>(c.stage.p);
-  const DltProblem* const p_prob = reinterpret_cast<const DltProblem*>(c.d_stage.p);
-  double* const p_xn = c.d_bear.p;   // (2 of its 3 doubles per correspondence)
-  {
-    const double* const p_x2d = c.d_x2d.p;
-    const uint64_t n_total = c.n_total;
-    MVGX_HIP(hipEventRecord(c.e0, c.stream));
-    hipLaunchKernelGGL(resection_dlt_normalize_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c.stream, p_prob, n_problems, n_total, p_x2d, p_xn);
-    MVGX_HIP(hipGetLastError());
-  }
-  if (!c.in_lds.empty()) {
-    const uint32_t n_lds_max = hp[c.in_lds[0]].n;   // (every workgroup of the launch gets the LDS of its largest problem)
-    if ((rc = dlt_launch<false>((uint32_t)c.in_lds.size(), dlt_lds_bytes(n_lds_max), c.stream, p_prob, c.p_lists(), p_xn, c.d_X.p, c.p_l10(), c.p_mt(), opt->max_iteration,
-                                opt->waves_ahead, n_lds_max, c.d_scratch.p, c.d_res.p, c.d_inl.p, p_trace, trace_events)))
-      return rc;
-  }
-  if (!c.in_global.empty()) {
-    if ((rc = dlt_launch<true>((uint32_t)c.in_global.size(), dlt_lds_bytes(0), c.stream, p_prob, c.p_lists() + c.in_lds.size(), p_xn, c.d_X.p, c.p_l10(), c.p_mt(),
-                               opt->max_iteration, opt->waves_ahead, 0, c.d_scratch.p, c.d_res.p, c.d_inl.p, p_trace, trace_events)))
-      return rc;
-  }
-  MVGX_HIP(hipEventRecord(c.e1, c.stream));
-  MVGX_HIP(hipMemcpyAsync(c.h_res.p, c.d_res.p, (size_t)n_problems * sizeof(ResResult), hipMemcpyDeviceToHost, c.stream));
-  std::vector<uint32_t> inl(c.n_total);   // the inlier lists come back in place (one list per problem at its start), then are packed
-  MVGX_HIP(hipMemcpyAsync(inl.data(), c.d_inl.p, c.n_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-  if (host_trace) MVGX_HIP(hipMemcpyAsync(host_trace, c.d_trace.p, trace_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-  MVGX_HIP(hipStreamSynchronize(c.stream));
-
-  uint64_t at = 0, iterations = 0, n_models = 0;
-  for (uint32_t p = 0; p < n_problems; ++p) {
-    out_inlier_start[p] = at;
-    const ResResult& r = c.h_res.p[p];
-    if (hp[p].n <= (uint32_t)kDltSample) continue;   // ACRANSAC's early return of (0, 0): nothing else is written
-    iterations += r.n_iterations; n_models += r.n_models;
-    out_min_nfa[p] = r.min_nfa;
-    const double d = hp[p].d_norm;
-    out_error_max[p] = r.n_inliers ? std::sqrt(r.error_max) / d : r.error_max;   // unormalizeError: sqrt(val) / N1(0, 0)
-    if (r.n_inliers) memcpy(out_inliers + at, inl.data() + hp[p].start, (size_t)r.n_inliers * sizeof(uint32_t));
-    at += r.n_inliers;
-    if ((double)r.n_inliers > 2.5 * kDltSample) {
-      // UnnormalizerResection: N1^-1 P, the inverse as Eigen's PartialPivLU of the dynamic matrix forms it (back substitution of I)
-      const double i00 = 1.0 / d, i02 = (0.0 - hp[p].off_x * 1.0) / d, i12 = (0.0 - hp[p].off_y * 1.0) / d;
-      double* const Pu = out_P + 12 * (size_t)p;
-      for (int e = 0; e < 4; ++e) {
-        Pu[e] = i00 * r.P[e] + i02 * r.P[8 + e];
-        Pu[4 + e] = i00 * r.P[4 + e] + i12 * r.P[8 + e];
-        Pu[8 + e] = r.P[8 + e];
-      }
-      double R[9], t[3];
-      res_krt_from_p(Pu, out_K + 9 * (size_t)p, R, t);
-      double* const pose = out_pose + 15 * (size_t)p;
-      for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) pose[4 * i + j] = R[3 * i + j];
-        pose[4 * i + 3] = t[i];
-        pose[12 + i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);   // C = -R^T t
-      }
-      out_ok[p] = 1;
-    }
-  }
-  out_inlier_start[n_problems] = at;
-  if (stats) {
-    float kernel_ms = 0.f;
-    (void)hipEventElapsedTime(&kernel_ms, c.e0, c.e1);
-    stats->n_problems = n_problems; stats->n_iterations = iterations; stats->n_models = n_models; stats->kernel_ms = kernel_ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return MVGX_OK;
+  if ((rc = res_trace_setup(c))) return rc;
+  if ((rc = res_prepare<DltProblem>(c, resection_dlt_normalize_kernel))) return rc;
+  if ((rc = res_launch(c, resection_acransac_kernel<ResDltForm, false>, resection_acransac_kernel<ResDltForm, true>, &ResDltForm::Layout::lds_bytes, c.p_prob<DltProblem>(),
+                       c.d_x2d.p, c.d_X.p, c.d_bear.p, c.p_l10(), c.p_mt(), opt->max_iteration, opt->solver, opt->waves_ahead, c.d_scratch.p, c.d_res.p, c.d_inl.p, c.p_trace(),
+                       c.trace_events)))
+    return rc;
+  return res_finish<DltProblem>(c, kDltSample, &DltProblem::d_norm, out_ok, out_error_max, out_min_nfa, out_inlier_start, out_inliers, stats, t_begin,
+                                [&](uint32_t p, const DltProblem& g, const ResResult& r) {
+                                  // UnnormalizerResection: N1^-1 P, the inverse as Eigen's PartialPivLU of the dynamic matrix forms it (back substitution of I)
+                                  const double d = g.d_norm;
+                                  const double i00 = 1.0 / d, i02 = (0.0 - g.off_x * 1.0) / d, i12 = (0.0 - g.off_y * 1.0) / d;
+                                  double* const Pu = out_P + 12 * (size_t)p;
+                                  for (int e = 0; e < 4; ++e) {
+                                    Pu[e] = i00 * r.P[e] + i02 * r.P[8 + e];
+                                    Pu[4 + e] = i00 * r.P[4 + e] + i12 * r.P[8 + e];
+                                    Pu[8 + e] = r.P[8 + e];
+                                  }
+                                  double R[9], t[3];
+                                  res_krt_from_p(Pu, out_K + 9 * (size_t)p, R, t);
+                                  res_write_pose(R, t, out_pose + 15 * (size_t)p);
+                                });
 }
 
 // Test hook (not declared in include/mvgx.h): the six-point solver alone, one wave per sample. x_norm: n_samples x 6 x 2 NORMALISED

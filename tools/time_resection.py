@@ -1,16 +1,19 @@
 """Times mvgx_resection_localize on the MI355X: 1 / 16 / 256 problems of 100 / 1 000 / 10 000 correspondences, 30 % outliers.
 
-  python tools/time_resection.py [--repeat 3] [--solver ding] [--max-iteration 4096] [--error-max PX] [--uncalibrated]
+  python tools/time_resection.py [--repeat 3] [--solver ding] [--max-iteration 4096] [--error-max PX] [--uncalibrated] [--digest]
 
 --error-max PX (finite): the bounded form, mvgx_resection_localize_bounded, on the same problems.
 --uncalibrated: mvgx_resection_localize_uncalibrated (the six-point DLT loop of a view without intrinsics) on the same problems, the
 image size 1280 x 960 in place of the intrinsics. With --max-iteration 1 every problem runs one solve, one sort and one NFA scan: the
 fixed part that the solver's share of the kernel time is read against (models / iterations of the full run are printed for it).
+--digest: every line also carries a sha256 over what the last call returned - ok, pose, P (and K of the uncalibrated entry), error_max,
+min_nfa and the inlier list of every problem: two builds of the library that print the same digests computed the same bits.
 
 Prints one JSON line per (problems, correspondences): kernel_ms = HIP events around the prepare pass and the a-contrario kernels
 (mvgx_resection_stats), total_ms = the whole call with uploads, downloads, KRt_From_P on the host; medians over --repeat calls after one
 warm-up call; iterations = a-contrario iterations run over all problems. Needs a GPU: there is no CPU path."""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -40,6 +43,18 @@ def make_problems(n_problems, n, outliers=0.3, noise=0.5, seed=0x5E):
     return (np.arange(n_problems + 1, dtype=np.uint64) * n, np.concatenate(x2d), np.concatenate(X3d), np.ones(n_problems, np.int32), intr), poses
 
 
+def digest(out):
+    """sha256 over the outputs of one call (a list of resection.Localization), problem by problem"""
+    h = hashlib.sha256()
+    for o in out:
+        h.update(bytes([int(o.ok)]))
+        for a in (o.R, o.t, o.C, o.P, getattr(o, "K", None), o.error_max, o.min_nfa):
+            if a is not None:
+                h.update(np.ascontiguousarray(a, np.float64).tobytes())
+        h.update(np.ascontiguousarray(o.inliers, np.uint32).tobytes())
+    return h.hexdigest()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=3)
@@ -47,6 +62,7 @@ def main():
     ap.add_argument("--max-iteration", type=int, default=4096)
     ap.add_argument("--error-max", type=float, default=float("inf"), help="a finite bound in pixels times the bounded form")
     ap.add_argument("--uncalibrated", action="store_true", help="times mvgx_resection_localize_uncalibrated (six-point DLT, no intrinsics)")
+    ap.add_argument("--digest", action="store_true", help="adds a sha256 over the last call's outputs to every line")
     ap.add_argument("--problems", type=int, nargs="*", default=[1, 16, 256])
     ap.add_argument("--sizes", type=int, nargs="*", default=[100, 1000, 10000])
     a = ap.parse_args()
@@ -70,10 +86,11 @@ def main():
                 out, st = run(*args, **kw)
                 kernel.append(st.kernel_ms); total.append(st.total_ms)
             err = [float(np.abs(o.R - R).max()) for o, (R, _) in zip(out, poses) if o.ok]
+            extra = dict(digest=digest(out)) if a.digest else {}
             print(json.dumps(dict(problems=n_problems, correspondences=n, solver="dlt6" if a.uncalibrated else a.solver, max_iteration=a.max_iteration,
                                   error_max=a.error_max if bounded else None, kernel_ms_median=float(np.median(kernel)), kernel_ms_min=float(min(kernel)), kernel_ms_max=float(max(kernel)),
                                   total_ms_median=float(np.median(total)), iterations=int(st.n_iterations), models=int(st.n_models),
-                                  ok=int(sum(o.ok for o in out)), largest_rotation_error=max(err) if err else None)), flush=True)
+                                  ok=int(sum(o.ok for o in out)), largest_rotation_error=max(err) if err else None, **extra)), flush=True)
 
 
 if __name__ == "__main__":
