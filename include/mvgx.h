@@ -546,8 +546,8 @@ int mvgx_geofilter_e_acransac_indexed(int device, const double* feat_xy, const d
  * bound D2R(precision) is compared with the SQUARED angles as it is. results[p].F receives m_E scaled to unit Frobenius norm (the
  * reference's eigenvector; the sign is free), results[p].precision_robust = ACRansacOut.first (radians), inlier_mask / n_inliers / ok
  * describe the a-contrario result; the functor's second stage - RelativePoseFromEssential on those inliers (cheirality), E_ACRobust_
- * Angular.hpp:126-143 - is host work on a handful of points per pair and stays with the caller (the replacement TU runs the
- * reference's own function). Bearing vectors: 3 doubles per match, or per feature in the indexed form. */
+ * Angular.hpp:126-143 - is not part of this entry: mvgx_relative_pose_from_essential below runs it on the device for a batch of
+ * pairs (the replacement TU keeps calling the reference's own function). Bearing vectors: 3 doubles per match, or per feature in the indexed form. */
 int mvgx_geofilter_e_angular_acransac(int device, const double* bearingI, const double* bearingJ, const uint64_t* match_start, uint64_t n_pairs,
                                       int upright, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
                                       mvgx_geofilter_stats* stats /* may be NULL */);
@@ -734,6 +734,85 @@ int mvgx_resection_localize_uncalibrated(int device, uint32_t n_problems, const 
                                          double* out_pose /* n_problems x 15 */, double* out_P /* n_problems x 12 */, double* out_K /* n_problems x 9 */,
                                          double* out_error_max, double* out_min_nfa, uint64_t* out_inlier_start /* n_problems + 1 */, uint32_t* out_inliers,
                                          mvgx_resection_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Relative pose of image pairs (no ABI bump: detect it by the symbol): from an essential matrix to (R, t) by cheirality, and the whole
+ * of sfm::robustRelativePose -
+ *   multiview/essential.cpp:79-113                         MotionFromEssential: the four candidate motions of E
+ *   multiview/motion_from_essential.cpp:20-95              RelativePoseFromEssential: the cheirality vote and the ratio test
+ *   sfm/pipelines/sfm_robust_model_estimation.cpp:29-120   robustRelativePose, as Relative_Pose_Engine::Process (sfm/pipelines/
+ *                                                          relative_pose_engine.cpp:87-223; 256 iterations, Square(2.5)), the sequential
+ *                                                          engine's initial pair (sequential_SfM.cpp:396-398, :531; 4096, Square(4.0)) and
+ *                                                          SfmSceneInitializerMaxPair.cpp:97-98 call it
+ * A batch of independent pairs, one wave each. Pair p owns the correspondences [start[p], start[p + 1]) of the two bearing arrays (3
+ * doubles each: what the camera's operator() returns).
+ * Reproduced: the candidates R in {U W V^T, U W^T V^T}, t = +-u3 after the two determinant fixes; Triangulate2View(method) of every
+ * listed correspondence under each candidate with the first camera at the origin; the winner = the FIRST maximum of the four counts,
+ * rejected unless its count is above 0 and second / best < positive_depth_ratio in double arithmetic; the selected positions in the
+ * order of the list and their points. Not reproduced: Eigen's JacobiSVD - the singular vectors come from a one-sided Jacobi iteration,
+ * so R, t and the points agree to rounding, and the ORDER of the four candidates follows this build's sign choices: a sign matrix that
+ * flips U and V together can turn W into W^T, which swaps candidates 0 <-> 1 and 2 <-> 3. Nothing reported for an accepted pair depends
+ * on that order (a tie for the first place rejects the pair: its ratio is 1); compare `cheirality` as a sorted tuple. t is u3 itself
+ * (Pose3 stores the centre and returns -(R C)); n_selected == the largest entry of cheirality, always.
+ * A pair that is not ok: pose zeros, n_selected 0, nothing written to the lists (the reference leaves stale values, its callers drop
+ * the pair). */
+#define MVGX_RELPOSE_PINHOLE 0
+#define MVGX_RELPOSE_ANGULAR 1
+typedef struct mvgx_relative_pose_options {
+  int32_t  kind;                   /* robust entry: MVGX_RELPOSE_PINHOLE (five-point, pixel epipolar error) or
+                                      MVGX_RELPOSE_ANGULAR (eight-point on bearing vectors; a camera that is not a pinhole) */
+  int32_t  method;                 /* ETriangulationMethod 0..3; default 3 (INVERSE_DEPTH_WEIGHTED_MIDPOINT) */
+  double   positive_depth_ratio;   /* 0.7 */
+  double   residual_tolerance;     /* robust entry: RelativePose_Info::initial_residual_tolerance AS THE REFERENCE TAKES IT:
+                                      squared pixels (pinhole), degrees (angular). Must be finite and > 0 */
+  uint32_t max_iterations;         /* robust entry: 256 (global engine), 4096 (sequential) */
+} mvgx_relative_pose_options;
+typedef struct mvgx_relative_pose_result {
+  double   pose[15];               /* R | t row-major 3 x 4, then the centre C = -R^T t  (layout of mvgx_resection_localize) */
+  double   E[9];                   /* the essential matrix used (robust entry: the a-contrario model)            */
+  double   found_precision;        /* robust entry: ACRansacOut.first as robustRelativePose stores it (angular: R2D) */
+  uint32_t cheirality[4];          /* points in front under each candidate, in this build's candidate order      */
+  uint32_t n_acransac_inliers;     /* robust entry                                                                */
+  uint32_t n_selected;             /* |vec_selected_points| of the winner                                         */
+  uint32_t ok;
+} mvgx_relative_pose_result;
+typedef struct mvgx_relative_pose_stats {
+  uint64_t n_pairs, n_pairs_ok, n_selected;
+  double kernel_ms;                /* device time of the cheirality kernel (HIP events)                           */
+  double acransac_kernel_ms;       /* robust entry: device time of the a-contrario stage before it                */
+  double total_ms;                 /* the whole call incl. transfers                                              */
+} mvgx_relative_pose_stats;
+void mvgx_relative_pose_default_options(mvgx_relative_pose_options*);   /* PINHOLE, 3, 0.7, Square(2.5), 256 */
+/* The cheirality stage alone: RelativePoseFromEssential on E + 9 p. use_index rows [use_start[p], use_start[p + 1]) are the positions
+ * within the pair to vote with (bearing_vector_index_to_use: any order, a subset, repeats allowed); use_index == NULL (use_start is then
+ * not read): all correspondences of the pair in their order - the call Relative_Pose_Engine makes with the winning pose's E to build
+ * its tiny scene (relative_pose_engine.cpp:168-187). Outputs: results[p]; out_selected_start (n_pairs + 1 offsets), out_selected /
+ * out_X (room for every list entry: 1 / 3 values each) = vec_selected_points / vec_points of the accepted pairs, one after the other.
+ * MVGX_ERR_ARG (outputs untouched): NULL arrays, a decreasing start, an index outside its pair, positive_depth_ratio outside (0, 1], a
+ * method outside 0..3. kind, residual_tolerance and max_iterations are not read. */
+int mvgx_relative_pose_from_essential(int device, uint32_t n_pairs, const uint64_t* start /* n_pairs + 1 */, const double* bearingI,
+                                      const double* bearingJ, const double* E /* n_pairs x 9, row-major */,
+                                      const uint64_t* use_start /* n_pairs + 1, or NULL */, const uint32_t* use_index /* or NULL */,
+                                      const mvgx_relative_pose_options* opt, mvgx_relative_pose_result* results,
+                                      uint64_t* out_selected_start /* n_pairs + 1 */, uint32_t* out_selected, double* out_X,
+                                      mvgx_relative_pose_stats* stats /* may be NULL */);
+/* robustRelativePose from start to end on the device: the E a-contrario stage of the geometric filter (PINHOLE: the five-point form of
+ * mvgx_geofilter_e_acransac with its inputs - pixels, bearings, image_wh, K per pair; ANGULAR: the eight-point form of
+ * mvgx_geofilter_e_angular_acransac - xI, xJ, image_wh, K are not read), then the stage above on the a-contrario inliers; bearings,
+ * mask and model stay on the device between the two, one download at the end. opt->residual_tolerance goes to the loop AS GIVEN
+ * (robustRelativePose hands initial_residual_tolerance to ACRANSAC unchanged: squared pixels; angular: D2R of it) - the filter entries
+ * take the square root of that for the pinhole model. The pair goes on to the cheirality stage unless n_acransac_inliers < 2.5 x
+ * MINIMUM_SAMPLES (:70-74, :101-105): 13 of 5, 20 of 8 - the filter functor's rule is `>` and refuses 20. inlier_mask: the a-contrario
+ * inliers of every pair that passed that rule (whatever the cheirality stage then decides), zeros otherwise. out_selected_start /
+ * out_selected / out_X: as above, each may be NULL to skip it; positions in ASCENDING index (the reference's list is in ACRANSAC's
+ * order, no caller reads that order). MVGX_ERR_UNSUPPORTED: an infinite residual_tolerance (the exhaustive-NFA form has no E path on the
+ * device, and no caller of the reference passes it), more than 2^20 correspondences in a pair. MVGX_ERR_ARG as above and as the filter
+ * entries'. */
+int mvgx_relative_pose_robust(int device, const double* xI, const double* xJ, const double* bearingI, const double* bearingJ,
+                              const uint64_t* match_start /* n_pairs + 1 */, const uint32_t* image_wh, const double* K, uint64_t n_pairs,
+                              const mvgx_relative_pose_options* opt, uint8_t* inlier_mask, mvgx_relative_pose_result* results,
+                              uint64_t* out_selected_start /* n_pairs + 1, or NULL */, uint32_t* out_selected /* or NULL */,
+                              double* out_X /* or NULL */, mvgx_relative_pose_stats* stats /* may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@
   triangulation : blind / robust triangulation of the tracks of a scene    (openmvg_amd.triangulation)
   resection     : robust resection of views (AC-RANSAC over P3P), batched   (openmvg_amd.resection: localize for an unbounded
                   precision, localize_bounded for a finite error_max)
+  relative_pose : E to (R, t) by cheirality, and robustRelativePose from putative matches, batched (openmvg_amd.relative_pose:
+                  from_essential, robust for pinhole pairs, robust_angular on bearing vectors)
 
 All compute lives in openmvg_amd/lib/libmvgx_hip.so (hand-written HIP, C ABI in include/mvgx.h);
 the Python modules only mirror the reference's host interfaces. No CPU fallback exists.

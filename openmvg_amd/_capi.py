@@ -156,6 +156,24 @@ class ResectionStats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+MVGX_RELPOSE_PINHOLE, MVGX_RELPOSE_ANGULAR = 0, 1
+
+
+class RelativePoseOptions(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("method", C.c_int32), ("positive_depth_ratio", C.c_double), ("residual_tolerance", C.c_double),
+                ("max_iterations", C.c_uint32)]
+
+
+class RelativePoseResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 15), ("E", C.c_double * 9), ("found_precision", C.c_double), ("cheirality", C.c_uint32 * 4),
+                ("n_acransac_inliers", C.c_uint32), ("n_selected", C.c_uint32), ("ok", C.c_uint32)]
+
+
+class RelativePoseStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_pairs_ok", C.c_uint64), ("n_selected", C.c_uint64), ("kernel_ms", C.c_double),
+                ("acransac_kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 PROTOTYPES = {
     "mvgx_last_error": (C.c_char_p, []),
     "mvgx_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -261,6 +279,13 @@ PROTOTYPES = {
     "mvgx_resection_localize_uncalibrated": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ResectionOptions),
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.POINTER(ResectionStats)]),
+    "mvgx_relative_pose_default_options": (None, [C.POINTER(RelativePoseOptions)]),
+    "mvgx_relative_pose_from_essential": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(RelativePoseOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(RelativePoseStats)]),
+    "mvgx_relative_pose_robust": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.POINTER(RelativePoseOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(RelativePoseStats)]),
 }
 
 _lib = None

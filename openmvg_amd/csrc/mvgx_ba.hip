@@ -5914,3 +5914,4 @@ int mvgx_ba_evaluate(mvgx_ba_ctx* c, double* cost, double* rmse) {
 }  // extern "C"
 
 #include "mvgx_triangulate.h"   // mvgx_triangulate_tracks: the step between tracks + poses and the points BA adjusts
+#include "mvgx_relative_pose.h" // relative pose of image pairs: E to (R, t) by cheirality, on the two-view triangulation above

@@ -32,6 +32,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <numeric>
 #include <thread>
@@ -81,7 +82,8 @@ constexpr int kMtN = 624, kMtM = 397;
 
 struct GeoPair {   // per pair, prepared on the host (glibc's log10 / hypot / sqrt: the reference's values)
   uint64_t start;
-  uint32_t n, pad_;
+  uint32_t n;
+  uint32_t accept_at_bound;   // 0: the functors' acceptance, n_inliers > 2.5 x the sample; 1: robustRelativePose's, !(n_inliers < 2.5 x the sample)
   double max_threshold, loge0, bins_by_interval;
   double bin_value[kBins];
   double logalpha_bin[kBins];   // logalpha0 + multError * log10(bin_value + FLT_EPSILON)
@@ -1078,7 +1080,8 @@ __global__ __launch_bounds__(64 * WAVES, MODEL == kModelE ? MVGX_GEO_E_WGS : MVG
   if (lane == 0) { for (int k = 0; k < 6; ++k) atomicAdd(&g_geo_stamps[k], geo_acc_[k]); }
 #endif
   if (minNFA >= 0) inl_count = 0;   // no meaningful model (:477-478)
-  const bool good = (double)inl_count > kMin * 2.5;   // F_ACRobust.hpp:103, H_ACRobust.hpp:98
+  // F_ACRobust.hpp:103, H_ACRobust.hpp:98; accept_at_bound: sfm_robust_model_estimation.cpp:70-74, :101-105 (the two part at 20 inliers of the eight-point form)
+  const bool good = P.accept_at_bound ? !((double)inl_count < kMin * 2.5) : (double)inl_count > kMin * 2.5;
   {
     double F[9];
 #pragma unroll
@@ -1144,6 +1147,9 @@ struct GeoSource {
   // 18 doubles per pair {K_I, K_J}, or 9 per image when indexed)
   const double* bI = nullptr; const double* bJ = nullptr; const double* feat_bearing = nullptr; const double* K = nullptr;
   const double* pair_precision = nullptr;   // orthographic model: the bound of every pair (NULL: opt->precision for all)
+  // the route of mvgx_relative_pose_robust: opt->precision is the residual threshold itself where the model's functor would square it (the
+  // angular models take degrees on both routes), and a pair keeps mask and model from 2.5 x the sample on, not only above it
+  bool bound_as_given = false, accept_at_bound = false;
 };
 
 // The form of a run, resolved once per call: MVGX_GEO_GLOBAL_ABOVE = a smaller bound than kCap0 for the LDS class (tests: the global form on
@@ -1202,8 +1208,8 @@ inline void inverse3(const double* m, double* inv) {
 // model takes them and the caller's precision `bound`; norm = {s1, tx1, ty1, s2, tx2, ty2}: the points are normalised on the device. Every field of
 // g is written. The expressions and their order are the reference's: glibc's log10 / hypot / sqrt give its values bit for bit.
 void geo_pair_constants(const GeoModelDesc& d, uint64_t start, uint32_t n, const uint32_t* wh1, const uint32_t* wh2, const double* K1, const double* K2,
-                        double bound, GeoPair& g, double* norm) {
-  g.start = start; g.n = n; g.pad_ = 0;
+                        double bound, bool bound_as_given, bool accept_at_bound, GeoPair& g, double* norm) {
+  g.start = start; g.n = n; g.accept_at_bound = accept_at_bound ? 1u : 0u;
   double t[2][3] = {{1.0, 0.0, 0.0}, {1.0, 0.0, 0.0}};
   if (d.angular) for (int k = 0; k < 6; ++k) norm[k] = 0.0;   // (uploaded, never read: no uninitialised bytes on the wire)
   for (int im = 0; im < 2 && !d.angular; ++im) {   // conditioning.cpp:44-53
@@ -1234,7 +1240,7 @@ void geo_pair_constants(const GeoModelDesc& d, uint64_t start, uint32_t n, const
   // SQUARED angles as it is (robust_estimator_ACRansac.hpp:351-353: maxThreshold = precision * normalizer2()(0,0)^2, the identity here)
   // orthographic model: the value the functor hands to ACRANSAC (Eo_Robust.hpp:96-100: the mean of the two cameras'
   // imagePlane_toCameraPlaneError(precision^2)), per pair or one for all
-  g.max_threshold = d.bound_as_given ? bound : d.angular ? bound * M_PI / 180.0 : bound * bound * t[1][0] * t[1][0];
+  g.max_threshold = (d.bound_as_given || (bound_as_given && !d.angular)) ? bound : d.angular ? bound * M_PI / 180.0 : bound * bound * t[1][0] * t[1][0];
   g.loge0 = n > (uint32_t)d.min_samples ? std::log10((double)d.max_models * (n - d.min_samples)) : 0.0;
   g.bins_by_interval = kBins / (g.max_threshold - 0.0);
   const double val = (g.max_threshold - 0.0) / static_cast<double>(kBins - 1);
@@ -1264,7 +1270,7 @@ int geo_prepare_pairs(const GeoModelDesc& d, const GeoSource& src, const uint64_
       const uint32_t* wh2 = d.angular ? kNoSize : src.indexed ? image_wh + 2 * (size_t)J : image_wh + 4 * p + 2;
       const double* K1 = !d.calibrated ? nullptr : src.indexed ? src.K + 9 * (size_t)I : src.K + 18 * p;
       const double* K2 = !d.calibrated ? nullptr : src.indexed ? src.K + 9 * (size_t)J : src.K + 18 * p + 9;
-      geo_pair_constants(d, lo, n, wh1, wh2, K1, K2, src.pair_precision ? src.pair_precision[p] : opt->precision, hp[p], norm + 6 * p);
+      geo_pair_constants(d, lo, n, wh1, wh2, K1, K2, src.pair_precision ? src.pair_precision[p] : opt->precision, src.bound_as_given, src.accept_at_bound, hp[p], norm + 6 * p);
     }
   };
   std::vector<std::thread> pool;
@@ -1431,9 +1437,12 @@ void geo_result(const GeoModelDesc& d, bool ran, const GeoResult& r, const doubl
   o.ok = ran && (double)r.n_inliers > d.min_samples * 2.5;   // F_ACRobust.hpp:103, H_ACRobust.hpp:98
 }
 
+// A stage enqueued behind the estimation on the same stream, before the one download of the call (mvgx_relative_pose_robust.h)
+using GeoNextStage = std::function<int(GeoDevice&, hipStream_t)>;
+
 int geofilter_run(int device, int model, const GeoSource& src, const uint64_t* match_start, const uint32_t* image_wh,
                   uint64_t n_pairs, const mvgx_geofilter_options* opt, uint8_t* inlier_mask, mvgx_geofilter_result* results,
-                  mvgx_geofilter_stats* stats) {
+                  mvgx_geofilter_stats* stats, const GeoNextStage* next = nullptr) {
   using clock = std::chrono::steady_clock;
   const auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
   const GeoModelDesc d = geo_model(model);
@@ -1475,6 +1484,7 @@ int geofilter_run(int device, int model, const GeoSource& src, const uint64_t* m
   mark(1);
   if ((rc = dev.gather_normalize(d, src, stream)) || (rc = dev.launch(model, plan, form, opt->max_iterations, stream))) return rc;
   MVGX_HIP(hipEventRecord(e1, stream));
+  if (next && (rc = (*next)(dev, stream))) return rc;   // reads dev's results, mask and bearings where they are; its own downloads are drained below
   if ((rc = dev.download(hr, inlier_mask, stream))) return rc;
   mark(2);
   float kernel_ms = 0.f;
@@ -1699,3 +1709,4 @@ int mvgx_debug_five_point4(const double* b1, const double* b2, double* Es_out, i
 #include "mvgx_resection_loop.h"   // robust resection, the a-contrario loop: uses this unit's generator, bounded draw, logcombi and un-contracted operations
 #include "mvgx_resection.h"        // ... its P3P forms (exhaustive and bounded) and the host side, under the same pragma
 #include "mvgx_resection_dlt.h"    // ... and its form for a view without intrinsics (six-point DLT)
+#include "mvgx_relative_pose_robust.h"   // robustRelativePose: the E a-contrario stage above, then the cheirality stage of mvgx_ba.hip's unit
