@@ -814,6 +814,52 @@ int mvgx_relative_pose_robust(int device, const double* xI, const double* xJ, co
                               uint64_t* out_selected_start /* n_pairs + 1, or NULL */, uint32_t* out_selected /* or NULL */,
                               double* out_X /* or NULL */, mvgx_relative_pose_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Feature tracks from pairwise matches (no ABI bump: detect it by the symbol): the step between Matcher_Regions::Match + the
+ * geometric filter and triangulation / resection / relative pose -
+ *   tracks/tracks.hpp:62-197        tracks::TracksBuilder: Build (:70-121), Filter (:124-165), ExportToSTL (:178-196)
+ *   tracks/union_find.hpp:75-103    UnionFind::Union: by rank; on equal rank the first argument's root stays root
+ * as every engine calls it (sequential_SfM.cpp:273-285, sequential_SfM2.cpp:208-212: Filter() = 2; the global and stellar engines,
+ * structure from known poses, translation averaging and LiGT: Filter(3)).
+ * Input: the PairWiseMatches container in the layout mvgx_match_results and the `_indexed` filter entries use - `pairs` (I, J) in the
+ * order of a std::map<Pair, IndMatches> (strictly ascending, I < J), pair p owns the matches [match_start[p], match_start[p + 1]) of
+ * `ij` ((i, j) per match, in list order). match_mask: one byte per match, 0 drops it (a geometric filter's inlier_mask goes in as it
+ * is); NULL keeps all. n_features: features per image, or NULL - then taken from the largest index a kept match uses.
+ * Reproduced exactly (all outputs are integers): a node is a distinct (image, feature) of a kept match, its index its rank in ascending
+ * (image, feature) order; one Union(node(I, i), node(J, j)) per kept match in container order; a track's id is the node index of its
+ * final root (NOT the smallest node of the component); Filter drops whole every component in which an image occurs twice and every one
+ * with fewer than min_length images; surviving tracks come out in ascending id, (image, feature) in ascending image inside a track.
+ * Output, allocated by the library, each released with mvgx_host_free: track_id (n_tracks, ascending), track_start (n_tracks + 1
+ * offsets: the CSR layout mvgx_triangulate_tracks takes), obs_image / obs_feature (track_start[n_tracks] each). No pairs, empty lists
+ * or a mask that keeps nothing: MVGX_OK, zero tracks, track_start = {0}.
+ * MVGX_ERR_ARG (nothing allocated): pairs not strictly ascending, I >= J, an image index >= n_images, a kept match with a feature
+ * index >= n_features[image], a match_start that decreases, min_length < 2, NULL arrays. MVGX_ERR_UNSUPPORTED: the sum of n_features
+ * (or of the spans derived) does not fit 32 bits; 2^32 - 1 or more matches. Bit-identical from run to run.
+ * Memory: 8 bytes of device memory per key of the dense key space, which is the sum of n_features - or, with n_features == NULL, the sum
+ * over the images of (largest used index + 1): a few large sparse indices per image are legal there but cost gigabytes (an image whose
+ * largest used index is 10^9 takes 8 GB); pass n_features, or renumber the features, when the indices are sparse. About 60 bytes per node
+ * and 24 per match beside that. Matches repeated inside a list are legal (a Union of one set with itself) but each copy is replayed:
+ * a surviving track with k matches costs k^2 / 64 reads per lane. */
+typedef struct mvgx_tracks_options {
+  uint32_t min_length;             /* TracksBuilder::Filter(nLengthSupTo); default 2, the global engines pass 3 */
+} mvgx_tracks_options;
+typedef struct mvgx_tracks_stats {
+  uint64_t n_matches_used;         /* matches the mask keeps                                                     */
+  uint64_t n_nodes;                /* distinct (image, feature) among them                                       */
+  uint64_t n_components;
+  uint64_t n_collision;            /* components in which an image occurs twice                                  */
+  uint64_t n_short;                /* components without a collision, below min_length                           */
+  uint64_t n_tracks, n_obs;
+  uint64_t n_sweeps;               /* iterations of the component labelling: 2 whenever a match is kept (one unites, one confirms) */
+  double kernel_ms;                /* device time of all passes (HIP events; the host's waits between are not in it) */
+  double total_ms;                 /* the whole call incl. transfers                                             */
+} mvgx_tracks_stats;
+void mvgx_tracks_default_options(mvgx_tracks_options*);   /* 2 */
+int mvgx_tracks_build(int device, uint32_t n_images, const uint32_t* n_features /* n_images, or NULL */, const uint32_t* pairs /* n_pairs x 2 */,
+                      const uint64_t* match_start /* n_pairs + 1 */, const uint32_t* ij, const uint8_t* match_mask /* or NULL */, uint64_t n_pairs,
+                      const mvgx_tracks_options* opt, uint32_t* n_tracks, uint32_t** track_id, uint64_t** track_start, uint32_t** obs_image,
+                      uint32_t** obs_feature, mvgx_tracks_stats* stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

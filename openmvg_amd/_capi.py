@@ -174,6 +174,16 @@ class RelativePoseStats(C.Structure):
                 ("acransac_kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class TracksOptions(C.Structure):
+    _fields_ = [("min_length", C.c_uint32)]
+
+
+class TracksStats(C.Structure):
+    _fields_ = [("n_matches_used", C.c_uint64), ("n_nodes", C.c_uint64), ("n_components", C.c_uint64), ("n_collision", C.c_uint64),
+                ("n_short", C.c_uint64), ("n_tracks", C.c_uint64), ("n_obs", C.c_uint64), ("n_sweeps", C.c_uint64), ("kernel_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
 PROTOTYPES = {
     "mvgx_last_error": (C.c_char_p, []),
     "mvgx_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -286,6 +296,10 @@ PROTOTYPES = {
     "mvgx_relative_pose_robust": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                             C.POINTER(RelativePoseOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(RelativePoseStats)]),
+    "mvgx_tracks_default_options": (None, [C.POINTER(TracksOptions)]),
+    "mvgx_tracks_build": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TracksOptions),
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                    C.POINTER(TracksStats)]),
 }
 
 _lib = None

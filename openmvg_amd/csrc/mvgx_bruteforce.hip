@@ -1069,3 +1069,5 @@ int mvgx_cascade_results(mvgx_cascade_ctx* c, const uint64_t** offsets, const ui
 }
 
 }  // extern "C"
+
+#include "mvgx_tracks.h"   // feature tracks from pairwise matches (mvgx_tracks_build): uses scan_counts_kernel of mvgx_match_batch.h
