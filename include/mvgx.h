@@ -754,6 +754,9 @@ int mvgx_resection_localize_uncalibrated(int device, uint32_t n_problems, const 
  * flips U and V together can turn W into W^T, which swaps candidates 0 <-> 1 and 2 <-> 3. Nothing reported for an accepted pair depends
  * on that order (a tie for the first place rejects the pair: its ratio is 1); compare `cheirality` as a sorted tuple. t is u3 itself
  * (Pose3 stores the centre and returns -(R C)); n_selected == the largest entry of cheirality, always.
+ * That exchange is the only one: the signs of u2 v1^T - u1 v2^T and of u3 change together or not at all (the tests assert it).
+ * The decomposition does not depend on the scale of E (any finite double, subnormals included: the iteration runs on E times a power of
+ * two); the E reported is the one given. An E that is zero or has an entry that is not finite gives no pose: every count 0, ok 0.
  * A pair that is not ok: pose zeros, n_selected 0, nothing written to the lists (the reference leaves stale values, its callers drop
  * the pair). */
 #define MVGX_RELPOSE_PINHOLE 0

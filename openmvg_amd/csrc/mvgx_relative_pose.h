@@ -92,8 +92,24 @@ __device__ __forceinline__ void relpose_unit_norm(double E[9]) {
 // the columns ordered by length; u3 = u1 x u2 and v3 = v1 x v2 are the third columns the two determinant fixes leave (det U = det V = +1;
 // the third column of E V is zero for a true essential matrix and carries no direction). With W = [0 -1 0; 1 0 0; 0 0 1]:
 // U W V^T = u2 v1^T - u1 v2^T + u3 v3^T and U W^T V^T = u1 v2^T - u2 v1^T + u3 v3^T. Out: A = u2 v1^T - u1 v2^T, B = u3 v3^T, u3.
+// The iteration works on E times the power of two that brings its largest entry to [1, 2): its tests compare products of squared column
+// lengths, fourth powers of the scale of E, which overflow above 1e77 and vanish below 1e-81 while E itself is an ordinary double - and
+// the decomposition does not depend on the scale (the reference's JacobiSVD divides by the largest entry). A power of two changes no
+// mantissa, so E and 2^k E give the same bits by construction. (Against the iteration on E as given, the results are the same bits in
+// IEEE arithmetic; on the device they move by a unit or two in the last place)
+// An E with an entry that is not finite becomes all NaN here (no comparison with a NaN holds: no rotation, no point in front, every count
+// 0) - a NaN confined to one column would otherwise leave the two other columns to pass for a motion.
 __device__ __forceinline__ void relpose_motion(const double E[9], double A[9], double B[9], double u3[3]) {
-  double a00 = E[0], a01 = E[1], a02 = E[2], a10 = E[3], a11 = E[4], a12 = E[5], a20 = E[6], a21 = E[7], a22 = E[8];   // a_rc
+  double big = 0.0;
+  bool finite = true;
+#pragma unroll
+  for (int u = 0; u < 9; ++u) { big = fmax(big, fabs(E[u])); finite = finite && fabs(E[u]) < INFINITY; }
+  int ex = 1;
+  if (finite && big > 0.0) (void)frexp(big, &ex);   // big = f 2^ex, f in [0.5, 1) (a subnormal included)
+  double W[9];
+#pragma unroll
+  for (int u = 0; u < 9; ++u) W[u] = finite ? ldexp(E[u], 1 - ex) : NAN;   // (a select, not a sum: -0.0 stays -0.0)
+  double a00 = W[0], a01 = W[1], a02 = W[2], a10 = W[3], a11 = W[4], a12 = W[5], a20 = W[6], a21 = W[7], a22 = W[8];   // a_rc
   double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
 #pragma unroll 1
   for (int sweep = 0; sweep < kRelPoseSweeps; ++sweep) {
